@@ -54,7 +54,8 @@ CPU_P_REG = 1536         # map points per registration pass of the CPU baseline'
 PIXEL_ERR_VAR = 10.0      # Const::PIXEL_ERR_VAR, reference src/app/SL_GlobParam.cpp:37
 MAX_EPI_ERR = 6.0         # Const::MAX_EPI_ERR, :36
 HBM_PEAK_GBS = 8000.0
-SETUP_SECONDS = float(os.environ.get("BENCH_SETUP_SECONDS", "0.5"))   # untimed set-up run before the warm-up (see main)
+SETUP_SECONDS = float(os.environ.get("BENCH_SETUP_SECONDS", "0.5"))   # untimed set-up run before the warm-up, if BENCH_SETUP_SECONDS is set
+SETUP_ROUNDS_1 = 48       # N = 1: untimed set-up rounds (~0.5 s of the loop): a fixed count, so the timed frames are the same every run
 SEED = 0xC051A + 2
 
 
@@ -542,6 +543,21 @@ def _render_one(job):
     return _SCENE.render(*job)
 
 
+def dump_outputs(out_dir, loop, frame):
+    """What the loop hands its caller after frame `frame` (the last timed step), as float64 .npy files: every camera's pose, its feature
+    slots (positions, track state, map point, static or not) and the map points in use with their covariances and flags.  Rank 0 holds
+    all cameras' records at N > 1 too.  A few hundred KB in all."""
+    loop.drain()
+    n_map = int(loop.d_mapcount.item())
+    b = frame & 1                      # frame i writes pose buffer i & 1
+    arrs = {"R": loop.d_R[b].reshape(loop.cfg.n_cams, 3, 3), "t": loop.d_t[b], "feature_xy": loop.d_xy, "feature_state": loop.d_state,
+            "feature_map_point": loop.d_slot2map, "feature_is_static": loop.d_isstatic, "map_points": loop.d_map[:n_map],
+            "map_cov": loop.d_cov.reshape(-1, 9)[:n_map], "map_flags": loop.d_mapflags[:n_map]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -578,8 +594,8 @@ def main():
     ap.add_argument("--no-upload-leg", action="store_true", help="skip the upload-inclusive repetition of the loop (config.with_upload)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (cfg2, cfg5 BA, cfg5 KLT, reference-default KLT)")
     ap.add_argument("--setup-rounds", type=int, default=int(os.environ.get("BENCH_SETUP_ROUNDS", "-1")),
-                    help="untimed set-up rounds of 4 key-frame intervals in front of the warm-up; -1 = N = 1: run for BENCH_SETUP_SECONDS, "
-                         "N > 1: 12 (every rank must take the same number of steps)")
+                    help="untimed set-up rounds of 4 key-frame intervals in front of the warm-up; -1 = N = 1: 48 (or, with "
+                         "BENCH_SETUP_SECONDS set, as many as fit in that many seconds), N > 1: 12 (every rank must take the same number of steps)")
     ap.add_argument("--klt-xcd-placement", type=int, default=int(os.environ.get("BENCH_KLT_XCD", "1")),
                     help="1: the persistent tracker numbers its workgroups so that a camera lands on its own XCD; 0: cameras as grid rows")
     ap.add_argument("--live-pmc", type=int, default=int(os.environ.get("BENCH_LIVE_PMC", "1")),
@@ -603,6 +619,9 @@ def main():
                     help="> 0: the pose stream confined to the last that many CU-mask bits; experiment")
     ap.add_argument("--klt-after-intracam", type=int, default=int(os.environ.get("BENCH_KLT_AFTER_INTRACAM", "0")),
                     help="1: the tracker of frame i + 1 starts behind frame i's intraCamEstimate (the pose solve runs on an empty chip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the timed loop's last step left (poses, feature records, map) as DIR/<name>.npy "
+                         "(float64); the frames, the set-up and the steps are fixed by the arguments, so two builds can be compared output for output")
     ap.add_argument("--native-comm", type=int, default=1, help="N > 1: collectives issued by libcoslam_hip (RCCL behind the C-ABI) instead of torch.distributed")
     args = ap.parse_args()
 
@@ -722,7 +741,7 @@ def main():
     # intervals, ending on a key-frame boundary.
     t_su = time.perf_counter()
     rounds = 0
-    fixed_rounds = args.setup_rounds if args.setup_rounds >= 0 else (12 if world > 1 else -1)
+    fixed_rounds = args.setup_rounds if args.setup_rounds >= 0 else (12 if world > 1 else -1 if "BENCH_SETUP_SECONDS" in os.environ else SETUP_ROUNDS_1)
     run((-n_done) % max(ke, 1))
     while (rounds < fixed_rounds) if fixed_rounds >= 0 else (time.perf_counter() - t_su < SETUP_SECONDS):
         run(4 * max(ke, 1))
@@ -756,6 +775,8 @@ def main():
     t_host = time.perf_counter() - t_begin
     barrier()
     dt = time.perf_counter() - t_begin
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loop, n_done)
     if prof is not None:
         import pstats
         prof.disable()

@@ -101,7 +101,11 @@ class LoopConfig:
         self.klt_after_intracam = False   # the tracker of frame i + 1 starts behind frame i's intraCamEstimate: the pose solve -- one
         # workgroup per camera, a latency chain of ~20 LM steps -- then runs on an otherwise empty chip instead of beside the
         # persistent tracker's resident waves ("what the pose stream pays for co-residency")
-        self.device_wait = True    # the BA result's apply waits for the solve on the device (cs_ba_output_wait_dev), not on the host
+        # True: the BA result's apply waits for the solve on the device (cs_ba_output_wait_dev).  Off by default: when the runtime maps the
+        # pose stream and a solve's worker stream onto one hardware queue, the solve's kernels queue behind the spinning wait and the
+        # wait can only end by timing out (2 s, counted by wait_errors).  The host wait returns once the worker has synchronised its
+        # stream behind the pack (the record is complete); with the apply lag the solve is long done by then.
+        self.device_wait = False
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError(f"LoopConfig: unknown field {k}")
