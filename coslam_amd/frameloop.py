@@ -148,6 +148,10 @@ class FrameLoop:
         self.c0 = c0 = rank * nc
         self.my_cams = list(range(c0, c0 + nc))
         self.lag = cfg.ba_lag if cfg.ba_lag > 0 else min(max(world, 2), 4)
+        if cfg.keyframe_drives and cfg.keyframe_lag > 0 and cfg.keyframe_lag >= self.lag * cfg.key_every:
+            # a window's apply is keyed lag * key_every frames behind its key frame, which the decision places keyframe_lag frames late: the
+            # apply would be due in the past and bundle adjustment silently off
+            raise ValueError(f"LoopConfig.keyframe_lag {cfg.keyframe_lag}: must be below the BA apply lag of {self.lag} x {cfg.key_every} frames")
         if (cfg.n_key_frames - 1 + self.lag) * cfg.key_every + 1 > cfg.hist:
             raise ValueError("the pose history is shorter than a window + its apply lag")
         dev = self.dev = torch.device("cuda", device)

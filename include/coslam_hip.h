@@ -136,7 +136,8 @@ int cs_klt_enable_graphs(cs_klt* k, int on);
  * neighbours exchange gains through 8-byte {tag, beta} granules; 0 = one launch per Gauss-Newton pass as the reference
  * schedules its shader (v3d_gpuklt.cpp:254-287).  Both give bit-identical results.  The persistent schedule needs every
  * wave co-resident (checked against the occupancy the runtime reports); otherwise the per-pass schedule runs.
- * Env COSLAM_KLT_FUSED=0 sets the default to 0. */
+ * The library reads no environment variable for this; the C++ frame loop (tools/cxx/frame_loop.cpp) calls it with 0 under
+ * COSLAM_KLT_FUSED=0. */
 int cs_klt_set_fused(cs_klt* k, int on);
 /* compute units available to the handle's stream when it carries a CU mask (co-residency budget of the persistent tracker) */
 int cs_klt_set_cu_count(cs_klt* k, int n_cus);

@@ -164,6 +164,12 @@ def test_cxx_frame_loop_on_two_ranks_ends_in_the_one_rank_runs_map(hip, tmp_path
     # counterpart): the C++ loop places the key frames the Python loop places on the same frames, requests and applies their windows, and two
     # C++ ranks -- each reading its own replica's decision -- end in the one-rank run's state
     kf_env = dict(base, COSLAM_KEYFRAME_DRIVES="1", COSLAM_KEYFRAME_LAG="1", COSLAM_KEYFRAME_RATIO="1.5")
+    # a decision lag of a whole apply lag (2 key-frame intervals of 5 frames) would key every window's apply in the past: refused with the
+    # loop's other argument errors, before any GPU work; one frame less is accepted
+    bad = subprocess.run([exe, wl, steps, warm, "0", "2"], env=dict(kf_env, COSLAM_KEYFRAME_LAG="10"), capture_output=True, text=True, timeout=120)
+    assert bad.returncode == 1 and "COSLAM_KEYFRAME_LAG=10" in bad.stderr, (bad.returncode, bad.stderr[-2000:])
+    ok9 = subprocess.run([exe, wl, steps, warm, "0", "2"], env=dict(kf_env, COSLAM_KEYFRAME_LAG="9"), capture_output=True, text=True, timeout=600)
+    assert ok9.returncode == 0 and line(ok9.stdout)["keyframe_lag"] == 9, ok9.stderr[-2000:]
     kd = subprocess.run([exe, wl, steps, warm, "0", "2"], env=kf_env, capture_output=True, text=True, timeout=600)
     assert kd.returncode == 0, kd.stderr[-2000:]
     jk = line(kd.stdout)

@@ -127,6 +127,14 @@ def test_the_decision_places_the_key_frames_without_a_host_wait_per_frame(hip):
                      keyframe_ratio=1.2, keyframe_lag=D)
     loop = FrameLoop(cfg, sc, video, None, bench.klt_config(), bench.reg_covariances(len(sc.points)), rank=0, world=1, device=0,
                      associate=bench.associate)
+    # a decision lag of a whole apply lag would key every window's apply in the past (bundle adjustment silently off): refused before any
+    # GPU work
+    late = LoopConfig(n_cams=NA, W=bench.W, H=bench.H, levels=bench.LEVELS, fw=bench.FW, fh=bench.FH, pts_stride=bench.PTS_STRIDE,
+                      n_col_blk=bench.N_COL_BLK, n_row_blk=bench.N_ROW_BLK, key_every=bench.KEY_EVERY, p_reg=bench.P_REG, keyframe_drives=True,
+                      keyframe_ratio=1.2, keyframe_lag=loop.lag * cfg.key_every)
+    with pytest.raises(ValueError, match="keyframe_lag"):
+        FrameLoop(late, sc, video, None, bench.klt_config(), bench.reg_covariances(len(sc.points)), rank=0, world=1, device=0,
+                  associate=bench.associate)
     loop.first_frame()
     BASE, T = 60, 300
     for i in range(1, BASE + 1):

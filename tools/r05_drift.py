@@ -15,7 +15,7 @@ variant and, every --every frames, drains the device and logs
     bookkeeping                           static mapped features per camera (on initial / on new points), pose correspondences, LM
                                           steps of intraCamEstimate, map points false / in use, attachments of the registration
 
-as JSON lines (one per sample) to --out.  tools/r05_drift.sh runs the variants one process each; profiles/r05_drift_*.jsonl are
+as JSON lines (one per sample) to --out.  The variants ran one process each; profiles/r05_drift_*.jsonl are
 its outputs, profiles/r05_drift_summary.md the table DESIGN.md quotes.  GPU only (the HIP path has no CPU fallback).
 """
 import argparse
