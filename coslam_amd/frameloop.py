@@ -22,10 +22,34 @@ inputs, the replicas never diverge: there is ONE map, held N times.  What is sha
 the pose solve, the registration search, the NCC cutter.  What added GPUs buy on the key-frame side is TIME: a rank solves every N-th
 window and has N key-frame intervals for it, so the solve's latency chain leaves the frame's critical path.
 The apply lag makes a run reproducible (the reference applies a result whenever its BA thread gets the lock, :1713-1720).
+
+The set-up and the frame are split into the stages of tools/cxx/frame_loop.cpp (setup_state ... setup_keyframe_solves, step,
+keyframe_decision_step, ncc_leg, register_frame, key-frame actions), so that the two loops can be read side by side.
 """
+import contextlib
 import ctypes as C
+import hashlib
+import os
+import sys
+import time
 
 import numpy as np
+
+import coslam_amd
+from coslam_amd._lib import check
+from coslam_amd.ba import BAInterCam, BAOutput, BAWindow, BAWorkspace, intercam_cams
+from coslam_amd.handback import handback_cams, handback_dev
+from coslam_amd.keyframe import keyframe_cams, keyframe_ready_dev, keyframe_snapshot_dev
+from coslam_amd.ncc import (NCC_PAIR_DTYPE, ncc_cams, ncc_epi_pairs_group_dev, ncc_fmats_dev, ncc_get_blocks_group_dev, ncc_pair_jobs,
+                            ncc_scaled_dims)
+from coslam_amd.newpts import NewPtsJob, ncc_candidate_mask_dev, newpts_from_pairs_dev, newpts_scratch_bytes
+from coslam_amd.pose import intraCamEstimate_batch_dev
+from coslam_amd.poseupdate import TrackHistory, poseupdate_cams
+from coslam_amd.register import (register_cams, register_cur_static_sequential_dev, register_decide_kinds_rounds_dev,
+                                 register_decide_scratch_bytes, register_decide_static_dev, register_list_current_dev, register_passes,
+                                 register_revisit_decide_dev, register_revisit_decide_next_dev, register_revisit_list_dev,
+                                 register_search_passes_dev)
+from coslam_amd.synth import csr_of_problem
 
 PIXEL_ERR_VAR = 10.0      # Const::PIXEL_ERR_VAR, reference src/app/SL_GlobParam.cpp:37
 MAX_EPI_ERR = 6.0         # Const::MAX_EPI_ERR, :36
@@ -36,7 +60,6 @@ class LoopConfig:
         self.n_cams, self.W, self.H, self.levels, self.fw, self.fh = 8, 640, 480, 4, 50, 40
         self.pts_stride, self.n_col_blk, self.n_row_blk = 192, 16, 12    # reference src/app/SL_SingleSLAM.h:36-37
         self.key_every, self.n_key_frames = 5, 5                         # requestForBA(5, 2, 2, 30), SL_CoSLAM.cpp:1345
-        self.ic_workers = 1        # workspaces (worker threads) the inter-camera solves of this rank rotate over (2 on one GPU: measured slower)
         self.ba_lag = 0            # key-frame intervals between a window's key frame and the frame its result is applied; 0 = min(max(N, 2), 4)
         self.p_reg = 4096          # cap on the frame's CURRENT map points (the registration's list: cs_register_list_current_dev)
         self.hist = 64             # depth of the bounded walks (dynamic test, classification, re-triangulation; the mergability walk's exact window)
@@ -76,12 +99,10 @@ class LoopConfig:
         self.fused_registration = True   # the registration's launches fused as tools/cxx/frame_loop.cpp runs them: the second visits' lists built by the
         # walks (cs_register_decide_kinds_rounds_dev, cs_register_revisit_decide_next_dev), advance + refine as one launch
         # (cs_feat_ref_advance_refine_dev); needs feature_chains.  False: a launch per step (the form DESIGN.md 3.13.1 describes first)
-        self.merge_refs = True       # the bMerge walks read and write the references too (checkUnify over stale features and chains, the hand-over as the
-        # reference's loop over pFeatures does it: cs_track_history_set_merge_refs)
-        self.classify_refs = True    # mapPointsClassify reads the references too (stale features, linked segments: cs_track_history_set_classify_refs)
         self.feature_chains = True   # MapPoint::pFeatures kept as feature references (cs_feat_ref): a camera that lost a point still contributes
         # its last feature to refineMapPoint / updateNewPosesPoints, and a point registered to a new track where it held an older feature has
-        # the old chain linked behind it (reference src/app/SL_CoSLAM.cpp:775-779); False: the features of this frame on their own tracks
+        # the old chain linked behind it (reference src/app/SL_CoSLAM.cpp:775-779); mapPointsClassify and the bMerge walks read the references
+        # too (cs_track_history_set_classify_refs / _set_merge_refs).  False: the features of this frame on their own tracks
         self.klt_fused = True      # False: one launch per Gauss-Newton pass (bit-identical): for SEVERAL processes sharing one GPU, where the
                                    # persistent tracker's co-residency budget does not hold
         self.prefetch = True
@@ -125,12 +146,6 @@ class FrameLoop:
     def __init__(self, cfg, scene, video, ic, klt_cfg, map_cov, rank=0, world=1, device=0, dist_backend="nccl", associate=None):
         import torch
 
-        import coslam_amd
-        from coslam_amd.ba import BAOutput, BAWindow, BAWorkspace
-        from coslam_amd.handback import handback_cams
-        from coslam_amd.poseupdate import TrackHistory, poseupdate_cams
-        from coslam_amd.register import register_cams, register_passes
-
         self.torch = torch
         self.cfg, self.sc, self.ic = cfg, scene, ic
         if cfg.pixel_err_reading not in ("variance", "std"):
@@ -138,15 +153,15 @@ class FrameLoop:
         self.sig = (lambda v: float(np.sqrt(v))) if cfg.pixel_err_reading == "variance" else (lambda v: float(v))
         self.sig_pix = self.sig(PIXEL_ERR_VAR)   # what the helpers get where the reference passes Const::PIXEL_ERR_VAR
         self.rank, self.world, self.device = rank, world, device
-        NA, N = cfg.n_cams, cfg.n_feat
+        NA = cfg.n_cams
         if NA % world:
             raise ValueError(f"{NA} cameras do not shard over {world} ranks")
         if cfg.keyframe_drives and world > 1 and cfg.keyframe_lag <= 0:
             raise ValueError("LoopConfig.keyframe_drives: one rank only (the host reads the decision back every frame); keyframe_lag > 0 has every "
                              "rank read its replica's decision")
-        self.nc = nc = NA // world
-        self.c0 = c0 = rank * nc
-        self.my_cams = list(range(c0, c0 + nc))
+        self.nc = NA // world
+        self.c0 = rank * self.nc
+        self.my_cams = list(range(self.c0, self.c0 + self.nc))
         self.lag = cfg.ba_lag if cfg.ba_lag > 0 else min(max(world, 2), 4)
         if cfg.keyframe_drives and cfg.keyframe_lag > 0 and cfg.keyframe_lag >= self.lag * cfg.key_every:
             # a window's apply is keyed lag * key_every frames behind its key frame, which the decision places keyframe_lag frames late: the
@@ -154,24 +169,42 @@ class FrameLoop:
             raise ValueError(f"LoopConfig.keyframe_lag {cfg.keyframe_lag}: must be below the BA apply lag of {self.lag} x {cfg.key_every} frames")
         if (cfg.n_key_frames - 1 + self.lag) * cfg.key_every + 1 > cfg.hist:
             raise ValueError("the pose history is shorter than a window + its apply lag")
-        dev = self.dev = torch.device("cuda", device)
+        self.dev = torch.device("cuda", device)
         self.T = int(next(iter(video.values())).shape[0])
         self.video = video
         self.associate = associate
-        # the map: structure-of-arrays with spare capacity (new map points are appended: cs_newpts_from_pairs_dev); unused entries carry
-        # no feature anywhere, which makes them inert for every kernel
-        n_pts = len(scene.points)
+        self._timing = {} if os.environ.get("FRAMELOOP_TIMING") else None   # (diagnostic: host seconds per section)
+        # (diagnostic, FRAMELOOP_GPU_SECTIONS=1: events on the pose stream at the sections' boundaries -> gpu_sections(): untraced GPU time
+        # of every section of a frame, by kind of frame.  Not a valid bench line: two events per section cost a few microseconds each.)
+        self._marks = [] if os.environ.get("FRAMELOOP_GPU_SECTIONS") else None
+        # (the stages in the order of their device allocations and stream creation: the order is part of what a run computes and how fast)
+        self.setup_state(map_cov)
+        self.setup_trackers(klt_cfg)
+        self.setup_comm(dist_backend)
+        self.setup_cameras()
+        self.setup_registration()
+        self.setup_keyframe_solves()
+        self._init_ncc()
+
+    # ---------------------------------------------------------------------------------------------------------------
+    def _z(self, shape, dt):
+        return self.torch.zeros(shape, dtype=dt, device=self.dev)
+
+    def setup_state(self, map_cov):
+        """the map: structure-of-arrays with spare capacity (new map points are appended: cs_newpts_from_pairs_dev; unused entries carry
+        no feature anywhere, which makes them inert for every kernel) -- the ONE map (a replica per rank) -- and every camera's records"""
+        torch, cfg, sc, dev, z = self.torch, self.cfg, self.sc, self.dev, self._z
+        NA, N = cfg.n_cams, cfg.n_feat
+        n_pts = len(sc.points)
         n_map = self.n_map = n_pts + cfg.map_spare
         f64, i32, u8 = torch.float64, torch.int32, torch.uint8
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
-        K = np.ascontiguousarray(scene.K, dtype=np.float64)
+        K = np.ascontiguousarray(sc.K, dtype=np.float64)
         self.d_K = torch.from_numpy(np.tile(K.ravel(), NA)).to(dev)
         self.d_K1 = torch.from_numpy(K.ravel().copy()).to(dev)
         self.d_iK1 = torch.from_numpy(np.linalg.inv(K).ravel().copy()).to(dev)
         self.d_kud = z(7, f64)
-        # ---- the ONE map (a replica per rank) and every camera's records
         self.d_map = z((n_map, 3), f64)
-        self.d_map[:n_pts] = torch.from_numpy(np.ascontiguousarray(scene.points, dtype=np.float64).copy()).to(dev)
+        self.d_map[:n_pts] = torch.from_numpy(np.ascontiguousarray(sc.points, dtype=np.float64).copy()).to(dev)
         self.d_cov = z(n_map * 9, f64)
         self.d_cov[:n_pts * 9] = torch.from_numpy(np.ascontiguousarray(map_cov, dtype=np.float64).reshape(-1)[:n_pts * 9].copy()).to(dev)
         self.d_mapcount = torch.tensor([n_pts], dtype=i32, device=dev)
@@ -185,12 +218,12 @@ class FrameLoop:
         self.d_npts, self.d_opt, self.d_ok = z(NA, i32), z((NA, 96), u8), z(NA, i32)
         self.d_isstatic, self.d_reproj = torch.ones((NA, N), dtype=u8, device=dev), z((NA, N), f64)
         self.d_pf = torch.full((n_map, NA), -1, dtype=i32, device=dev)          # MapPoint::pFeatures of this frame (hand-back)
-        R0 = np.stack([scene.pose(c, 0)[0].ravel() for c in range(NA)])
-        t0 = np.stack([scene.pose(c, 0)[1] for c in range(NA)])
+        R0 = np.stack([sc.pose(c, 0)[0].ravel() for c in range(NA)])
+        t0 = np.stack([sc.pose(c, 0)[1] for c in range(NA)])
         self.d_R = [torch.from_numpy(R0.copy()).to(dev), torch.from_numpy(R0.copy()).to(dev)]   # pose ping-pong: frame i reads [(i+1)&1]
         self.d_t = [torch.from_numpy(t0.copy()).to(dev), torch.from_numpy(t0.copy()).to(dev)]
-        self.d_dests = [[z(N * 5, i32) for _ in range(nc)] for _ in range(2)]
-        self.d_counts = [z(4, i32) for _ in range(nc)]
+        self.d_dests = [[z(N * 5, i32) for _ in range(self.nc)] for _ in range(2)]
+        self.d_counts = [z(4, i32) for _ in range(self.nc)]
         self.d_cls_counts, self.d_apply_counts = z(2, i32), z(3, i32)
         # the registration's tables: indexed by the MAP index (whole-map tables); the frame's current points as a compact list
         self.d_mergeable = z((n_map, NA), u8)
@@ -199,7 +232,10 @@ class FrameLoop:
         self.d_curlist, self.d_curcount = torch.full((n_map,), -1, dtype=i32, device=dev), z(1, i32)
         self.d_curoverflow = z(1, i32)   # current points beyond the list's cap (left out of that frame's registration; 0 in every bench configuration)
         self.d_merge_counts = z(4, i32)   # running mergability: cache hits, full tail walks, verdicts 2, tail terms (summed over the run)
-        # ---- streams
+
+    def setup_trackers(self, klt_cfg):
+        """the two streams and the trackers of the own cameras as one group"""
+        torch, cfg, dev, device = self.torch, self.cfg, self.dev, self.device
         self.klt_s, self.pose_s = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)   # (equal priorities: a high-priority pose or
         # tracker stream halves the rate, 2188 -> 942 / 906 frames/s: profiles/r04_ab_runs.txt)
         if cfg.klt_cus > 0 or cfg.pose_cus > 0:
@@ -220,7 +256,6 @@ class FrameLoop:
         self.intracam_done = [torch.cuda.Event(), torch.cuda.Event()]
         self.klt_done = [torch.cuda.Event(), torch.cuda.Event()]
         self.dest_free = [torch.cuda.Event(), torch.cuda.Event()]
-        # ---- trackers of the own cameras
         self.trks = []
         for _ in self.my_cams:
             t = coslam_amd.KLT_SequenceTracker(klt_cfg, device=device)
@@ -238,33 +273,42 @@ class FrameLoop:
         elif cfg.klt_cus > 0:
             for t in self.trks:   # the persistent tracker's co-residency budget = the CUs its stream may use
                 t.set_cu_count(int(cfg.klt_cus))
-        # ---- multi-GPU exchange
-        self.xchg = self.native = None
-        if world > 1:
-            from coslam_amd import multicam
+        self.stage_slot, self.h_frames = {}, None   # (step(upload=True): the caller's pinned frames, staged two frames ahead)
 
-            self.native_fallback = None
-            if cfg.native_comm and dist_backend == "nccl":
-                # the library's own RCCL communicators; if ANY rank cannot bring them up, ALL ranks use torch.distributed's collectives
-                # instead (agreed through one all-reduce) -- said loudly: stderr here, `collectives` in bench.py's line
-                import torch.distributed as dist_
+    def setup_comm(self, dist_backend):
+        """N > 1: the exchange of every camera's records and poses, over the library's own RCCL communicators -- if ANY rank cannot bring
+        them up, ALL ranks use torch.distributed's collectives instead (agreed through one all-reduce), said loudly: stderr here,
+        `collectives` in bench.py's line"""
+        self.xchg = self.native = self.native_fallback = None
+        if self.world == 1:
+            return
+        from coslam_amd import multicam
 
-                err = None
-                try:
-                    self.native = multicam.NativeComm(world, rank, device)
-                except coslam_amd.CoslamHipError as ex:
-                    err = str(ex)
-                ok = torch.tensor([0 if err else 1], dtype=torch.int32, device=dev)
-                dist_.all_reduce(ok, op=dist_.ReduceOp.MIN)
-                if int(ok.item()) == 0:
-                    if self.native is not None:
-                        self.native.close()
-                        self.native = None
-                    self.native_fallback = err or "another rank could not create its communicator"
-                    print(f"[frameloop rank {rank}] libcoslam_hip's RCCL communicator is not available ({self.native_fallback}): "
-                          "torch.distributed collectives instead", file=__import__("sys").stderr, flush=True)
-            self.xchg = multicam.CameraExchange(N * nc, dev, native=self.native, cams_per_rank=nc)
-        # ---- per-camera argument tables (built once)
+        if self.cfg.native_comm and dist_backend == "nccl":
+            import torch.distributed as dist_
+
+            err = None
+            try:
+                self.native = multicam.NativeComm(self.world, self.rank, self.device)
+            except coslam_amd.CoslamHipError as ex:
+                err = str(ex)
+            ok = self.torch.tensor([0 if err else 1], dtype=self.torch.int32, device=self.dev)
+            dist_.all_reduce(ok, op=dist_.ReduceOp.MIN)
+            if int(ok.item()) == 0:
+                if self.native is not None:
+                    self.native.close()
+                    self.native = None
+                self.native_fallback = err or "another rank could not create its communicator"
+                print(f"[frameloop rank {self.rank}] libcoslam_hip's RCCL communicator is not available ({self.native_fallback}): "
+                      "torch.distributed collectives instead", file=sys.stderr, flush=True)
+        self.xchg = multicam.CameraExchange(self.cfg.n_feat * self.nc, self.dev, native=self.native, cams_per_rank=self.nc)
+
+    def setup_cameras(self):
+        """the per-camera argument tables of the hand-back, the pose update and the registration search (built once), and the track
+        history with the feature references"""
+        torch, cfg, z = self.torch, self.cfg, self._z
+        NA, N, nc, c0, n_map = cfg.n_cams, cfg.n_feat, self.nc, self.c0, self.n_map
+
         def hb_cam(g, dest):
             return dict(dest=dest, K=self.d_K1.data_ptr(), kud=self.d_kud.data_ptr(), mapPts=self.d_map.data_ptr(),
                         slot2map=self.d_slot2map[g].data_ptr(), trackSpan=self.d_trackspan[g].data_ptr(), xy=self.d_xy[g].data_ptr(),
@@ -274,24 +318,24 @@ class FrameLoop:
 
         self.hb_own = [handback_cams([hb_cam(c0 + i, self.d_dests[b][i].data_ptr()) for i in range(nc)]) for b in range(2)]
         self.hb_other = None
-        if world > 1:
+        if self.world > 1:
             others = [g for g in range(NA) if g not in self.my_cams]
-            self.hb_other = handback_cams([hb_cam(g, self.xchg.record_ptr(g, device)) for g in others])
+            self.hb_other = handback_cams([hb_cam(g, self.xchg.record_ptr(g, self.device)) for g in others])
         # (the window's push reads xy / state / slot2map of every camera; dest is not looked at)
         self.hb_all = handback_cams([hb_cam(g, self.d_dests[0][0].data_ptr()) for g in range(NA)])
         self.dest_ptrs = [[d.data_ptr() for d in self.d_dests[b]] for b in range(2)]
         self.cnt_ptrs = [c.data_ptr() for c in self.d_counts]
         self.img_ptrs = [[self.video[c][f].data_ptr() for c in self.my_cams] for f in range(self.T)]
-        self.pose_upd = self.d_fref = None
+        self.pose_upd = self.d_fref = self.d_rstat = None
         if cfg.with_pose_update:
-            self.pose_upd = TrackHistory(NA, N, cfg.hist, device=device, storeLen=max(cfg.hist_store, cfg.hist))
-            self.d_merge_cache = z(self.pose_upd.mergability_cache_bytes(n_map), u8)
-            self.d_fref = torch.full((n_map, NA, 4), -1, dtype=i32, device=dev) if cfg.feature_chains else None
-            self.d_rstat = z((n_map, NA), u8) if cfg.feature_chains else None
-            self.d_fref_counts = z(5, i32)   # tracked on, first features, re-linked, links dropped (pool full), detached -- summed over the run
-            if self.d_fref is not None and cfg.classify_refs:
+            self.pose_upd = TrackHistory(NA, N, cfg.hist, device=self.device, storeLen=max(cfg.hist_store, cfg.hist))
+            self.d_merge_cache = z(self.pose_upd.mergability_cache_bytes(n_map), torch.uint8)
+            if cfg.feature_chains:
+                self.d_fref = torch.full((n_map, NA, 4), -1, dtype=torch.int32, device=self.dev)
+                self.d_rstat = z((n_map, NA), torch.uint8)
+            self.d_fref_counts = z(5, torch.int32)   # tracked on, first features, re-linked, links dropped (pool full), detached -- summed over the run
+            if self.d_fref is not None:   # the classification and the bMerge walks read the references too
                 self.pose_upd.set_classify_refs(self.d_fref.data_ptr(), self.d_rstat.data_ptr())
-            if self.d_fref is not None and cfg.merge_refs:
                 self.pose_upd.set_merge_refs(self.d_fref.data_ptr(), self.d_rstat.data_ptr())
             self.pu_args = poseupdate_cams([dict(K=self.d_K1.data_ptr(), iK=self.d_iK1.data_ptr(), xy=self.d_xy[g].data_ptr(),
                                                  state=self.d_state[g].data_ptr(), slot2map=self.d_slot2map[g].data_ptr(),
@@ -301,9 +345,13 @@ class FrameLoop:
                                              xy=self.d_xy[g].data_ptr(), state=self.d_state[g].data_ptr(),
                                              slot2map=self.d_slot2map[g].data_ptr(), isStatic=self.d_isstatic[g].data_ptr())
                                         for g in range(NA)]) for b in range(2)]
-        # CoSLAMThread.cpp:117 currentMapPointsRegister, search step: ONE pass over the frame's current points (the list), wherever they sit
-        # in the map -- the points genNewMapPoints appended this frame included; it serves the static AND the dynamic registration (the
-        # certainly dynamic points are searched with their own scale, SL_CoSLAM.cpp:973)
+
+    def setup_registration(self):
+        """CoSLAMThread.cpp:117 currentMapPointsRegister, search step: ONE pass over the frame's current points (the list), wherever they sit
+        in the map -- the points genNewMapPoints appended this frame included; it serves the static AND the dynamic registration (the
+        certainly dynamic points are searched with their own scale, SL_CoSLAM.cpp:973) -- and the second visits' rounds behind it"""
+        torch, cfg, z = self.torch, self.cfg, self._z
+        NA, n_map, i32, f64 = cfg.n_cams, self.n_map, torch.int32, torch.float64
         o_ = self.reg_out
         # (maxDist only scales every distance of a search alike -- searchMahaNearestFeatPt compares them with nothing: the reference's literal)
         cur_pass = dict(P=cfg.p_reg, sigmaSearch=self.sig_pix, maxDist=3 * PIXEL_ERR_VAR, sigmaMerge=self.sig_pix, M=self.d_map.data_ptr(),
@@ -315,92 +363,84 @@ class FrameLoop:
             # (diagnostic: the search half of activeMapPointsRegister as rounds 2-4 ran it -- points p_act0 .. + 1536 searched with the
             # active loop's scale, their tables read by nothing)
             self.act_out = dict(slot=z((1536, NA), i32), m=z((1536, NA, 2), f64), var=z((1536, NA, 4), f64), dist=z((1536, NA), f64),
-                                flags=z((1536, NA), i32), pf=torch.full((1536, NA), -1, dtype=i32, device=dev))
+                                flags=z((1536, NA), i32), pf=torch.full((1536, NA), -1, dtype=i32, device=self.dev))
             a_ = self.act_out
             passes.append(dict(P=1536, sigmaSearch=self.sig(2.5 * PIXEL_ERR_VAR), maxDist=3 * PIXEL_ERR_VAR, sigmaMerge=self.sig_pix,
                                M=self.d_map.data_ptr() + 24 * 1536, cov=self.d_cov.data_ptr() + 72 * 1536, pointFeat=a_["pf"].data_ptr(),
                                slot=a_["slot"].data_ptr(), m=a_["m"].data_ptr(), var=a_["var"].data_ptr(), dist=a_["dist"].data_ptr(),
                                flags=a_["flags"].data_ptr()))
         self.reg_passes = register_passes(passes)
+        self._pass_current = (type(self.reg_passes[0]) * 1)(self.reg_passes[0])   # (the sequential registration's copy of the current pass)
         # the second visits' rounds (cfg.revisit_rounds): their own short list, the same tables (rows of listed points only are rewritten)
         self.RV_CAP = 1024
-        self.d_rvlist = torch.full((self.RV_CAP,), -1, dtype=i32, device=dev)
+        self.d_rvlist = torch.full((self.RV_CAP,), -1, dtype=i32, device=self.dev)
         self.d_rv_visit, self.d_rv_next = z(n_map, i32), z(n_map, i32)
         self.d_rv_reg = [z(n_map, torch.uint8), z(n_map, torch.uint8)]
         self.d_rv_counts, self.d_rv_listcounts = z(4, i32), z(4, i32)
         self.rv_pass = register_passes([dict(cur_pass, P=self.RV_CAP, list=self.d_rvlist.data_ptr())])
         # the fused form (LoopConfig.fused_registration): a list per round, built by the walks themselves
         nr = max(cfg.revisit_rounds, 1)
-        self.d_rvlists = torch.full((nr, self.RV_CAP), -1, dtype=i32, device=dev)
+        self.d_rvlists = torch.full((nr, self.RV_CAP), -1, dtype=i32, device=self.dev)
         self.d_rvcounts = z(nr + 1, i32)
         self.rv_passes = [register_passes([dict(cur_pass, P=self.RV_CAP, list=self.d_rvlists[r].data_ptr())]) for r in range(nr)]
-        # ---- key-frame solves
-        # the inter-camera solves of consecutive key frames are independent of each other (each starts from its own frame's poses):
-        # key frame k of this rank goes to workspace k mod ic_workers, each with its own worker thread, stream and staging
-        self.n_ic_workers = max(cfg.ic_workers, 1)
-        if ic is not None:
-            self.n_ic_workers = 1
+        self.sequential_registration = bool(cfg.sequential_registration)   # (may be switched between frames)
+        self._cand = None   # N > 1 with the decision on: the own cameras' candidate columns (send) and every rank's (receive)
+        if self.world > 1 and self._decides():
+            n = 3 * self.nc * cfg.p_reg   # (rows of a record = the list's cap)
+            self._cand = (z(n, i32), z(n * self.world, i32))
+
+    def setup_keyframe_solves(self):
+        """the window bundle adjustment (ring, output records) and the inter-camera solve, each on a workspace with its own worker thread,
+        stream and staging; the window schedule's counters"""
+        torch, cfg, NA, N, device = self.torch, self.cfg, self.cfg.n_cams, self.cfg.n_feat, self.device
         self.ba_ws = BAWorkspace(device)
-        self.ic_wss = [BAWorkspace(device) for _ in range(self.n_ic_workers)]
-        self.ic_ws = self.ic_wss[0]
+        self.ic_ws = BAWorkspace(device)
+        self.ic_wss, self.n_ic_workers = [self.ic_ws], 1   # (bench.py reports the workspaces the inter-camera solves use)
         self.win = self.out = None
         if cfg.with_joint and self.pose_upd is not None:
-            self.win = BAWindow(NA, cfg.n_key_frames, N, n_map, device=device)
+            self.win = BAWindow(NA, cfg.n_key_frames, N, self.n_map, device=device)
             self.win.reserve(self.ba_ws)
             # (records in flight: lag windows on the cadence; with the decision placing the key frames, up to one request per frame of the lag)
-            self.out = BAOutput(NA, cfg.n_key_frames, n_map, n_slots=8 if not cfg.keyframe_drives else min(self.lag * cfg.key_every + 6, 64), device=device)
+            self.out = BAOutput(NA, cfg.n_key_frames, self.n_map, n_slots=8 if not cfg.keyframe_drives else min(self.lag * cfg.key_every + 6, 64),
+                                device=device)
             self.out.attach(self.ba_ws)
             if self.d_fref is not None:
                 self.out.set_feat_refs(self.d_fref.data_ptr(), self.d_rstat.data_ptr())
-            self.recv_rec = z((2, self.out.record_bytes), u8)     # records solved by other ranks arrive here
+            self.recv_rec = self._z((2, self.out.record_bytes), torch.uint8)     # records solved by other ranks arrive here
         self.icam = None
-        if ic is None:
-            from coslam_amd.ba import BAInterCam, intercam_cams
-
+        if self.ic is None:
             # InterCamPoseEstimator::addMapPoints from the live records of ALL cameras (reference src/app/SL_InterCamPoseEstimator.cpp:18-91)
-            self.icams = [BAInterCam(NA, N, cfg.pts_stride, n_map, max_dyn=60, device=device) for _ in range(self.n_ic_workers)]
-            self.icam = self.icams[0]
+            self.icam = BAInterCam(NA, N, cfg.pts_stride, self.n_map, max_dyn=60, device=device)
             self.ic_cams = intercam_cams([dict(K=self.d_K1.data_ptr(), xy=self.d_xy[g].data_ptr(), state=self.d_state[g].data_ptr(),
                                                slot2map=self.d_slot2map[g].data_ptr(), trackSpan=self.d_trackspan[g].data_ptr(),
                                                isStatic=self.d_isstatic[g].data_ptr()) for g in range(NA)])
         else:
-            from coslam_amd.synth import csr_of_problem
-
+            ic = self.ic
             iptr, icam, ixy = csr_of_problem(ic)
             self.ic_ws.upload(ic["Ks"], ic["Rs0"], ic["ts0"], ic["pts0"], iptr, icam, ixy)
-            self.d_iR = torch.from_numpy(ic["Rs0"].reshape(-1).copy()).to(dev)
-            self.d_iT = torch.from_numpy(ic["ts0"].reshape(-1).copy()).to(dev)
-            self.d_iM = torch.from_numpy(ic["pts0"].reshape(-1).copy()).to(dev)
+            self.d_iR = torch.from_numpy(ic["Rs0"].reshape(-1).copy()).to(self.dev)
+            self.d_iT = torch.from_numpy(ic["ts0"].reshape(-1).copy()).to(self.dev)
+            self.d_iM = torch.from_numpy(ic["pts0"].reshape(-1).copy()).to(self.dev)
         self.n_pushed = self.n_windows = self.n_key = self.n_my_solves = self.n_my_ic = 0
         self.skip_busy, self.n_skipped = False, 0   # (set by the caller: drop a window request while the previous solve is running)
-        self.sequential_registration = bool(cfg.sequential_registration)   # (may be switched between frames)
-        self.apply_at, self.my_seq = {}, {}
+        self.apply_at = {}   # frame -> the window whose result is applied at it (_request_window -> _apply_due)
         self.applied, self.last_apply, self.pushed_frames = 0, None, []
-        self.stage_slot, self.h_frames = {}, None
-        import os as _os
-
-        self._timing = {} if _os.environ.get("FRAMELOOP_TIMING") else None   # (diagnostic: host seconds per section)
-        # (diagnostic, FRAMELOOP_GPU_SECTIONS=1: events on the pose stream at the sections' boundaries -> gpu_sections(): untraced GPU time
-        # of every section of a frame, by kind of frame.  Not a valid bench line: two events per section cost a few microseconds each.)
-        self._marks = [] if _os.environ.get("FRAMELOOP_GPU_SECTIONS") else None
-        self._init_ncc()
+        self.n_empty_solves = 0   # requested solves that had nothing to solve (drain())
+        self.kf = None            # the key-frame decision's state (enable_keyframe_decision); None: off
 
     # ---------------------------------------------------------------------------------------------------------------
     def _sec(self, name):
         """diagnostic (FRAMELOOP_TIMING=1): host seconds spent inside a section of the enqueue"""
-        import contextlib
-        import time as _t
-
         if self._timing is None:
             return contextlib.nullcontext()
 
         @contextlib.contextmanager
         def cm():
-            t0 = _t.perf_counter()
+            t0 = time.perf_counter()
             try:
                 yield
             finally:
-                self._timing[name] = self._timing.get(name, 0.0) + _t.perf_counter() - t0
+                self._timing[name] = self._timing.get(name, 0.0) + time.perf_counter() - t0
         return cm()
 
     def _mark(self, i, name):
@@ -435,19 +475,12 @@ class FrameLoop:
         ncc_every-th frame.  A rank cuts the NCC blocks of its OWN cameras (it holds their images); N > 1: the blocks travel (one
         all-gather of 330 KB per camera); every rank then scores all consecutive camera pairs and turns the matches into new map points
         on its replica -- the same bytes in, the same points out."""
-        torch, cfg = self.torch, self.cfg
+        torch, cfg, z = self.torch, self.cfg, self._z
         self.ncc = None
         NA, N = cfg.n_cams, cfg.n_feat
         if not cfg.with_ncc or NA < 2 or self.pose_upd is None:
             return
-        from coslam_amd.ncc import NCC_PAIR_DTYPE, ncc_scaled_dims
-        from coslam_amd.newpts import NewPtsJob, newpts_scratch_bytes
-
         ws_, hs_ = ncc_scaled_dims(cfg.W, cfg.H, 0.3)
-        Kinv = np.linalg.inv(self.sc.K)
-
-        dev = self.dev
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
         rec = N * 128 + N * 32 + N * 4          # one camera's record: blocks | abc | valid
         self.ncc = dict(small=z((self.nc, ws_ * hs_), torch.uint8), rec=z((NA, rec), torch.uint8), rec_bytes=rec, runs=0,
                         send=z((self.nc, rec), torch.uint8) if self.world > 1 else None,
@@ -465,11 +498,6 @@ class FrameLoop:
                                     [self.ncc["pair_count"][a:a + 1].data_ptr() for a in range(NA - 1)])
 
     def _ncc_leg(self, i, f, dst):
-        import coslam_amd
-        from coslam_amd._lib import check
-        from coslam_amd.ncc import ncc_cams, ncc_epi_pairs_group_dev, ncc_fmats_dev, ncc_get_blocks_group_dev, ncc_pair_jobs
-        from coslam_amd.newpts import ncc_candidate_mask_dev, newpts_from_pairs_dev
-
         cfg, nc, c0, N, NA, ncc = self.cfg, self.nc, self.c0, self.cfg.n_feat, self.cfg.n_cams, self.ncc
         s_ = self.pose_s.cuda_stream
         # NewMapPtsNCC::addSlam's features: this frame's, on tracks of more than three frames, unmapped or on a false point -- of the
@@ -501,36 +529,32 @@ class FrameLoop:
                               maxDisp=80.0, maxRpErr=3.0, pixelErrVar=self.sig_pix, minLen=2, device=self.device, W=cfg.W, H=cfg.H)
         ncc["runs"] += 1
 
-    def _gather_ncc_records(self):
-        """the own cameras' NCC records (blocks | abc | candidate mask) to every rank: ONE all-gather, 330 KB per camera, every 4th frame"""
-        import ctypes as C_
-
-        import coslam_amd
-        from coslam_amd._lib import check
-
-        torch, ncc, nc, c0 = self.torch, self.ncc, self.nc, self.c0
-        L, vp, ps = coslam_amd.lib(), C_.c_void_p, self.pose_s.cuda_stream
-        with torch.cuda.stream(self.pose_s):
-            ncc["send"].copy_(ncc["rec"][c0:c0 + nc], non_blocking=True)
+    def _allgather(self, send, recv, nbytes):
+        """one all-gather on the pose stream: the library's communicator, else torch.distributed's"""
         if self.native is not None:
-            L.cs_comm_allgather_dev.argtypes = [vp, vp, vp, vp, C_.c_size_t]
-            check(L.cs_comm_allgather_dev(self.native.exchange_comm, vp(ps), vp(ncc["send"].data_ptr()), vp(ncc["rec"].data_ptr()),
-                                          ncc["send"].numel()), "cs_comm_allgather_dev")
+            L, vp = coslam_amd.lib(), C.c_void_p
+            L.cs_comm_allgather_dev.argtypes = [vp, vp, vp, vp, C.c_size_t]
+            check(L.cs_comm_allgather_dev(self.native.exchange_comm, vp(self.pose_s.cuda_stream), vp(send.data_ptr()), vp(recv.data_ptr()),
+                                          nbytes), "cs_comm_allgather_dev")
         else:
             import torch.distributed as dist
 
-            with torch.cuda.stream(self.pose_s):
-                dist.all_gather_into_tensor(ncc["rec"].view(-1), ncc["send"].view(-1))
+            with self.torch.cuda.stream(self.pose_s):
+                dist.all_gather_into_tensor(recv, send)
+
+    def _gather_ncc_records(self):
+        """the own cameras' NCC records (blocks | abc | candidate mask) to every rank: ONE all-gather, 330 KB per camera, every 4th frame"""
+        ncc, nc, c0 = self.ncc, self.nc, self.c0
+        with self.torch.cuda.stream(self.pose_s):
+            ncc["send"].copy_(ncc["rec"][c0:c0 + nc], non_blocking=True)
+        self._allgather(ncc["send"].view(-1), ncc["rec"].view(-1), ncc["send"].numel())
 
     # ---------------------------------------------------------------------------------------------------------------
     def first_frame(self):
         """GPUKLT::first (reference src/tracking/GPUKLT.cpp:133-142) of every camera, the slot -> map-point association that stands
         in for the map initialisation (out of scope), and the first hand-back."""
         torch, cfg = self.torch, self.cfg
-        import coslam_amd
-        from coslam_amd.handback import handback_dev
-
-        NA, N = cfg.n_cams, cfg.n_feat
+        NA = cfg.n_cams
         self.grp.detect_dev(self.img_ptrs[0], self.dest_ptrs[0], self.cnt_ptrs)
         self.grp.advanceFrame()
         self.grp.synchronize()
@@ -567,12 +591,9 @@ class FrameLoop:
         `frame` would: a key pose with self motion in every camera (pose buffer b), nMappedPts = the certainly static mapped features of that
         frame, m_minCamTranslation = the mean distance between the cameras / 4.5.  From the next step on cs_keyframe_ready_dev runs per frame.
         Synchronises."""
-        from coslam_amd.keyframe import keyframe_cams
-
-        torch, NA = self.torch, self.cfg.n_cams
+        torch, cfg, NA, z = self.torch, self.cfg, self.cfg.n_cams, self._z
         torch.cuda.synchronize()
         i32, f64 = torch.int32, torch.float64
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.dev)   # noqa: E731
         st, fl, s2m = self.d_state.cpu().numpy(), self.d_mapflags.cpu().numpy(), self.d_slot2map.cpu().numpy()
         km = [int((((st[g] == 0) | (st[g] == 1)) & (s2m[g] >= 0) & ((fl[np.clip(s2m[g], 0, len(fl) - 1)] & 7) == 0)).sum()) for g in range(NA)]
         self.kf = dict(frame=torch.full((NA,), int(frame), dtype=i32, device=self.dev), mapped=torch.tensor(km, dtype=i32, device=self.dev),
@@ -586,22 +607,20 @@ class FrameLoop:
                                                R=self.d_R[q][g].data_ptr(), t=self.d_t[q][g].data_ptr(), keyFrame=self.kf["frame"][g:].data_ptr(),
                                                keyMapped=self.kf["mapped"][g:].data_ptr(), selfR=self.kf["selfR"][g].data_ptr(),
                                                selfT=self.kf["selfT"][g].data_ptr()) for g in range(NA)]) for q in range(2)]
-        torch.cuda.synchronize()
+        if cfg.intracam_mapping and self.pose_upd is not None:
+            self.kf.update(im_scr=z(self.pose_upd.newpts_intracam_scratch_bytes(), torch.uint8), im_cnt=z(3, i32), im_total=z(3, torch.int64))
+        if cfg.keyframe_drives and cfg.keyframe_lag > 0:
+            self.kf["lag_ring"], self.kf["lag_blocked"] = self._kf_lag_ring(), 0
+        torch.cuda.synchronize()   # (zero-filled on torch's stream, used on the pose stream)
 
     def _kf_lag_ring(self):
         """the ring of D + 1 snapshots a lagged key-frame decision acts on: per slot the hand-back's xy / state / slot2map of all cameras, the
         poses, the decision word in pinned host memory and an event behind it"""
-        k, torch, cfg, NA, N = self.kf, self.torch, self.cfg, self.cfg.n_cams, self.cfg.n_feat
-        if "lag_ring" in k:
-            return k["lag_ring"]
-        from coslam_amd.handback import handback_cams
-
+        torch, cfg, NA, N, z = self.torch, self.cfg, self.cfg.n_cams, self.cfg.n_feat, self._z
         ring = []
         for _ in range(cfg.keyframe_lag + 1):
-            xy = torch.zeros((NA, 2 * N), dtype=torch.float64, device=self.dev)
-            st = torch.zeros((NA, N), dtype=torch.int32, device=self.dev)
-            s2m = torch.zeros((NA, N), dtype=torch.int32, device=self.dev)
-            R, t = torch.zeros((NA, 9), dtype=torch.float64, device=self.dev), torch.zeros((NA, 3), dtype=torch.float64, device=self.dev)
+            xy, st, s2m = z((NA, 2 * N), torch.float64), z((NA, N), torch.int32), z((NA, N), torch.int32)
+            R, t = z((NA, 9), torch.float64), z((NA, 3), torch.float64)
             hb = handback_cams([dict(dest=self.d_dests[0][0].data_ptr(), K=self.d_K1.data_ptr(), kud=self.d_kud.data_ptr(), mapPts=self.d_map.data_ptr(),
                                      slot2map=s2m[g].data_ptr(), trackSpan=self.d_trackspan[g].data_ptr(), xy=xy[g].data_ptr(), state=st[g].data_ptr(),
                                      Ms=self.d_Ms[g].data_ptr(), ms=self.d_ms[g].data_ptr(), sel=self.d_sel[g].data_ptr(),
@@ -609,16 +628,12 @@ class FrameLoop:
                                      isStatic=0) for g in range(NA)])
             ring.append(dict(xy=xy, st=st, s2m=s2m, R=R, t=t, hb=hb, word=torch.zeros(1, dtype=torch.int32).pin_memory(),
                              ev=torch.cuda.Event(), frame=-1))
-        torch.cuda.synchronize()   # (zero-filled on torch's stream, used on the pose stream)
-        k["lag_ring"], k["lag_blocked"] = ring, 0
         return ring
 
     def _kf_lag_record(self, i, dst):
         """frame i's decision word, records and poses into its ring slot, on the pose stream; no host wait"""
-        k, torch, NA = self.kf, self.torch, self.cfg.n_cams
-        sl = self._kf_lag_ring()[i % (self.cfg.keyframe_lag + 1)]
-        from coslam_amd.keyframe import keyframe_snapshot_dev
-
+        k, NA = self.kf, self.cfg.n_cams
+        sl = k["lag_ring"][i % (self.cfg.keyframe_lag + 1)]
         keyframe_snapshot_dev(self.pose_s.cuda_stream, NA, self.cfg.n_feat, self.d_xy.data_ptr(), self.d_state.data_ptr(), self.d_slot2map.data_ptr(),
                               self.d_R[dst].data_ptr(), self.d_t[dst].data_ptr(), k["ready"][NA + 1:].data_ptr(), sl["xy"].data_ptr(), sl["st"].data_ptr(),
                               sl["s2m"].data_ptr(), sl["R"].data_ptr(), sl["t"].data_ptr(), sl["word"].data_ptr(), device=self.device)
@@ -630,7 +645,7 @@ class FrameLoop:
         poses and the window's request (genNewMapPoints :1331-1346), D frames late"""
         k, D = self.kf, self.cfg.keyframe_lag
         f = i - D
-        sl = self._kf_lag_ring()[f % (D + 1)]
+        sl = k["lag_ring"][f % (D + 1)]
         if f < 1 or sl["frame"] != f:
             return
         if not sl["ev"].query():
@@ -643,7 +658,7 @@ class FrameLoop:
 
     def keyframe_stats(self):
         """what the key-frame decision said over the frames it ran on (cs_keyframe_ready_dev's d_stats; a synchronous read)"""
-        if not getattr(self, "kf", None):
+        if not self.kf:
             return None
         a = self.kf["stats"].cpu().tolist()
         im = None if "im_total" not in self.kf else dict(zip(("candidates_tried", "points_added", "points_dropped_map_full"), self.kf["im_total"].cpu().tolist()))
@@ -655,8 +670,6 @@ class FrameLoop:
                     mapped_static_at_the_last_key_frame=self.kf["mapped"].cpu().tolist())
 
     def _handback(self, b, frame, which="all"):
-        from coslam_amd.handback import handback_dev
-
         cfg = self.cfg
         a = dict(N=cfg.n_feat, W=cfg.W, H=cfg.H, nColBlk=cfg.n_col_blk, nRowBlk=cfg.n_row_blk, ptsStride=cfg.pts_stride, device=self.device,
                  frame=frame)
@@ -665,52 +678,58 @@ class FrameLoop:
         if which in ("all", "other") and self.hb_other is not None:
             handback_dev(self.pose_s.cuda_stream, self.hb_other, **a)
 
-    def _apply_due(self, i, src):
-        """RobustBundleRTS::output() of the window whose lag ends at this frame, before anything of frame i touches the map"""
-        due = self.apply_at.pop(i, None)
-        if due is None:
-            return
-        k, owner, first_key, seq = due
-        frames = None
-        if isinstance(first_key, (list, tuple)):   # (key frames the decision placed: a list instead of first + j * key_every)
-            frames, first_key = list(first_key), first_key[0]
-            if (i - 1) - first_key + 1 > self.pose_upd.storeLen:   # (the frames the history KEEPS: hist_store, not the walks' depth)
-                # the camera graphs would start behind the pose history's oldest frame: the record is consumed, nothing is written back
-                self.my_seq.pop(k, None)
-                self.kf["not_applied"] += 1
-                return
-        if owner == self.rank:
-            # the pose stream waits ON THE DEVICE for this rank's worker to publish the record: the host goes on enqueueing frames
-            self.my_seq.pop(k)
-            rec = self.out.wait_dev(seq, self.pose_s.cuda_stream) if self.cfg.device_wait else self.out.wait(seq)
-        else:
-            rec = self.recv_rec[k & 1].data_ptr()
-        if self.world > 1:
-            self.xchg.broadcast(rec, self.out.record_bytes, owner, self.device, self.pose_s)
-        if frames is not None:
-            self.out.apply_frames_dev(rec, self.pose_s.cuda_stream, self.pose_upd, self.win, self.pu_args, self.d_pf.data_ptr(), self.n_map,
-                                      self.d_map.data_ptr(), self.d_cov.data_ptr(), self.d_mapflags.data_ptr(), self.sig_pix, frames,
-                                      self.d_R[src].data_ptr(), self.d_t[src].data_ptr(), self.d_apply_counts.data_ptr(), seq=seq)
-        else:
-            self.out.apply_dev(rec, self.pose_s.cuda_stream, self.pose_upd, self.win, self.pu_args, self.d_pf.data_ptr(), self.n_map,
-                               self.d_map.data_ptr(), self.d_cov.data_ptr(), self.d_mapflags.data_ptr(), self.sig_pix, first_key,
-                               self.cfg.key_every, self.d_R[src].data_ptr(), self.d_t[src].data_ptr(), self.d_apply_counts.data_ptr(), seq=seq)
-        self.applied += 1
-        self.last_apply = dict(window=k, solved_by_rank=owner, first_key_frame=first_key, applied_at_frame=i)
-
     def stage(self, i):
         f = self.vid(i)
         self.stage_slot[i] = self.grp.stage_h([self.h_frames[f][c].data_ptr() for c in range(self.nc)])
 
+    # ---------------------------------------------------------------------------------------------------------------
     def step(self, i, key_frame, upload=False):
-        from coslam_amd.pose import intraCamEstimate_batch_dev
-        from coslam_amd.register import register_search_passes_dev
+        """frame i: the tracker, then on the pose stream the frame's stages in the reference's order (src/gui/CoSLAMThread.cpp:104-118)"""
+        cfg = self.cfg
+        b, src, dst = i & 1, (i + 1) & 1, i & 1   # dest buffer, pose buffer read, pose buffer written
+        self._frame_now, self._dst_now = i, dst   # (read between frames by the caller)
+        self._track(i, b, upload)
+        self._mark(i, "tracker done")
+        if self.out is not None:
+            with self._sec("apply"):
+                self._apply_due(i, src)
+        self._mark(i, "BA applied")
+        self._handback(b, i, "own")
+        self._mark(i, "hand-back")
+        self._intracam(b, src, dst)
+        self._mark(i, "intracam")
+        if self.world > 1:
+            self._exchange(i, b, dst)
+        if self.pose_upd is not None:
+            self._pose_update(i, dst)
+        self._mark(i, "pose update + classify")
+        # poseUpdate (with mapPointsClassify) -> activeMapPointsRegister -> genNewMapPoints -> currentMapPointsRegister: the new map points
+        # take their features BEFORE the current points' registration looks at them (a feature that carries a point ends a registration walk)
+        if self.kf:
+            placed = self._keyframe_decision_step(i, dst)
+            if cfg.keyframe_drives:
+                key_frame = placed
+        if self.ncc is not None and i % cfg.ncc_every == 0:
+            self._ncc_leg(i, self.vid(i), dst)
+            self._mark(i, "ncc leg")
+        self._register_frame(i, dst)
+        self._mark(i, "decide + refine")
+        # the tracker of frame i + 2 (it writes this dest buffer) is released HERE, at the end of the frame's pose work, although the
+        # buffer's last reader was the hand-back: released earlier the tracker runs two frames ahead and under more of the pose stream's
+        # kernels -- measured 1978-1986 (behind the hand-back) / 1928-1934 (behind the gate) / 1894-1903 (behind the classification)
+        # against 2173-2193 frames/s here, 2119-2123 behind the key-frame requests (profiles/r04_ab_runs.txt)
+        self.dest_free[b].record(self.pose_s)
+        if cfg.keyframe_drives and cfg.keyframe_lag > 0 and self.kf:
+            self._kf_lag_record(i, dst)
+            self._kf_lag_act(i, dst)
+        if key_frame:
+            with self._sec("key_frame"):
+                self._key_frame(i, dst)
+            self._mark(i, "key-frame push + requests")
 
-        torch, cfg = self.torch, self.cfg
-        klt_s, pose_s, c0, nc, NA_ = self.klt_s, self.pose_s, self.c0, self.nc, self.cfg.n_cams
-        self._frame_in_step = i
-        f, fn = self.vid(i), self.vid(i + 1)
-        b = i & 1
+    def _track(self, i, b, upload):
+        """GPUKLT::next of the own cameras on the tracker stream into dest buffer b; the pose stream waits for it"""
+        cfg, klt_s = self.cfg, self.klt_s
         if i >= 2:
             klt_s.wait_event(self.dest_free[b])      # the consumer of this dest buffer two frames ago is done
             if cfg.klt_after_intracam:
@@ -719,147 +738,113 @@ class FrameLoop:
             self.stage(i + 2)
             cur, nxt = self.grp.staged(self.stage_slot.pop(i)), self.grp.staged(self.stage_slot[i + 1])
         else:
-            cur, nxt = self.img_ptrs[f], self.img_ptrs[fn]
+            cur, nxt = self.img_ptrs[self.vid(i)], self.img_ptrs[self.vid(i + 1)]
         if cfg.prefetch:   # this frame's detector tail also builds the next frame's pyramids + cornerness maps
             self.grp.prefetch_dev(nxt)
         self.grp.redetect_dev(cur, self.dest_ptrs[b], self.cnt_ptrs)
         self.grp.advanceFrame()
         self.klt_done[b].record(klt_s)
-        pose_s.wait_event(self.klt_done[b])          # pose(f) consumes what the tracker produced for frame f
-        src, dst = (i + 1) & 1, i & 1
-        ps = pose_s.cuda_stream
-        self._mark(i, "tracker done")
-        if self.out is not None:
-            if self._timing is not None:
-                import time as _t
+        self.pose_s.wait_event(self.klt_done[b])          # pose(f) consumes what the tracker produced for frame f
 
-                t0 = _t.perf_counter()
-                self._apply_due(i, src)
-                self._timing["apply"] = self._timing.get("apply", 0.0) + _t.perf_counter() - t0
-            else:
-                self._apply_due(i, src)
-        self._mark(i, "BA applied")
-        self._handback(b, i, "own")
-        self._mark(i, "hand-back")
-        intraCamEstimate_batch_dev(ps, nc, cfg.pts_stride, self.d_K.data_ptr(), self.d_R[src].data_ptr() + 72 * c0,
+    def _intracam(self, b, src, dst):
+        """intraCamEstimate of the own cameras from the previous poses (src) into this frame's (dst)"""
+        cfg, c0 = self.cfg, self.c0
+        intraCamEstimate_batch_dev(self.pose_s.cuda_stream, self.nc, cfg.pts_stride, self.d_K.data_ptr(), self.d_R[src].data_ptr() + 72 * c0,
                                    self.d_t[src].data_ptr() + 24 * c0, self.d_npts.data_ptr() + 4 * c0, 0,
                                    self.d_Ms.data_ptr() + 24 * cfg.pts_stride * c0, self.d_ms.data_ptr() + 16 * cfg.pts_stride * c0, 10.0,
                                    self.d_R[dst].data_ptr() + 72 * c0, self.d_t[dst].data_ptr() + 24 * c0, self.d_opt.data_ptr() + 96 * c0,
                                    self.d_ok.data_ptr() + 4 * c0, device=self.device)
         if cfg.klt_after_intracam:
-            self.intracam_done[b].record(pose_s)
-        self._mark(i, "intracam")
-        if self.world > 1:
-            # the merge step: every camera's {dest[], R, t} to every rank, then the other ranks' cameras through the same hand-back
-            with torch.cuda.stream(pose_s):
-                self.xchg.pack_group(self.d_dests[b], self.d_R[dst][c0:c0 + nc], self.d_t[dst][c0:c0 + nc], pose_s)
-                self.xchg.all_gather(pose_s)
-                self.xchg.unpack_poses(self.d_R[dst], self.d_t[dst], pose_s, skip_own=True)
-            self._handback(b, i, "other")
-        if self.pose_upd is not None:
-            # parallelPoseUpdate(false): gate 2.0, sigma = PIXEL_ERR_VAR; detectDynamicFeaturePoints(20, 5, 3, MAX_EPI_ERR)
-            if cfg.with_classify:   # CoSLAM::poseUpdate as a whole: two launches (the gate also builds the classification's worklist)
-                self.pose_upd.pose_update_classify_frame_dev(ps, self.pu_args, self.d_pf.data_ptr(), self.n_map, self.d_R[dst].data_ptr(),
-                                                             self.d_t[dst].data_ptr(), self.d_map.data_ptr(), self.d_cov.data_ptr(),
-                                                             self.d_mapflags.data_ptr(), 0, self.sig_pix, i, self.d_newpt.data_ptr(),
-                                                             self.d_sfn.data_ptr(), self.d_firstfrm.data_ptr(), self.sig(12.0), 20, 5, 3,
-                                                             MAX_EPI_ERR, d_counts=self.d_cls_counts.data_ptr())
-            else:
-                self.pose_upd.pose_update_frame_dev(ps, self.pu_args, self.d_pf.data_ptr(), self.n_map, self.d_R[dst].data_ptr(),
-                                                    self.d_t[dst].data_ptr(), self.d_map.data_ptr(), self.d_cov.data_ptr(),
-                                                    self.d_mapflags.data_ptr(), 0, self.sig_pix, i, 20, 5, 3, MAX_EPI_ERR)
-        self._mark(i, "pose update + classify")
-        # the reference's order of a frame (src/gui/CoSLAMThread.cpp:104-118): poseUpdate (with mapPointsClassify) -> activeMapPointsRegister ->
-        # genNewMapPoints -> currentMapPointsRegister: the new map points take their features BEFORE the current points' registration
-        # looks at them (a feature that carries a point ends a registration walk)
-        if getattr(self, "kf", None):
-            # genNewMapPoints' first half (:1294-1346): is a camera ready for a key frame, and addKeyFrame's bookkeeping when one's mapped
-            # points have decreased
-            from coslam_amd.keyframe import keyframe_ready_dev
+            self.intracam_done[b].record(self.pose_s)
 
-            k = self.kf
-            keyframe_ready_dev(ps, k["cams"][dst], cfg.n_feat, self.n_map, self.d_map.data_ptr(), self.d_mapflags.data_ptr(), self.d_firstfrm.data_ptr(),
-                               i, k["min_translation"], k["ready"].data_ptr(), k["cnt"].data_ptr(), k["cen"].data_ptr(), ratio=cfg.keyframe_ratio,
-                               addKeyFrame=True, d_stats=k["stats"].data_ptr(), device=self.device)
-            k["frames"] += 1
-            if cfg.keyframe_drives and cfg.keyframe_lag > 0:
-                # no wait: this frame's `decrease`, records and poses go into slot i % (D + 1) of a ring (the word into pinned host memory, an
-                # event behind it); what the host acts on below is the decision of frame i - D
-                key_frame = False   # (recorded at the end of the frame, where the push of a key frame sits: behind the registration's attachments)
-            elif cfg.keyframe_drives:
-                # `decrease` (ready[nCams + 1]) back to the host: the frame is a key frame for ALL cameras when one camera's mapped points
-                # have decreased (:1331-1346) -- the push and the request below follow the device's answer, not the caller's cadence
-                pose_s.synchronize()
-                key_frame = bool(int(k["ready"][NA_ + 1].item()))
-                if key_frame:
-                    k["placed"].append(i)
-            if cfg.intracam_mapping and self.pose_upd is not None:
-                # ... and for the cameras that are ready (view angle / translation; with `decrease` the cameras that said so too: :1310-1346)
-                # SingleSLAM::newMapPoints: the unmapped features on tracks of nMinFeatTrkLen = 20 frames, each from its own track
-                if "im_scr" not in k:
-                    torch = self.torch
-                    k["im_scr"] = torch.zeros(self.pose_upd.newpts_intracam_scratch_bytes(), dtype=torch.uint8, device=self.dev)
-                    k["im_cnt"] = torch.zeros(3, dtype=torch.int32, device=self.dev)
-                    k["im_total"] = torch.zeros(3, dtype=torch.int64, device=self.dev)
-                    torch.cuda.synchronize()
-                self.pose_upd.newpts_intracam_dev(ps, self.pu_args, self.d_map.data_ptr(), self.d_cov.data_ptr(), self.d_mapflags.data_ptr(),
-                                                  self.d_newpt.data_ptr(), self.d_firstfrm.data_ptr(), self.d_pf.data_ptr(), self.n_map,
-                                                  self.d_mapcount.data_ptr(), k["im_scr"].data_ptr(), self.sig_pix, d_ready=k["ready"].data_ptr(),
-                                                  readyMin=1, minTrackLen=20, maxWalk=1024, maxEpiErr=2.0, d_counts=k["im_cnt"].data_ptr())
-                with self.torch.cuda.stream(self.pose_s):
-                    k["im_total"] += k["im_cnt"]
-        if self.ncc is not None and i % cfg.ncc_every == 0:
-            self._ncc_leg(i, f, dst)
-            self._mark(i, "ncc leg")
+    def _exchange(self, i, b, dst):
+        """the merge step: every camera's {dest[], R, t} to every rank, then the other ranks' cameras through the same hand-back"""
+        c0, nc, pose_s = self.c0, self.nc, self.pose_s
+        with self.torch.cuda.stream(pose_s):
+            self.xchg.pack_group(self.d_dests[b], self.d_R[dst][c0:c0 + nc], self.d_t[dst][c0:c0 + nc], pose_s)
+            self.xchg.all_gather(pose_s)
+            self.xchg.unpack_poses(self.d_R[dst], self.d_t[dst], pose_s, skip_own=True)
+        self._handback(b, i, "other")
+
+    def _pose_update(self, i, dst):
+        """parallelPoseUpdate(false): gate 2.0, sigma = PIXEL_ERR_VAR; detectDynamicFeaturePoints(20, 5, 3, MAX_EPI_ERR)"""
+        ps = self.pose_s.cuda_stream
+        if self.cfg.with_classify:   # CoSLAM::poseUpdate as a whole: two launches (the gate also builds the classification's worklist)
+            self.pose_upd.pose_update_classify_frame_dev(ps, self.pu_args, self.d_pf.data_ptr(), self.n_map, self.d_R[dst].data_ptr(),
+                                                         self.d_t[dst].data_ptr(), self.d_map.data_ptr(), self.d_cov.data_ptr(),
+                                                         self.d_mapflags.data_ptr(), 0, self.sig_pix, i, self.d_newpt.data_ptr(),
+                                                         self.d_sfn.data_ptr(), self.d_firstfrm.data_ptr(), self.sig(12.0), 20, 5, 3,
+                                                         MAX_EPI_ERR, d_counts=self.d_cls_counts.data_ptr())
+        else:
+            self.pose_upd.pose_update_frame_dev(ps, self.pu_args, self.d_pf.data_ptr(), self.n_map, self.d_R[dst].data_ptr(),
+                                                self.d_t[dst].data_ptr(), self.d_map.data_ptr(), self.d_cov.data_ptr(),
+                                                self.d_mapflags.data_ptr(), 0, self.sig_pix, i, 20, 5, 3, MAX_EPI_ERR)
+
+    def _keyframe_decision_step(self, i, dst):
+        """genNewMapPoints' first half (:1294-1346): is a camera ready for a key frame, and addKeyFrame's bookkeeping when one's mapped
+        points have decreased; with intracam_mapping the new map points of the ready cameras.  Returns whether frame i is a key frame by
+        the decision read back now (keyframe_drives without lag; otherwise False)."""
+        cfg, k, ps = self.cfg, self.kf, self.pose_s.cuda_stream
+        keyframe_ready_dev(ps, k["cams"][dst], cfg.n_feat, self.n_map, self.d_map.data_ptr(), self.d_mapflags.data_ptr(), self.d_firstfrm.data_ptr(),
+                           i, k["min_translation"], k["ready"].data_ptr(), k["cnt"].data_ptr(), k["cen"].data_ptr(), ratio=cfg.keyframe_ratio,
+                           addKeyFrame=True, d_stats=k["stats"].data_ptr(), device=self.device)
+        k["frames"] += 1
+        placed = False
+        # (keyframe_lag > 0: no wait -- this frame's `decrease`, records and poses go into slot i % (D + 1) of a ring at the end of the frame,
+        # behind the registration's attachments (_kf_lag_record); what the host acts on is the decision of frame i - D)
+        if cfg.keyframe_drives and cfg.keyframe_lag <= 0:
+            # `decrease` (ready[nCams + 1]) back to the host: the frame is a key frame for ALL cameras when one camera's mapped points
+            # have decreased (:1331-1346) -- the push and the request follow the device's answer, not the caller's cadence
+            self.pose_s.synchronize()
+            placed = bool(int(k["ready"][cfg.n_cams + 1].item()))
+            if placed:
+                k["placed"].append(i)
+        if cfg.intracam_mapping and self.pose_upd is not None:
+            # ... and for the cameras that are ready (view angle / translation; with `decrease` the cameras that said so too: :1310-1346)
+            # SingleSLAM::newMapPoints: the unmapped features on tracks of nMinFeatTrkLen = 20 frames, each from its own track
+            self.pose_upd.newpts_intracam_dev(ps, self.pu_args, self.d_map.data_ptr(), self.d_cov.data_ptr(), self.d_mapflags.data_ptr(),
+                                              self.d_newpt.data_ptr(), self.d_firstfrm.data_ptr(), self.d_pf.data_ptr(), self.n_map,
+                                              self.d_mapcount.data_ptr(), k["im_scr"].data_ptr(), self.sig_pix, d_ready=k["ready"].data_ptr(),
+                                              readyMin=1, minTrackLen=20, maxWalk=1024, maxEpiErr=2.0, d_counts=k["im_cnt"].data_ptr())
+            with self.torch.cuda.stream(self.pose_s):
+                k["im_total"] += k["im_cnt"]
+        return placed
+
+    # ---------------------------------------------------------------------------------------------------------------
+    def _decides(self):
+        return self.cfg.with_register and self.cfg.with_decide and self.pose_upd is not None and self.cfg.with_mergability
+
+    def _register_frame(self, i, dst):
+        """currentMapPointsRegister: the frame's current points listed and searched in the own cameras (poses dst), their mergability,
+        then the decisions and refine; without decisions the feature references only follow the tracks"""
+        cfg, ps = self.cfg, self.pose_s.cuda_stream
         if cfg.with_register:
-            from coslam_amd.register import register_list_current_dev
-
             # curMapPts of this frame as a list (mapStateUpdate, SL_CoSLAM.cpp:1176-1194); the rows of every other point lose their candidates
-            register_list_current_dev(ps, NA_, self.n_map, self.d_mapcount.data_ptr(), self.d_pf.data_ptr(), self.d_mapflags.data_ptr(),
+            register_list_current_dev(ps, cfg.n_cams, self.n_map, self.d_mapcount.data_ptr(), self.d_pf.data_ptr(), self.d_mapflags.data_ptr(),
                                       self.d_curlist.data_ptr(), self.d_curcount.data_ptr(), self.reg_out["slot"].data_ptr(), device=self.device,
                                       listCap=cfg.p_reg, d_overflow=self.d_curoverflow.data_ptr())
-            register_search_passes_dev(ps, self.reg_args[dst], cfg.n_feat, cfg.W, cfg.H, self.reg_passes, device=self.device, cam0=c0,
-                                       nCamsRun=nc)
+            register_search_passes_dev(ps, self.reg_args[dst], cfg.n_feat, cfg.W, cfg.H, self.reg_passes, device=self.device, cam0=self.c0,
+                                       nCamsRun=self.nc)
             self._mark(i, "list + search")
             if self.pose_upd is not None and cfg.with_mergability:
-                self._mergability(ps)
+                self._mergability(i)
                 self._mark(i, "mergability")
-        self._dst_now, self._frame_now = dst, i
-        if cfg.with_register and cfg.with_decide and self.pose_upd is not None and cfg.with_mergability:
-            self._decide(ps)
+        if self._decides():
+            self._decide(i, dst)
         elif self.pose_upd is not None:
-            self._advance_refs(ps)   # (no decisions in this configuration: the references still follow the tracks, every frame)
-        # the tracker of frame i + 2 (it writes this dest buffer) is released HERE, at the end of the frame's pose work, although the
-        # buffer's last reader was the hand-back: released earlier the tracker runs two frames ahead and under more of the pose stream's
-        # kernels -- measured 1978-1986 (behind the hand-back) / 1928-1934 (behind the gate) / 1894-1903 (behind the classification)
-        # against 2173-2193 frames/s here, 2119-2123 behind the key-frame requests (profiles/r04_ab_runs.txt)
-        self._mark(i, "decide + refine")
-        self.dest_free[b].record(pose_s)
-        if cfg.keyframe_drives and cfg.keyframe_lag > 0 and getattr(self, "kf", None):
-            self._kf_lag_record(i, dst)
-            self._kf_lag_act(i, dst)
-        if key_frame:
-            if self._timing is not None:
-                import time as _t
+            self._advance_refs(i)   # (no decisions in this configuration: the references still follow the tracks, every frame)
 
-                t0 = _t.perf_counter()
-                self._key_frame(i, dst)
-                self._timing["key_frame"] = self._timing.get("key_frame", 0.0) + _t.perf_counter() - t0
-            else:
-                self._key_frame(i, dst)
-            self._mark(i, "key-frame push + requests")
-
-    def _mergability(self, ps):
+    def _mergability(self, i):
         """staticCheckMergability of every candidate of the current points' pass over its WHOLE track (SL_CoSLAM.cpp:714-729, :768), as a
         running verdict: the newest `hist` frames walked as they stand, the older ones' verdict cached per (point, camera) and extended
         by one term per frame (cs_register_mergability_running_dev) -- own cameras' columns"""
-        cfg = self.cfg
+        cfg, ps = self.cfg, self.pose_s.cuda_stream
         self.pose_upd.register_mergability_running_dev(ps, self.pu_args, self.n_map, self.d_map.data_ptr(), self.d_cov.data_ptr(),
                                                        self.reg_out["slot"].data_ptr(), self.sig_pix, self.d_merge_cache.data_ptr(),
                                                        self.d_mergeable.data_ptr(), tolPix=cfg.merge_tol_pix, d_counts=self.d_merge_counts.data_ptr(),
                                                        cam0=self.c0, nCamsRun=self.nc, d_list=self.d_curlist.data_ptr(), nList=cfg.p_reg,
                                                        d_flags=self.reg_out["flags"].data_ptr())
-        if cfg.merge_tol_pix > 0 and cfg.verdict_check_every > 0 and self._frame_now_for_check() % cfg.verdict_check_every == 0:
+        if cfg.merge_tol_pix > 0 and cfg.verdict_check_every > 0 and i % cfg.verdict_check_every == 0:
             # diagnostic (VERDICT r05): how often does a CACHED tail change a verdict?  Every n-th frame the same candidates are judged once more
             # with tolPix = 0 -- every tail whose point has moved at all walked again with today's point -- on a copy of the cache, into a
             # scratch table; the two tables are compared where a candidate was judged.  Two launches + a 6 MB copy on those frames.
@@ -881,9 +866,6 @@ class FrameLoop:
                 V["n"] += torch.stack([judged.sum(), (judged & (self.d_mergeable[:, lc] != V["out"][:, lc])).sum(),
                                        torch.ones((), dtype=torch.int64, device=self.dev)])
 
-    def _frame_now_for_check(self):
-        return getattr(self, "_frame_in_step", 0)
-
     def verdict_check(self):
         """{candidates judged, verdicts the cached tails changed, frames checked} of the running mergability verdict's diagnostic"""
         if not hasattr(self, "_vc"):
@@ -891,88 +873,76 @@ class FrameLoop:
         a = self._vc["n"].cpu().tolist()
         return {"candidates_judged": a[0], "verdicts_changed_by_the_cache": a[1], "frames_checked": a[2]}
 
-    def _decide(self, ps):
+    def _decide(self, i, dst):
         """currentMapPointsRegister's decisions -- curStaticPointsRegInGroup (reference src/app/SL_CoSLAM.cpp:854-898, 731-830, bMerge ==
         false) and behind it curDynamicPointsRegInGroup (:904-1020) on the certainly dynamic points, one call -- over the search
         tables of ALL cameras, then refineMapPoint of the points that gained a feature (:889-893, :666-713).  N > 1: the own cameras'
         columns of the tables travel first (one small all-gather), every rank then takes the same decisions on its replica."""
-        from coslam_amd.register import register_decide_scratch_bytes, register_decide_static_dev
-
-        cfg, NA = self.cfg, self.cfg.n_cams
-        if not hasattr(self, "_dec"):
-            torch = self.torch
-            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.dev)   # noqa: E731
+        cfg, NA, ps, o = self.cfg, self.cfg.n_cams, self.pose_s.cuda_stream, self.reg_out
+        if not hasattr(self, "_dec"):   # (created by the first decision: bench.py asks for it to know that the decision ran)
+            torch, z = self.torch, self._z
             self.n_merge_frames = 0
             self._dec = dict(att=z((self.n_map, NA), torch.uint8), reg=z(self.n_map, torch.uint8), cnt=z(4, torch.int32), ref_cnt=z(1, torch.int32),
                              mcnt=z(4, torch.int32),
-                             scr=z(register_decide_scratch_bytes(NA, cfg.n_feat, self.n_map), torch.uint8), s2m=None,
+                             scr=z(register_decide_scratch_bytes(NA, cfg.n_feat, self.n_map), torch.uint8),
+                             s2m=[self.d_slot2map[g].data_ptr() for g in range(NA)],
                              mscr=z(self.pose_upd.decide_merge_scratch_bytes(self.n_map, cfg.p_reg), torch.uint8))
             torch.cuda.synchronize()   # (the zero fills ran on torch's stream: done before the pose stream touches the buffers)
         D = self._dec
+        merge = cfg.merge_every > 0 and i % cfg.merge_every == 0   # a bMerge frame (CoSLAMThread.cpp:117-118)
         if self.sequential_registration:
-            from coslam_amd.register import register_cur_static_sequential_dev
-
             if self.world > 1:
                 raise RuntimeError("sequential_registration: one rank only (the per-loop tables are not exchanged)")
-            if not hasattr(self, "_pass_current"):
-                T_ = type(self.reg_passes[0])
-                self._pass_current = (T_ * 1)(self.reg_passes[0])
-            o = self.reg_out
-            D["s2m"] = register_cur_static_sequential_dev(ps, self.pose_upd, self.pu_args, self.reg_args[self._dst_now], cfg.n_feat, cfg.W, cfg.H,
+            D["s2m"] = register_cur_static_sequential_dev(ps, self.pose_upd, self.pu_args, self.reg_args[dst], cfg.n_feat, cfg.W, cfg.H,
                                                           self._pass_current, self.n_map, o["slot"].data_ptr(), o["flags"].data_ptr(),
-                                                          self.d_mergeable.data_ptr(), self.d_mapflags.data_ptr(), self.d_pf.data_ptr(),
-                                                          D["s2m"] if D["s2m"] is not None else [self.d_slot2map[g].data_ptr() for g in range(NA)],
+                                                          self.d_mergeable.data_ptr(), self.d_mapflags.data_ptr(), self.d_pf.data_ptr(), D["s2m"],
                                                           D["att"].data_ptr(), D["reg"].data_ptr(), D["scr"].data_ptr(), self.d_map.data_ptr(),
                                                           self.d_cov.data_ptr(), self.sig_pix, d_counts=D["cnt"].data_ptr(), device=self.device,
-                                                          with_dynamic=True, merge=(cfg.merge_every > 0 and self._frame_now % cfg.merge_every == 0),   # CoSLAMThread.cpp:117-118
-                                                          d_merge_scratch=D["mscr"].data_ptr(), mergability=self._mergability, n_sweeps=0)
-            self._advance_refs(ps)   # (the sequential mode refines inside its camera loops over this frame's features; the references follow)
+                                                          with_dynamic=True, merge=merge, d_merge_scratch=D["mscr"].data_ptr(),
+                                                          mergability=lambda _stream: self._mergability(i), n_sweeps=0)
+            self._advance_refs(i)   # (the sequential mode refines inside its camera loops over this frame's features; the references follow)
             return
         if self.world > 1:
             self._gather_candidates()
         kinds = 3
-        if cfg.merge_every > 0 and self._frame_now % cfg.merge_every == 0:
-            # a bMerge frame: the static points' walks one after the other with checkUnify at a conflict, the dynamic points' behind them
-            o = self.reg_out
+        if merge:
+            # the static points' walks one after the other with checkUnify at a conflict, the dynamic points' behind them
             self.pose_upd.register_decide_merge_dev(ps, self.pu_args, self.n_map, 0, o["slot"].data_ptr(), o["flags"].data_ptr(),
                                                     self.d_mergeable.data_ptr(), self.d_mapflags.data_ptr(), self.d_pf.data_ptr(),
                                                     self.d_map.data_ptr(), self.d_cov.data_ptr(), self.sig_pix, D["att"].data_ptr(),
                                                     D["reg"].data_ptr(), D["mscr"].data_ptr(), D["mcnt"].data_ptr(),
                                                     d_list=self.d_curlist.data_ptr(), nList=cfg.p_reg)
-            self._refine(ps, D["reg"].data_ptr())
+            self._refine(i, D["reg"].data_ptr())
             self.n_merge_frames += 1
             kinds = 2
         if cfg.fused_registration and kinds == 3 and self.d_fref is not None:
-            self._decide_fused(ps, D)
+            self._decide_fused(i, dst, D)
             return
-        D["s2m"] = register_decide_static_dev(ps, NA, cfg.n_feat, self.n_map, 0, self.reg_out["slot"].data_ptr(), self.reg_out["flags"].data_ptr(),
-                                              self.d_mergeable.data_ptr(), self.d_mapflags.data_ptr(), self.d_pf.data_ptr(),
-                                              D["s2m"] if D["s2m"] is not None else [self.d_slot2map[g].data_ptr() for g in range(NA)],
+        # curStaticPointsRegInGroup and curDynamicPointsRegInGroup (currentMapPointsRegister, :834-853); n_sweeps 0: ONE launch that sweeps
+        # until the owners have settled
+        D["s2m"] = register_decide_static_dev(ps, NA, cfg.n_feat, self.n_map, 0, o["slot"].data_ptr(), o["flags"].data_ptr(),
+                                              self.d_mergeable.data_ptr(), self.d_mapflags.data_ptr(), self.d_pf.data_ptr(), D["s2m"],
                                               D["att"].data_ptr(), D["reg"].data_ptr(), D["scr"].data_ptr(), D["cnt"].data_ptr(), device=self.device,
-                                              kinds=kinds, n_sweeps=0)   # (0: ONE launch that sweeps until the owners have settled)   # curStaticPointsRegInGroup and curDynamicPointsRegInGroup (currentMapPointsRegister, :834-853)
-        self._refine(ps, D["reg"].data_ptr())
+                                              kinds=kinds, n_sweeps=0)
+        self._refine(i, D["reg"].data_ptr())
         if cfg.revisit_rounds > 0 and kinds == 3:
-            self._revisit_rounds(ps, D)
+            self._revisit_rounds(i, dst, D)
 
-    def _decide_fused(self, ps, D):
+    def _decide_fused(self, i, dst, D):
         """the single pass, its refine and the second visits' rounds with the launches fused (tools/cxx/frame_loop.cpp's sequence): 2 + 4 per
         round instead of 3 + 6; the same map, tables and poses"""
-        from coslam_amd.register import register_decide_kinds_rounds_dev, register_revisit_decide_next_dev, register_search_passes_dev
-
-        cfg, NA, R = self.cfg, self.cfg.n_cams, self.cfg.revisit_rounds
-        o = self.reg_out
-        s2m = D["s2m"] if D["s2m"] is not None else [self.d_slot2map[g].data_ptr() for g in range(NA)]
+        cfg, NA, R, ps, o = self.cfg, self.cfg.n_cams, self.cfg.revisit_rounds, self.pose_s.cuda_stream, self.reg_out
         D["s2m"] = register_decide_kinds_rounds_dev(ps, NA, cfg.n_feat, self.n_map, 0, o["slot"].data_ptr(), o["flags"].data_ptr(), self.d_mergeable.data_ptr(),
-                                                    self.d_mapflags.data_ptr(), self.d_pf.data_ptr(), s2m, D["att"].data_ptr(), D["reg"].data_ptr(),
+                                                    self.d_mapflags.data_ptr(), self.d_pf.data_ptr(), D["s2m"], D["att"].data_ptr(), D["reg"].data_ptr(),
                                                     D["scr"].data_ptr(), self.d_rvlists.data_ptr() if R > 0 else 0, self.RV_CAP, R, self.d_rvcounts.data_ptr(),
                                                     self.d_rv_visit.data_ptr(), self.d_rv_next.data_ptr(), d_counts=D["cnt"].data_ptr(), device=self.device)
         adv = lambda lst, n, all_, sel, clr: self.pose_upd.feat_ref_advance_refine_dev(   # noqa: E731
-            ps, self.pu_args, self.n_map, self.d_pf.data_ptr(), self._frame_now, self.d_fref.data_ptr(), self.d_rstat.data_ptr(), lst, n, all_, sel, clr,
+            ps, self.pu_args, self.n_map, self.d_pf.data_ptr(), i, self.d_fref.data_ptr(), self.d_rstat.data_ptr(), lst, n, all_, sel, clr,
             self.d_map.data_ptr(), self.d_cov.data_ptr(), self.sig_pix, d_counts=self.d_fref_counts.data_ptr())
         adv(self.d_curlist.data_ptr(), cfg.p_reg, True, D["reg"].data_ptr(), False)
         for r in range(R):
             lst = self.d_rvlists[r].data_ptr()
-            register_search_passes_dev(ps, self.reg_args[self._dst_now], cfg.n_feat, cfg.W, cfg.H, self.rv_passes[r], device=self.device)
+            register_search_passes_dev(ps, self.reg_args[dst], cfg.n_feat, cfg.W, cfg.H, self.rv_passes[r], device=self.device)
             self.pose_upd.register_mergability_running_dev(ps, self.pu_args, self.n_map, self.d_map.data_ptr(), self.d_cov.data_ptr(), o["slot"].data_ptr(),
                                                            self.sig_pix, self.d_merge_cache.data_ptr(), self.d_mergeable.data_ptr(), tolPix=0.0, d_counts=0,
                                                            cam0=0, nCamsRun=NA, d_list=lst, nList=self.RV_CAP, d_flags=o["flags"].data_ptr())
@@ -985,47 +955,46 @@ class FrameLoop:
                                              d_nextCount=self.d_rvcounts[r + 1:].data_ptr() if more else 0, d_overflow=self.d_rvcounts[R:].data_ptr())
             adv(lst, self.RV_CAP, False, self.d_rv_reg[0].data_ptr(), True)
 
-    def _revisit_rounds(self, ps, D):
+    def _revisit_rounds(self, i, dst, D):
         """The reference's SECOND VISITS (src/app/SL_CoSLAM.cpp:864-869, :889-893) behind the single pass and its refine: the points that
         registered are visited again in their next camera's loop, from their refined positions -- list, search, whole-track mergability
         (no cached tail: tolPix 0), the walks, refine; the points that registered again go round once more.  Every rank plays the rounds
         for ALL cameras on its replica (the lists are short): no collective."""
-        from coslam_amd.register import register_revisit_decide_dev, register_revisit_list_dev, register_search_passes_dev
-
-        cfg, NA = self.cfg, self.cfg.n_cams
+        cfg, NA, ps, o = self.cfg, self.cfg.n_cams, self.pose_s.cuda_stream, self.reg_out
         reg_in, keep = D["reg"], True
         for r in range(cfg.revisit_rounds):
             reg_out = self.d_rv_reg[r & 1]
             register_revisit_list_dev(ps, NA, self.n_map, self.RV_CAP, r == 0, self.d_pf.data_ptr(), D["att"].data_ptr(), reg_in.data_ptr(), keep,
                                       self.d_rv_visit.data_ptr(), self.d_rv_next.data_ptr(), self.d_rvlist.data_ptr(), self.d_rv_listcounts.data_ptr(),
                                       device=self.device, d_regOutClear=reg_out.data_ptr())
-            register_search_passes_dev(ps, self.reg_args[self._dst_now], cfg.n_feat, cfg.W, cfg.H, self.rv_pass, device=self.device)
+            register_search_passes_dev(ps, self.reg_args[dst], cfg.n_feat, cfg.W, cfg.H, self.rv_pass, device=self.device)
             self.pose_upd.register_mergability_running_dev(ps, self.pu_args, self.n_map, self.d_map.data_ptr(), self.d_cov.data_ptr(),
-                                                           self.reg_out["slot"].data_ptr(), self.sig_pix, self.d_merge_cache.data_ptr(),
+                                                           o["slot"].data_ptr(), self.sig_pix, self.d_merge_cache.data_ptr(),
                                                            self.d_mergeable.data_ptr(), tolPix=0.0, d_counts=0, cam0=0, nCamsRun=NA,
-                                                           d_list=self.d_rvlist.data_ptr(), nList=self.RV_CAP, d_flags=self.reg_out["flags"].data_ptr())
+                                                           d_list=self.d_rvlist.data_ptr(), nList=self.RV_CAP, d_flags=o["flags"].data_ptr())
             D["s2m"] = register_revisit_decide_dev(ps, NA, cfg.n_feat, self.n_map, self.RV_CAP, 0, 3, self.d_rvlist.data_ptr(), self.d_rv_next.data_ptr(),
-                                                   self.d_rv_visit.data_ptr(), self.reg_out["slot"].data_ptr(), self.reg_out["flags"].data_ptr(),
+                                                   self.d_rv_visit.data_ptr(), o["slot"].data_ptr(), o["flags"].data_ptr(),
                                                    self.d_mergeable.data_ptr(), self.d_mapflags.data_ptr(), self.d_pf.data_ptr(), D["s2m"],
                                                    D["att"].data_ptr(), reg_out.data_ptr(), D["scr"].data_ptr(), self.d_curlist.data_ptr(),
                                                    self.d_curcount.data_ptr(), cfg.p_reg, self.d_rv_counts.data_ptr(), device=self.device,
                                                    d_listCount=self.d_rv_listcounts.data_ptr())
-            self._refine(ps, reg_out.data_ptr(), self.d_rvlist.data_ptr(), self.RV_CAP)   # (the round changed the listed points only)
+            self._refine(i, reg_out.data_ptr(), self.d_rvlist.data_ptr(), self.RV_CAP)   # (the round changed the listed points only)
             reg_in, keep = reg_out, False
 
-    def _advance_refs(self, ps, d_list=None, n_list=0):
-        """MapPoint::pFeatures of this frame: cs_feat_ref_advance_dev behind whatever changed pointFeat (hand-back, classification, the
+    def _advance_refs(self, i, d_list=None, n_list=0):
+        """MapPoint::pFeatures of frame i: cs_feat_ref_advance_dev behind whatever changed pointFeat (hand-back, classification, the
         registration's decisions) -- tracked on / first feature / re-linked behind an older one / stale / detached.  Idempotent within a frame;
         d_list: a further call of the frame over just the rows a registration round has changed."""
         if self.d_fref is not None:
-            self.pose_upd.feat_ref_advance_dev(ps, self.pu_args, self.n_map, self.d_pf.data_ptr(), self._frame_now, self.d_fref.data_ptr(),
+            self.pose_upd.feat_ref_advance_dev(self.pose_s.cuda_stream, self.pu_args, self.n_map, self.d_pf.data_ptr(), i, self.d_fref.data_ptr(),
                                                d_refStatic=self.d_rstat.data_ptr(), d_counts=self.d_fref_counts.data_ptr(), d_list=d_list, nList=n_list)
 
-    def _refine(self, ps, d_select, d_list=None, n_list=0):
+    def _refine(self, i, d_select, d_list=None, n_list=0):
         """CoSLAM::refineMapPoint of the points that gained a feature (:889-893, :666-713) -- over the feature references when they are kept
         (stale features of other cameras are views, a re-registered point's second view comes from its OLD chain), else over this frame's"""
+        ps = self.pose_s.cuda_stream
         if self.d_fref is not None:
-            self._advance_refs(ps, d_list, n_list)
+            self._advance_refs(i, d_list, n_list)
             self.pose_upd.refine_map_points_ref_dev(ps, self.pu_args, self.d_fref.data_ptr(), self.n_map, self.d_map.data_ptr(), self.d_cov.data_ptr(),
                                                     self.sig_pix, d_select=d_select)
         else:
@@ -1035,36 +1004,22 @@ class FrameLoop:
     def _gather_candidates(self):
         """the own cameras' columns of the current-static pass's candidate tables to every rank (18 KB per camera: latency-bound, ONE
         collective), so that every rank takes the same registration decisions on its replica"""
-        import ctypes as C_
-
-        import coslam_amd
-        from coslam_amd._lib import check
-
-        torch, cfg, nc, NA, P = self.torch, self.cfg, self.nc, self.cfg.n_cams, self.cfg.p_reg   # P: rows of a record = the list's cap
-        L, vp, ps = coslam_amd.lib(), C_.c_void_p, self.pose_s.cuda_stream
-        if not hasattr(self, "_cand"):
-            self._cand = (torch.zeros(3 * nc * P, dtype=torch.int32, device=self.dev), torch.zeros(3 * nc * P * self.world, dtype=torch.int32, device=self.dev))
-            torch.cuda.synchronize()   # (zero-filled on torch's stream, used on the pose stream)
+        NA, nc, P = self.cfg.n_cams, self.nc, self.cfg.p_reg   # P: rows of a record = the list's cap
+        L, vp, ps, o = coslam_amd.lib(), C.c_void_p, self.pose_s.cuda_stream, self.reg_out
         send, recv = self._cand
-        o = self.reg_out
         check(L.cs_register_candidates_pack_list_dev(self.device, vp(ps), P, NA, self.c0, nc, vp(self.d_curlist.data_ptr()), vp(o["slot"].data_ptr()),
                                                      vp(o["flags"].data_ptr()), vp(self.d_mergeable.data_ptr()), vp(send.data_ptr())),
               "cs_register_candidates_pack_list_dev")
-        if self.native is not None:
-            L.cs_comm_allgather_dev.argtypes = [vp, vp, vp, vp, C_.c_size_t]
-            check(L.cs_comm_allgather_dev(self.native.exchange_comm, vp(ps), vp(send.data_ptr()), vp(recv.data_ptr()), send.numel() * 4),
-                  "cs_comm_allgather_dev")
-        else:
-            import torch.distributed as dist
-
-            with torch.cuda.stream(self.pose_s):
-                dist.all_gather_into_tensor(recv, send)
+        self._allgather(send, recv, send.numel() * 4)
         check(L.cs_register_candidates_unpack_list_dev(self.device, vp(ps), P, NA, nc, self.rank, vp(self.d_curlist.data_ptr()), vp(recv.data_ptr()),
                                                        vp(o["slot"].data_ptr()), vp(o["flags"].data_ptr()), vp(self.d_mergeable.data_ptr())),
               "cs_register_candidates_unpack_list_dev")
 
+    # ---------------------------------------------------------------------------------------------------------------
     def _key_frame(self, i, dst, snap=None):
-        cfg, ps, NA = self.cfg, self.pose_s.cuda_stream, self.cfg.n_cams
+        """the key-frame actions: the inter-camera solve (its rank's turn), the push of key frame i into the window ring -- its records
+        and poses as they stand (dst), or as kept in `snap` for a lagged decision -- and the window's request"""
+        cfg, ps = self.cfg, self.pose_s.cuda_stream
         k_ic = self.n_key
         self.n_key += 1
         if cfg.with_intercam and (k_ic + self.world // 2) % self.world == self.rank:
@@ -1073,8 +1028,7 @@ class FrameLoop:
             # held fixed, the dynamic points free; sigma 6, 3 x 40
             with self._sec("kf_intercam"):
                 if self.icam is not None:
-                    w = self.n_my_ic % self.n_ic_workers
-                    self.icams[w].solve_async(self.ic_wss[w], ps, self.ic_cams, cfg.W, cfg.H, cfg.n_col_blk, cfg.n_row_blk, self.d_R[dst].data_ptr(),
+                    self.icam.solve_async(self.ic_ws, ps, self.ic_cams, cfg.W, cfg.H, cfg.n_col_blk, cfg.n_row_blk, self.d_R[dst].data_ptr(),
                                           self.d_t[dst].data_ptr(), self.d_map.data_ptr(), self.d_mapflags.data_ptr(), self.d_newpt.data_ptr(),
                                           self.d_pf.data_ptr(), 6.0, 3, 40)
                 else:
@@ -1085,17 +1039,21 @@ class FrameLoop:
             self.n_my_ic += 1
         if self.win is None:
             return
-        # this key frame into the ring (every camera's records and poses: identical on every rank), then requestForBA(5, 2, 2, 30):
-        # the numCams * 2 oldest key cameras held, 2 points held, maxIter 2, inner 10 -- solved by ONE rank
+        # this key frame into the ring (every camera's records and poses: identical on every rank)
         with self._sec("kf_push"):
-            if snap is not None:   # (a lagged decision: the key frame's own records and poses, kept in the ring)
+            if snap is not None:
                 self.win.push_dev(ps, snap["hb"], self.d_K1.data_ptr(), 1, snap["R"].data_ptr(), snap["t"].data_ptr(), i)
             else:
                 self.win.push_dev(ps, self.hb_all, self.d_K1.data_ptr(), 1, self.d_R[dst].data_ptr(), self.d_t[dst].data_ptr(), i)
         self.n_pushed += 1
         self.pushed_frames = (self.pushed_frames + [i])[-cfg.n_key_frames:]   # the ring's key frames, oldest first
-        if self.n_pushed < cfg.n_key_frames:
-            return
+        if self.n_pushed >= cfg.n_key_frames:
+            self._request_window(i)
+
+    def _request_window(self, i):
+        """requestForBA(5, 2, 2, 30) at key frame i: the numCams * 2 oldest key cameras held, 2 points held, maxIter 2, inner 10 -- window k
+        solved by rank k mod N -- and the frame its result is applied at, lag key-frame intervals later (_apply_due)"""
+        cfg = self.cfg
         if self.skip_busy:
             # the reference's own policy (CoSLAM::requestForBA, src/app/SL_CoSLAM.cpp:1750-1755): a request that finds the previous bundle
             # adjustment still running is dropped.  "Running" is asked when the DEVICE has reached this key frame (the host enqueues
@@ -1107,19 +1065,48 @@ class FrameLoop:
         k = self.n_windows
         self.n_windows += 1
         owner = k % self.world
-        if owner == self.rank:
-            with self._sec("kf_request"):
-                self.win.solve_flags_async(self.ba_ws, ps, self.d_map.data_ptr(), self.d_mapflags.data_ptr(), 2 * NA, 2, 6.0, 2, 10)
-            self.my_seq[k] = self.n_my_solves
-            self.n_my_solves += 1
         # the record's sequence number ON ITS OWNER: windows go round the ranks, so it is the owner's (k // world)-th solve (one rank:
         # its own count, which the reference's request policy -- skip_busy -- may leave behind k)
-        seq = self.my_seq[k] if owner == self.rank else k // self.world
-        first = i - (cfg.n_key_frames - 1) * cfg.key_every
-        if cfg.keyframe_drives:
-            first = list(self.pushed_frames)   # the window's key frames where the decision put them
-        self.apply_at[i + self.lag * cfg.key_every] = (k, owner, first, seq)
+        seq = k // self.world
+        if owner == self.rank:
+            with self._sec("kf_request"):
+                self.win.solve_flags_async(self.ba_ws, self.pose_s.cuda_stream, self.d_map.data_ptr(), self.d_mapflags.data_ptr(), 2 * cfg.n_cams,
+                                           2, 6.0, 2, 10)
+            seq = self.n_my_solves
+            self.n_my_solves += 1
+        # the window's key frames: on the cadence, or (keyframe_drives) where the decision put them
+        frames = list(self.pushed_frames) if cfg.keyframe_drives else None
+        first = frames[0] if frames is not None else i - (cfg.n_key_frames - 1) * cfg.key_every
+        self.apply_at[i + self.lag * cfg.key_every] = (k, owner, seq, first, frames)
 
+    def _apply_due(self, i, src):
+        """RobustBundleRTS::output() of the window whose lag ends at this frame, before anything of frame i touches the map"""
+        due = self.apply_at.pop(i, None)
+        if due is None:
+            return
+        k, owner, seq, first, frames = due
+        if frames is not None and (i - 1) - first + 1 > self.pose_upd.storeLen:   # (the frames the history KEEPS: hist_store, not the walks' depth)
+            # the camera graphs would start behind the pose history's oldest frame: the record is consumed, nothing is written back
+            self.kf["not_applied"] += 1
+            return
+        if owner == self.rank:
+            # device_wait: the pose stream waits ON THE DEVICE for this rank's worker to publish the record, the host goes on enqueueing frames
+            rec = self.out.wait_dev(seq, self.pose_s.cuda_stream) if self.cfg.device_wait else self.out.wait(seq)
+        else:
+            rec = self.recv_rec[k & 1].data_ptr()
+        if self.world > 1:
+            self.xchg.broadcast(rec, self.out.record_bytes, owner, self.device, self.pose_s)
+        ps, args = self.pose_s.cuda_stream, (self.pose_upd, self.win, self.pu_args, self.d_pf.data_ptr(), self.n_map, self.d_map.data_ptr(),
+                                             self.d_cov.data_ptr(), self.d_mapflags.data_ptr(), self.sig_pix)
+        if frames is not None:
+            self.out.apply_frames_dev(rec, ps, *args, frames, self.d_R[src].data_ptr(), self.d_t[src].data_ptr(), self.d_apply_counts.data_ptr(), seq=seq)
+        else:
+            self.out.apply_dev(rec, ps, *args, first, self.cfg.key_every, self.d_R[src].data_ptr(), self.d_t[src].data_ptr(),
+                               self.d_apply_counts.data_ptr(), seq=seq)
+        self.applied += 1
+        self.last_apply = dict(window=k, solved_by_rank=owner, first_key_frame=first, applied_at_frame=i)
+
+    # ---------------------------------------------------------------------------------------------------------------
     def measure_collectives(self, n=40):
         """GPU-clock latency of each of the frame loop's collectives as THIS loop issues them (the buffers of the last frame, the pose
         stream; every rank calls it at the same point): microseconds per call, averaged over n back-to-back calls.  N = 1: {}."""
@@ -1145,7 +1132,7 @@ class FrameLoop:
                 self.xchg.all_gather(ps)
 
         timed("all_gather_features_and_poses_per_frame", gather_features)
-        if self.cfg.with_register and self.cfg.with_decide and self.pose_upd is not None and hasattr(self, "_cand"):
+        if self._cand is not None:
             timed("all_gather_registration_candidates_per_frame", self._gather_candidates)
         if self.ncc is not None:
             timed("all_gather_ncc_records_every_4th_frame", self._gather_ncc_records)
@@ -1162,22 +1149,18 @@ class FrameLoop:
         """the worker threads' queues are part of the work: every requested solve completes.  A window / a rig that holds no usable point
         (every map point of its key frames false, say) is a solve with nothing to do, not a failure of the loop: it packed an empty
         record (ok = 0, applies nothing) and is counted here."""
-        import coslam_amd
-
         for w in self.ic_wss + [self.ba_ws]:
             try:
                 w.wait()
             except coslam_amd.CoslamHipError as ex:
                 if "no map point has two feature points" in str(ex) or "no static feature point carries a map point" in str(ex):
-                    self.n_empty_solves = getattr(self, "n_empty_solves", 0) + 1
+                    self.n_empty_solves += 1
                 else:
                     raise
         self.torch.cuda.synchronize()
 
     def digest_parts(self):
         """per-array short digests (diagnostic: finding where two runs part ways)"""
-        import hashlib
-
         self.drain()
         names = ("map", "cov", "mapflags", "slot2map", "trackspan", "xy", "state", "isstatic", "R0", "R1", "t0", "t1", "pf", "newpt", "sfn")
         arrs = (self.d_map, self.d_cov, self.d_mapflags, self.d_slot2map, self.d_trackspan, self.d_xy, self.d_state, self.d_isstatic,
@@ -1186,8 +1169,6 @@ class FrameLoop:
 
     def digest(self):
         """sha256 over the state every rank must agree on (the map, its flags and covariances, every camera's records and poses)"""
-        import hashlib
-
         self.torch.cuda.synchronize()
         h = hashlib.sha256()
         for t in (self.d_map, self.d_cov, self.d_mapflags, self.d_slot2map, self.d_trackspan, self.d_xy, self.d_state, self.d_isstatic,
