@@ -22,6 +22,11 @@ the whole rig, i.e. every camera's image consumed and poses updated:
     N > 1         the cameras are sharded over the ranks (8 / N each); per frame one all-gather of {features, pose} of
                   every camera; the joint BA is sliced by points over the ranks with one all-reduce of S || rhs per LM step.
 Inputs (images, map points, BA problems) are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs: set-up, warm-up and the timed steps of the Python loop (and --dump-outputs), then the
+same stretch of the sequence in the C++ loop, whose rate is `value`.  Everything else the line can carry -- the upload-inclusive
+repetition, the secondary legs, the roofline of the dominant kernel, the CPU baseline, at N > 1 the collectives' timing and the
+comparison of the ranks' replicas -- runs with --full.
 """
 import argparse
 import ctypes as C
@@ -563,6 +568,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the upload-inclusive repetition, the secondary legs, the roofline, "
+                         "the CPU baseline, at N > 1 the collectives' timing and the replicas' comparison (the --no-* options below leave "
+                         "parts of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--ba-lag", type=int, default=int(os.environ.get("BENCH_BA_LAG", "0")),
                     help="key-frame intervals between a window's key frame and the frame its bundle adjustment is written back into the "
@@ -599,7 +608,7 @@ def main():
     ap.add_argument("--klt-xcd-placement", type=int, default=int(os.environ.get("BENCH_KLT_XCD", "1")),
                     help="1: the persistent tracker numbers its workgroups so that a camera lands on its own XCD; 0: cameras as grid rows")
     ap.add_argument("--live-pmc", type=int, default=int(os.environ.get("BENCH_LIVE_PMC", "1")),
-                    help="1 (default): roofline.traffic / valu are collected by THIS run -- three rocprofv3 --pmc passes of the 8-camera KLT stage in "
+                    help="with --full, 1 (default): roofline.traffic / valu are collected by THIS run -- three rocprofv3 --pmc passes of the 8-camera KLT stage in "
                          "child processes behind the timed loops, a few seconds each, bounded by timeouts; a pass that fails falls back to the "
                          "committed profiles/r05_tracker_pmc.json and says so.  0: read the committed file")
     ap.add_argument("--keyframe-decision", type=int, default=0,
@@ -624,6 +633,7 @@ def main():
                          "(float64); the frames, the set-up and the steps are fixed by the arguments, so two builds can be compared output for output")
     ap.add_argument("--native-comm", type=int, default=1, help="N > 1: collectives issued by libcoslam_hip (RCCL behind the C-ABI) instead of torch.distributed")
     args = ap.parse_args()
+    secondary = args.full and not args.no_secondary
 
     # `python bench.py --gpus N` started bare (no launcher: WORLD_SIZE unset) spawns its own N ranks, one per GPU, through
     # torch.distributed.run on 127.0.0.1 and a free port, and hands their exit code on.  Started BY a launcher the world size
@@ -800,7 +810,7 @@ def main():
                   "inter_camera": {"solves": wi[0], "ms_total": wi[1], "ms_max": wi[3], "share_of_timed_region": wi[1] / (dt * 1e3),
                                    "workspaces_the_key_frames_rotate_over": loop.n_ic_workers}}
     with_upload = None
-    if not args.no_upload_leg:
+    if args.full and not args.no_upload_leg:
         # the same loop once more, the images coming from pinned host memory every frame (same key-frame cadence, same drain):
         # one pinned ring entry per frame, the cameras' images back to back, as capture threads writing into cs_pinned_alloc'd
         # memory would leave them -> ONE host-to-device copy per frame
@@ -823,7 +833,7 @@ def main():
                                "loop (cs_klt_group_stage_h: copy stream + ring of 3 device slots, two frames ahead of the tracker)"}
         loop.stage_slot.clear()
     ref_policy = None
-    if world == 1 and not args.no_secondary and loop.out is not None:
+    if world == 1 and secondary and loop.out is not None:
         # SECONDARY: the reference's own request policy -- CoSLAM::requestForBA refuses a request while the previous bundle adjustment
         # is still running (src/app/SL_CoSLAM.cpp:1750-1755) -- instead of solving every key frame's window: same loop, same frames
         loop.drain()
@@ -841,7 +851,7 @@ def main():
                       "what": "the same loop with the reference's request policy: a key frame's window BA is requested only when no bundle "
                               "adjustment is running (CoSLAM::requestForBA, SL_CoSLAM.cpp:1750-1755); the headline solves EVERY window"}
     seq_reg = single_pass = None
-    if world == 1 and not args.no_secondary and hasattr(loop, "_dec"):
+    if world == 1 and secondary and hasattr(loop, "_dec"):
         # SECONDARY: the registration of the current static points step for step as the reference runs it (camera loop after camera
         # loop, search + mergability + walks + refineMapPoint per loop: bit-identical to the reference's own run on its golden scenes,
         # tests/test_register_decide_gpu.py) instead of the headline's single pass: same loop, same frames, fewer steps
@@ -877,7 +887,7 @@ def main():
                        "what": "the same loop without the second visits' rounds (LoopConfig.revisit_rounds = 0): the registration of rounds 3-5, which "
                                "parts from the reference's order within a few registering frames (1 / 8 / 18 frames from three start frames)"}
     kf_leg = None
-    if world == 1 and not args.no_secondary and not args.keyframe_decision:
+    if world == 1 and secondary and not args.keyframe_decision:
         # SECONDARY: the reference's key-frame DECISION per frame beside the same loop (CoSLAM::IsReadyForKeyFrame + addKeyFrame's key-pose
         # bookkeeping on the device, pinned: tests/golden/keyframe_golden.npz); the key frames themselves stay on the fixed cadence
         loop.drain()
@@ -897,14 +907,14 @@ def main():
         loop.kf = None
     gc.enable()
     coll_us = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             loop.drain()
             coll_us = loop.measure_collectives()
         except Exception as ex:   # (a diagnostic: never the reason a bench line is lost)
             coll_us = {"error": str(ex)[:300]}
     replicas = None
-    if world > 1:
+    if world > 1 and args.full:
         # ONE map held N times: every rank hashes the state all ranks must agree on after the last frame
         import hashlib
 
@@ -916,6 +926,7 @@ def main():
         replicas = {"ranks": world, "identical_map_records_and_poses_on_every_rank": bool(all(torch.equal(v, allv[0]) for v in allv)),
                     "what": "sha256 over map points, covariances, flags, every camera's hand-back records, track spans, feature types and "
                             "poses, compared across the ranks after the last frame"}
+    if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
@@ -997,7 +1008,7 @@ def main():
             n_done += 1
 
     in_loop_us = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # the same kernel INSIDE the frame loop (every stream busy): 100 more frames of the whole loop with the tracker launch bracketed
         trks[0].set_profiling(True)
         run(20)
@@ -1007,7 +1018,7 @@ def main():
         p_in = trks[0].get_profile()
         trks[0].set_profiling(False)
         in_loop_us = p_in["tracker_us_total"] / max(p_in["frames"], 1) / max(p_in["launches_per_frame"], 1)
-    if rank == 0:
+    if rank == 0 and args.full:
         trks[0].set_profiling(True)
         replay(100)   # (also for a short --steps run: the first frames after the switch to profiling are slower)
         prof = trks[0].get_profile()
@@ -1059,7 +1070,7 @@ def main():
     # ---- secondary key: cfg2 (BASELINE.json configs[1]) = ONE camera on the GPU, KLT + hand-back + pose per frame, no
     # key-frame solves; same kernels through the single-handle entry points.  Not the headline; kept for continuity.
     cfg2 = None
-    if rank == 0 and n_gpus == 1 and not args.no_secondary:
+    if rank == 0 and n_gpus == 1 and secondary:
         for t in trks:
             t.set_cu_count(256)   # (the headline loop may have budgeted the tracker for fewer cameras per launch)
         n2 = min(args.steps, 200)
@@ -1103,7 +1114,7 @@ def main():
     # ---- secondary key: the sliding-window BA of cfg5 (BASELINE.json configs[4]: 4 cameras x 30 key frames = 120 poses of which 8
     # fixed, 5000 points, every point in every key frame: 600 k measurements, reduced system of order 672), one full robust solve
     cfg5 = None
-    if rank == 0 and n_gpus == 1 and not args.no_secondary:
+    if rank == 0 and n_gpus == 1 and secondary:
         from coslam_amd.synth import csr_of_problem, make_ba_problem
 
         pr5 = make_ba_problem(n_cams=120, n_pts=5000, W=1920, H=1080, noise=0.3, outlier_frac=0.01, outlier_mag=40.0, n_cams_con=8,
@@ -1130,7 +1141,7 @@ def main():
     # cs_newpts_from_pairs_dev.  (The frame loop's runs above find few pairs on the synthetic scene; this one has every track to
     # reconstruct.)
     newpts_loaded = None
-    if rank == 0 and n_gpus == 1 and not args.no_secondary:
+    if rank == 0 and n_gpus == 1 and secondary:
         try:
             newpts_loaded = _newpts_loaded_leg(dev)
         except Exception as e:   # (the fixture is data under tests/golden; a missing file must not cost the line)
@@ -1187,7 +1198,7 @@ def main():
         return res
 
     cfg5_klt = ref_default = None
-    if rank == 0 and n_gpus == 1 and not args.no_secondary:
+    if rank == 0 and n_gpus == 1 and secondary:
         from coslam_amd.synth import Scene as _Scene
 
         sc5 = _Scene(4, 1920, 1080, 12000, seed=0xC051A + 5, loop_period=6)
@@ -1206,7 +1217,7 @@ def main():
                                     "redetect + prefetch per frame")
 
     cpu = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         cores = os.cpu_count() or 1
         nt = min(cores, N_CAMS)
         joint = build_joint_problem(sc)
@@ -1377,7 +1388,7 @@ def main():
                                  "by one term per frame (cs_register_mergability_running_dev); counts summed over the whole run"),
                         "active_search": "off: the reference's activeMapPointsRegister cannot attach (numVisCam == 0 on actMapPts, SL_CoSLAM.cpp:1114; "
                                          "tests/cxx/ref_active_test.cpp)" if not cfg.with_active_search else "on (diagnostic)"},
-                       "key_frame_decision": loop.keyframe_stats() or "not run in this line (--keyframe-decision 1; secondary_keyframe_decision has a run)",
+                       "key_frame_decision": loop.keyframe_stats() or "not run in this line (--keyframe-decision 1; with --full, secondary_keyframe_decision has a run)",
                        "feature_references": None if getattr(loop, "d_fref", None) is None else dict(zip(
                            ("tracked_on", "first_features", "re_linked_behind_an_older_feature", "links_dropped_pool_full", "detached"),
                            loop.d_fref_counts.cpu().tolist()),

@@ -1,5 +1,5 @@
-"""bench.py's output contract on the MI355X: one JSON line with the driver's keys, the headline workload named, a roofline
-object for the dominant kernel and (when asked for) a CPU baseline -- and the data-coupled legs really ran."""
+"""bench.py's output contract on the MI355X: one JSON line with the driver's keys, the headline workload named; with --full a
+roofline object for the dominant kernel and (when asked for) a CPU baseline -- and the data-coupled legs really ran."""
 import json
 import os
 import subprocess
@@ -21,7 +21,7 @@ def _run_bench(extra, env=None, timeout=900):
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys(hip):
-    j = _run_bench(["--gpus", "1", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"])
+    j = _run_bench(["--gpus", "1", "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in j, k
@@ -69,8 +69,24 @@ def test_bench_prints_one_json_line_with_the_contract_keys(hip):
     assert abs(r["achieved"] - r["algorithmic_bytes_per_launch"] / (r["avg_launch_us"] * 1e-6) / 1e9) < 1e-6 * r["achieved"]
 
 
+def test_a_plain_run_does_what_the_headline_needs_and_no_more(hip, tmp_path):
+    """Without --full: set-up, warm-up, the timed steps of both loops, the outputs, the line -- `value` the C++ loop's rate as with
+    --full -- and none of the legs behind --full."""
+    import numpy as np
+
+    j = _run_bench(["--gpus", "1", "--steps", "10", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    cfg = j["config"]
+    assert j["steps"] == 10 and j["warmup"] == 2 and abs(j["value"] - 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+    assert cfg["value_source"] == "cxx_frame_loop" and cfg["cxx_frame_loop"]["frames_per_s"] == j["value"]
+    assert cfg["cxx_frame_loop"]["steps"] == 10 and cfg["python_frame_loop"]["frames_per_s"] > 0
+    assert j["roofline"] is None and j["cpu_baseline"] is None and cfg["with_upload"] is None
+    assert all(v is None for k, v in cfg.items() if k.startswith("secondary_") and k != "secondary_legs_note")
+    R, xy = np.load(tmp_path / "R.npy"), np.load(tmp_path / "feature_xy.npy")
+    assert R.shape == (8, 3, 3) and xy.dtype == np.float64 and np.load(tmp_path / "map_points.npy").shape[1] == 3
+
+
 TWO_RANKS_ON_ONE_GPU = dict(BENCH_FORCE_DEVICE="0", BENCH_DIST_BACKEND="gloo")
-SHORT = ["--no-cpu-baseline", "--no-secondary", "--no-cxx-loop", "--no-upload-leg"]
+SHORT = ["--full", "--no-cpu-baseline", "--no-secondary", "--no-cxx-loop", "--no-upload-leg"]   # (--full: the roofline, the replicas' comparison)
 
 
 def test_roofline_traffic_is_measured_by_the_run_that_prints_it(hip):
