@@ -34,4 +34,4 @@ from .poseupdate import (MAP_DYNAMIC, MAP_FALSE, MAP_UNCERTAIN, PoseUpdateCam, T
 from .ncc import (ncc_blocks_dev, ncc_epi_mat_dev, ncc_get_blocks_dev, ncc_match_between, ncc_match_between_full,  # noqa: F401,E402
                   ncc_scaled_dims)
 from .posegraph import PoseGraphs, after_ba_function, after_ba_record, posegraph_set_poses_dev  # noqa: F401,E402
-from .results import ExportCam, export_results_v1  # noqa: F401,E402
+from .results import ExportCam, LoopExportCam, export_results_v1, loop_export_results  # noqa: F401,E402

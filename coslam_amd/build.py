@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "newpts.hip",
     "posegraph.hip",
     "results.cpp",
+    "export.hip",
     "ba.hip",
     "comm.hip",
 ]

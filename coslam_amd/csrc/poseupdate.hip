@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "cs_common.h"
+#include "history_view.h"
 #include "small_ops.h"
 
 #pragma clang fp contract(off)
@@ -1917,6 +1918,21 @@ __global__ __launch_bounds__(256) void k_history_span(int set, int nCams, int fi
         *a = *b;
 }
 
+// the entry at ring slot rs of every camera (pixels [2N], R [9], t [3]) into archive entry a (same layout, archCap for H)
+__global__ __launch_bounds__(256) void k_history_archive(int nCams, int N, int H, int rs, int archCap, int a, const double* __restrict__ xy,
+                                                         const double* __restrict__ R, const double* __restrict__ t, double* axy, double* aR,
+                                                         double* aT) {
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x, per = 2 * (size_t)N + 12;
+    if (q >= (size_t)nCams * per) return;
+    const int c = (int)(q / per), e = (int)(q - (size_t)c * per);
+    if (e < 2 * N)
+        axy[((size_t)c * archCap + a) * 2 * N + e] = xy[((size_t)c * H + rs) * 2 * N + e];
+    else if (e < 2 * N + 9)
+        aR[((size_t)c * archCap + a) * 9 + (e - 2 * N)] = R[((size_t)c * H + rs) * 9 + (e - 2 * N)];
+    else
+        aT[((size_t)c * archCap + a) * 3 + (e - 2 * N - 9)] = t[((size_t)c * H + rs) * 3 + (e - 2 * N - 9)];
+}
+
 }  // namespace
 
 struct cs_track_history {
@@ -1947,6 +1963,11 @@ struct cs_track_history {
     unsigned char* mergeRefStatic;
     // poses rewritten in frames older than the walk depth (the running mergability verdict's cached tails: MgRunArgs::epoch)
     mutable int tailEpoch = 0, tailFromMin = 0x7fffffff;
+    // the whole-run archive behind the store (cs_track_history_set_archive): frames archFirst .. archFirst + archCount - 1, the entry a
+    // push is about to overwrite copied in first; same layout as the ring with archCap for H.  firstFrame: the oldest frame pushed since
+    // the history (re)started -- what an export needs to reach
+    int archCap = 0, archCount = 0, archFirst = 0, firstFrame = 0;
+    double *archXY = nullptr, *archR = nullptr, *archT = nullptr;
 };
 
 // the camera centres by walk depth, if the ring's poses changed since they were last computed
@@ -2001,6 +2022,7 @@ extern "C" void cs_track_history_destroy(cs_track_history* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipFree(h->xy), (void)hipFree(h->R), (void)hipFree(h->t), (void)hipFree(h->cen), (void)hipFree(h->segPool), (void)hipFree(h->segCount);
+    if (h->archXY) (void)hipFree(h->archXY), (void)hipFree(h->archR), (void)hipFree(h->archT);
     if (h->clsList) (void)hipFree(h->clsList);
     if (h->alive) (void)hipFree(h->alive);
     delete h;
@@ -2062,14 +2084,41 @@ void pu_fill_gate(PuArgs& A, const int* d_pointFeat, int nMap, double* d_mapPts,
     A.numNodes = d_numNodes, A.numOut = d_numOut;
 }
 
-// advance the ring to `frame` (host bookkeeping only; the launch writes the entry)
-void pu_advance(cs_track_history* h, int frame) {
+// advance the ring to `frame` (host bookkeeping; the launch writes the entry).  With an archive, the entry about to be overwritten -- the
+// oldest frame of a full store -- is copied into it first, on the same stream: every write-back that can reach that frame is enqueued
+// before this push (cs_track_history_create_ex's header comment), so the copy is final.  A full archive or a gap in the frame numbers
+// (which would drop the stored frames) is refused before anything moves.
+int pu_advance(const char* who, cs_track_history* h, hipStream_t s, int frame) {
+    if (frame == h->lastFrame) {   // the same frame again (camera-by-camera calls): the entry is rewritten
+        h->ringVersion += 1;
+        return CS_OK;
+    }
+    if (h->archCap > 0 && h->count > 0 && frame != h->lastFrame + 1) {
+        cs_set_error("%s: frame %d after %d: the history keeps an archive, whose frames must be consecutive", who, frame, h->lastFrame);
+        return CS_ERR_INVALID;
+    }
+    const bool spill = frame == h->lastFrame + 1 && h->count == h->H && h->archCap > 0;
+    if (spill && h->archCount >= h->archCap) {
+        cs_set_error("%s: the archive is full (%d frames, %d..%d): frame %d would push frame %d out of the store", who, h->archCap,
+                     h->archFirst, h->archFirst + h->archCount - 1, frame, frame - h->H);
+        return CS_ERR_INVALID;
+    }
     h->ringVersion += 1;
-    if (frame == h->lastFrame) return;  // the same frame again (camera-by-camera calls): the entry is rewritten
     if (frame != h->lastFrame + 1) h->count = 0;  // Track2D's length() counts frames: a gap in the numbering loses the history
     h->head = (h->head + 1) % h->H;
+    if (spill) {
+        if (h->archCount == 0) h->archFirst = frame - h->H;
+        CS_HIP(hipSetDevice(h->device));
+        const size_t n = (size_t)h->nCams * (2 * (size_t)h->N + 12);
+        hipLaunchKernelGGL(k_history_archive, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->nCams, h->N, h->H, h->head, h->archCap,
+                           h->archCount, (const double*)h->xy, (const double*)h->R, (const double*)h->t, h->archXY, h->archR, h->archT);
+        CS_HIP(hipGetLastError());
+        h->archCount += 1;
+    }
+    if (h->count == 0) h->firstFrame = frame;
     h->count = h->count < h->H ? h->count + 1 : h->H;
     h->lastFrame = frame;
+    return CS_OK;
 }
 
 void pu_fill_dyn(PuArgs& A, cs_track_history* h, int minLen, int minOutNum, double maxEpiErr, int* d_numDyn) {
@@ -2116,7 +2165,7 @@ extern "C" int cs_detect_dynamic_dev(cs_track_history* h, void* hip_stream, int 
     memset(&A, 0, sizeof(A));
     A.nCams = h->nCams, A.N = h->N, A.cam0 = cam0, A.nCamsRun = nCamsRun, A.R = d_R, A.t = d_t;
     A.nMap = nMap, A.mapFlags = (unsigned char*)d_mapFlags;
-    pu_advance(h, frame);
+    if ((rc = pu_advance("cs_detect_dynamic_dev", h, (hipStream_t)hip_stream, frame)) != CS_OK) return rc;
     pu_fill_dyn(A, h, minLen, minOutNum, maxEpiErr, d_numDyn);
     return pu_launch("cs_detect_dynamic_dev", h->device, hip_stream, A, cams, false, true);
 }
@@ -2140,7 +2189,7 @@ extern "C" int cs_pose_update_frame_dev(cs_track_history* h, void* hip_stream, c
     memset(&A, 0, sizeof(A));
     A.nCams = h->nCams, A.N = h->N, A.cam0 = 0, A.nCamsRun = h->nCams, A.R = d_R, A.t = d_t;
     pu_fill_gate(A, d_pointFeat, nMap, d_mapPts, d_mapCov, d_mapFlags, largeErr, pixelErrVar, d_numNodes, d_numOut);
-    pu_advance(h, frame);
+    if ((rc = pu_advance("cs_pose_update_frame_dev", h, (hipStream_t)hip_stream, frame)) != CS_OK) return rc;
     pu_fill_dyn(A, h, minLen, minOutNum, maxEpiErr, d_numDyn);
     return pu_launch("cs_pose_update_frame_dev", h->device, hip_stream, A, cams, true, true);
 }
@@ -2303,6 +2352,45 @@ extern "C" int cs_track_history_set_span_dev(cs_track_history* h, void* hip_stre
 }
 extern "C" int cs_track_history_newest_frame(const cs_track_history* h) { return h ? h->lastFrame : -0x7fffffff; }
 extern "C" int cs_track_history_cams(const cs_track_history* h) { return h ? h->nCams : 0; }
+
+extern "C" int cs_track_history_set_archive(cs_track_history* h, int capFrames) {
+    if (!h || capFrames < 0) {
+        cs_set_error("cs_track_history_set_archive: bad arguments");
+        return CS_ERR_INVALID;
+    }
+    if (h->archCount > 0 || (h->count > 0 && h->lastFrame - h->firstFrame + 1 > h->count)) {
+        cs_set_error("cs_track_history_set_archive: frames have already left the store (set the archive before the first push)");
+        return CS_ERR_INVALID;
+    }
+    CS_HIP(hipSetDevice(h->device));
+    if (h->archXY) (void)hipFree(h->archXY), (void)hipFree(h->archR), (void)hipFree(h->archT);
+    h->archXY = h->archR = h->archT = nullptr;
+    h->archCap = 0;
+    if (capFrames == 0) return CS_OK;
+    const size_t n = (size_t)h->nCams * capFrames;
+    if (hipMalloc((void**)&h->archXY, sizeof(double) * n * 2 * h->N) != hipSuccess || hipMalloc((void**)&h->archR, sizeof(double) * n * 9) != hipSuccess ||
+        hipMalloc((void**)&h->archT, sizeof(double) * n * 3) != hipSuccess) {
+        (void)hipFree(h->archXY), (void)hipFree(h->archR), (void)hipFree(h->archT);
+        h->archXY = h->archR = h->archT = nullptr;
+        cs_set_error("cs_track_history_set_archive: hipMalloc of %d frames (%.1f MB) failed", capFrames, (16.0 * h->N + 96) * n / 1e6);
+        return CS_ERR_HIP;
+    }
+    h->archCap = capFrames;
+    return CS_OK;
+}
+extern "C" int cs_track_history_archive_frames(const cs_track_history* h) { return h ? h->archCount : 0; }
+extern "C" int cs_track_history_first_frame(const cs_track_history* h) { return h ? (h->archCount > 0 ? h->archFirst : h->firstFrame) : 0; }
+
+// what the export reads of a handle (csrc/export.hip)
+void cs_history_view(const cs_track_history* h, CsHistView* v) {
+    v->device = h->device, v->nCams = h->nCams, v->N = h->N, v->H = h->H, v->head = h->head;
+    v->stored = h->count < h->H ? h->count : h->H;
+    v->lastFrame = h->lastFrame, v->firstFrame = h->firstFrame;
+    v->xy = h->xy, v->R = h->R, v->t = h->t;
+    v->archCap = h->archCap, v->archCount = h->archCount, v->archFirst = h->archFirst;
+    v->archXY = h->archXY, v->archR = h->archR, v->archT = h->archT;
+    v->segPool = h->segPool, v->segCount = h->segCount, v->segCap = h->segCap;
+}
 
 namespace {
 int up_launch(const char* who, const cs_track_history* h, void* hip_stream, const cs_poseupdate_cam* cams, UpArgs& A, int* d_counts, int nCounts) {
@@ -3220,7 +3308,7 @@ extern "C" int cs_pose_update_classify_frame_dev(cs_track_history* h, void* hip_
     memset(&A, 0, sizeof(A));
     A.nCams = h->nCams, A.N = h->N, A.cam0 = 0, A.nCamsRun = h->nCams, A.R = d_R, A.t = d_t;
     pu_fill_gate(A, d_pointFeat, nMap, d_mapPts, d_mapCov, d_mapFlags, largeErr, pixelErrVar, d_numNodes, d_numOut);
-    pu_advance(h, frame);
+    if ((rc = pu_advance("cs_pose_update_classify_frame_dev", h, s, frame)) != CS_OK) return rc;
     pu_fill_dyn(A, h, minLen, minOutNum, maxEpiErr, d_numDyn);
     const int par = h->clsPar;
     h->clsPar ^= 1;

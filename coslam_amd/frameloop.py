@@ -49,6 +49,7 @@ from coslam_amd.register import (register_cams, register_cur_static_sequential_d
                                  register_decide_scratch_bytes, register_decide_static_dev, register_list_current_dev, register_passes,
                                  register_revisit_decide_dev, register_revisit_decide_next_dev, register_revisit_list_dev,
                                  register_search_passes_dev)
+from coslam_amd.results import loop_export_results
 from coslam_amd.synth import csr_of_problem
 
 PIXEL_ERR_VAR = 10.0      # Const::PIXEL_ERR_VAR, reference src/app/SL_GlobParam.cpp:37
@@ -127,6 +128,8 @@ class LoopConfig:
         # wait can only end by timing out (2 s, counted by wait_errors).  The host wait returns once the worker has synchronised its
         # stream behind the pack (the record is complete); with the apply lag the solve is long done by then.
         self.device_wait = False
+        self.export_frames = 0     # > 0: a whole-run archive of that many frames behind the pose history (cs_track_history_set_archive), so that
+        # FrameLoop.export_results can write the whole run's trajectory and features; 0: off (nothing allocated, nothing launched)
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError(f"LoopConfig: unknown field {k}")
@@ -167,6 +170,8 @@ class FrameLoop:
             # a window's apply is keyed lag * key_every frames behind its key frame, which the decision places keyframe_lag frames late: the
             # apply would be due in the past and bundle adjustment silently off
             raise ValueError(f"LoopConfig.keyframe_lag {cfg.keyframe_lag}: must be below the BA apply lag of {self.lag} x {cfg.key_every} frames")
+        if cfg.export_frames > 0 and not (cfg.with_pose_update and cfg.feature_chains):
+            raise ValueError("LoopConfig.export_frames: the export reads the pose history and the feature references (with_pose_update, feature_chains)")
         if (cfg.n_key_frames - 1 + self.lag) * cfg.key_every + 1 > cfg.hist:
             raise ValueError("the pose history is shorter than a window + its apply lag")
         self.dev = torch.device("cuda", device)
@@ -329,6 +334,8 @@ class FrameLoop:
         self.pose_upd = self.d_fref = self.d_rstat = None
         if cfg.with_pose_update:
             self.pose_upd = TrackHistory(NA, N, cfg.hist, device=self.device, storeLen=max(cfg.hist_store, cfg.hist))
+            if cfg.export_frames > 0:
+                self.pose_upd.set_archive(cfg.export_frames)
             self.d_merge_cache = z(self.pose_upd.mergability_cache_bytes(n_map), torch.uint8)
             if cfg.feature_chains:
                 self.d_fref = torch.full((n_map, NA, 4), -1, dtype=torch.int32, device=self.dev)
@@ -1158,6 +1165,29 @@ class FrameLoop:
                 else:
                     raise
         self.torch.cuda.synchronize()
+
+    def export_results(self, dir_path, video_paths=None, start_frame_in_video=0, cov_as_reference=True):
+        """CoSLAM::exportResults (reference src/gui/CoSLAMThread.cpp, behind its frame loop): input_videos.txt, mappts.txt,
+        <c>_campose.txt and <c>_featpts.txt of the run so far into dir_path, from the device state (cs_loop_export_results) -- every
+        frame's poses from the history's store and archive (LoopConfig.export_frames), the features from the feature references.  Drains
+        first.  Every rank holds the same map and history: rank 0 writes, the others return None.  video_paths: one per camera
+        (default camera_<c>).  Returns dict(points, features, features_from_archive)."""
+        cfg = self.cfg
+        if cfg.export_frames <= 0 or self.pose_upd is None or self.d_fref is None:
+            raise RuntimeError("FrameLoop.export_results: needs LoopConfig.export_frames > 0 (with the pose update and feature chains on)")
+        self.drain()
+        if self.rank != 0:
+            return None
+        NA = cfg.n_cams
+        paths = list(video_paths) if video_paths is not None else [f"camera_{c}" for c in range(NA)]
+        if len(paths) != NA:
+            raise ValueError(f"FrameLoop.export_results: {len(paths)} video paths for {NA} cameras")
+        K = np.ascontiguousarray(self.sc.K, np.float64).ravel()
+        cams = [dict(videoFilePath=paths[c], K=K, kc=np.zeros(5), W=cfg.W, H=cfg.H, startFrameInVideo=int(start_frame_in_video)) for c in range(NA)]
+        out = loop_export_results(dir_path, self.pose_upd, self.pose_s.cuda_stream, self.d_fref.data_ptr(), self.n_map, self.d_map.data_ptr(),
+                                  self.d_cov.data_ptr(), self.d_mapflags.data_ptr(), cams, cov_as_reference=cov_as_reference)
+        self.torch.cuda.synchronize()
+        return out
 
     def digest_parts(self):
         """per-array short digests (diagnostic: finding where two runs part ways)"""

@@ -68,6 +68,19 @@ class TrackHistory:
     def frames(self):
         return self._L.cs_track_history_frames(C.c_void_p(self._h))
 
+    def set_archive(self, cap_frames):
+        """cs_track_history_set_archive: keep every frame that leaves the store (pixels + poses) in a whole-run archive of cap_frames
+        frames (0: none); a push that would overflow it fails"""
+        check(self._L.cs_track_history_set_archive(C.c_void_p(self._h), int(cap_frames)), "cs_track_history_set_archive")
+
+    @property
+    def archive_frames(self):
+        return self._L.cs_track_history_archive_frames(C.c_void_p(self._h))
+
+    @property
+    def first_frame(self):
+        return self._L.cs_track_history_first_frame(C.c_void_p(self._h))
+
     def detect_dynamic_dev(self, stream_ptr, cams, d_R, d_t, nMap, d_mapFlags, frame, maxLen=20, minLen=5, minOutNum=3,
                            maxEpiErr=6.0, d_numDyn=None, cam0=0, nCamsRun=None):
         """detectDynamicFeaturePoints(20, 5, 3, Const::MAX_EPI_ERR) (reference src/app/SL_CoSLAM.cpp:361, 404-405)."""

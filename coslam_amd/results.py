@@ -1,6 +1,6 @@
 """Result text files of a run (cs_export_results_v1): what CoSLAM::exportResultsVer1 writes (reference
-src/app/SL_CoSLAM.cpp:1914-2028) -- input_videos.txt, mappts.txt, <c>_campose.txt, <c>_featpts.txt -- from arrays.  Host code
-only; no GPU is needed to call it."""
+src/app/SL_CoSLAM.cpp:1914-2028) -- input_videos.txt, mappts.txt, <c>_campose.txt, <c>_featpts.txt -- from arrays (host code only; no
+GPU is needed to call it), or from a frame loop's device state (cs_loop_export_results: loop_export_results)."""
 import ctypes as C
 
 import numpy as np
@@ -42,3 +42,31 @@ def export_results_v1(dir_path, cams, cur_frame, pt_id, pt_M, pt_cov, cov_as_ref
     path = dir_path if isinstance(dir_path, bytes) else str(dir_path).encode()
     check(lib().cs_export_results_v1(path, len(cams), arr, int(cur_frame), len(pt_id), p(pt_id), p(pt_M), p(pt_cov),
                                      1 if cov_as_reference else 0), "cs_export_results_v1")
+
+
+class LoopExportCam(C.Structure):
+    """== cs_loop_export_cam (include/coslam_hip.h)."""
+
+    _fields_ = [("videoFilePath", C.c_char_p), ("K", C.c_void_p), ("kc", C.c_void_p), ("W", C.c_int), ("H", C.c_int),
+                ("startFrameInVideo", C.c_int)]
+
+
+def loop_export_results(dir_path, history, stream_ptr, d_feat_ref, n_map, d_M, d_cov, d_map_flags, cams, cov_as_reference=True):
+    """cs_loop_export_results: the six files from a loop's device state.  history: a poseupdate.TrackHistory (store + archive);
+    d_feat_ref / d_M / d_cov / d_map_flags: device pointers ([nMap][nCams] cs_feat_ref, [nMap][3], [nMap][9], [nMap]); cams: list of
+    dicts(videoFilePath, K[9], kc[5], W, H, startFrameInVideo).  Synchronous.  Returns dict(points, features, features_from_archive)."""
+    keep, arr = [], (LoopExportCam * len(cams))()
+    for a, c in zip(arr, cams):
+        K = np.ascontiguousarray(c["K"], np.float64).reshape(9)
+        kc = np.ascontiguousarray(c.get("kc", np.zeros(5)), np.float64).reshape(5)
+        keep += [K, kc]
+        path = c["videoFilePath"]
+        a.videoFilePath = path if isinstance(path, bytes) else str(path).encode()
+        a.K, a.kc = K.ctypes.data, kc.ctypes.data
+        a.W, a.H, a.startFrameInVideo = int(c["W"]), int(c["H"]), int(c.get("startFrameInVideo", 0))
+    stats = (C.c_longlong * 3)()
+    vp = C.c_void_p
+    path = dir_path if isinstance(dir_path, bytes) else str(dir_path).encode()
+    check(lib().cs_loop_export_results(path, vp(history._h), vp(stream_ptr), vp(d_feat_ref), int(n_map), vp(d_M), vp(d_cov), vp(d_map_flags),
+                                       arr, 1 if cov_as_reference else 0, stats), "cs_loop_export_results")
+    return dict(points=int(stats[0]), features=int(stats[1]), features_from_archive=int(stats[2]))

@@ -630,6 +630,23 @@ int cs_track_history_get_span_dev(const cs_track_history* h, void* hip_stream, i
 int cs_track_history_set_span_dev(cs_track_history* h, void* hip_stream, int firstFrame, int nFrames, const double* d_R, const double* d_t);
 int cs_track_history_newest_frame(const cs_track_history* h); /* the frame of the newest entry */
 int cs_track_history_cams(const cs_track_history* h);
+/* The WHOLE-RUN ARCHIVE behind the store: capFrames (0 = none, the default) frames of what the store holds per frame -- every slot's
+ * hand-back pixel (double x, y as the ring keeps them) and the pose of every camera: 16 N + 96 bytes per camera and frame, 256 KB per frame
+ * at 8 cameras x 2000 slots.  Set it before frames leave the store.  When a push (cs_pose_update_frame_dev, cs_detect_dynamic_dev,
+ * cs_pose_update_classify_frame_dev) is about to overwrite the store's oldest frame, it first copies that frame's entry into the archive on
+ * its own stream, no host wait.  A push that finds the archive full fails (CS_ERR_INVALID, cs_last_error says so) and moves nothing: no
+ * frame is ever dropped silently; so does a push whose frame number skips (a gap restarts the history and would drop the stored frames).
+ * An archived pose is FINAL: every write-back into the history reaches only frames the store still holds --
+ *   cs_track_history_set_poses_dev skips the (camera, frame) pairs the ring does not hold (judged when it is enqueued);
+ *   cs_track_history_set_span_dev / _get_span_dev refuse a span that is not all in the ring, and cs_ba_output_apply_*_dev read
+ *   (get_span) the span from the window's first key frame before they write anything, so an apply whose first key frame has left the
+ *   store is refused;
+ * -- and every such call is enqueued before the push that moves the frame out, on the stream that owns the history (calls on one handle
+ * belong on one stream).  Nothing can reach an archived frame after its copy was enqueued.  The walks never read the archive; only the
+ * export does (cs_loop_export_results). */
+int cs_track_history_set_archive(cs_track_history* h, int capFrames);
+int cs_track_history_archive_frames(const cs_track_history* h); /* frames archived so far */
+int cs_track_history_first_frame(const cs_track_history* h);    /* the oldest frame held, archive or store */
 int cs_update_new_poses_points_dev(const cs_track_history* h, void* hip_stream, const cs_poseupdate_cam* cams, const int* d_pointFeat,
                                    int nMap, const int* d_lastFrame, const unsigned char* d_isCurrent, int firstKeyFrame,
                                    double* d_mapPts, double* d_mapCov, const unsigned char* d_mapFlags, double pixelErrVar,
@@ -931,6 +948,35 @@ typedef struct cs_export_cam {
  * the "<3x3 covariance>" the reference's README.md:152-158 documents. */
 int cs_export_results_v1(const char* dirPath, int nCams, const cs_export_cam* cams, int curFrame, int nPts, const long long* ptId,
                          const double* ptM, const double* ptCov, int covAsReference);
+/* A frame loop's results from its device state, written by cs_export_results_v1 (CoSLAM::exportResults at the end of a run).  Device work
+ * on hip_stream (csrc/export.hip), then a synchronous copy of the finished arrays and the host writer:
+ *   h           the pose history: store + archive (cs_track_history_set_archive); every frame from the history's first frame to its newest
+ *               (curFrame) must still be held -- a run longer than the store needs an archive, or the call fails
+ *   d_featRef   [nMap][nCams] the feature references cs_feat_ref_advance_dev keeps, with h's linked-segment pools
+ *   d_M [nMap][3], d_cov [nMap][9], d_mapFlags [nMap]: the map
+ *   cams        HOST array of nCams: video path, K [9], kc [5], W, H, startFrameInVideo (host memory)
+ *   stats       HOST [3] or NULL: static points written, features written, features whose frame was read from the archive.
+ * Definitions:
+ *   static points   map points that are certain static (none of CS_MAP_FALSE, CS_MAP_DYNAMIC, CS_MAP_UNCERTAIN) and carried by at least
+ *                   one exported feature, in ascending map index; a point's ID IS ITS MAP INDEX (the reference's is the object's address)
+ *   features        feature (camera c, frame f, slot s) carries static point p iff it lies on p's chain in c: the run [first, frame] of
+ *                   d_featRef[p][c] on its slot, then every linked segment's run [first, last] on its own slot, following `next` -- walked
+ *                   without the per-frame walks' histLen bound, into the archive; nodes before the history's first frame are dropped.
+ *                   Within a frame the features are listed in slot order (m_featPts.getFrame), two points on one feature by map index;
+ *                   xy = the history's hand-back pixel of (c, f, s)
+ *   poses           every frame of every camera from the history's first frame, archive then store
+ * Limit: a (camera, frame) row is sorted in LDS, at most 4096 features (at most N slots unless points share features); a larger row fails
+ * the call (CS_ERR_INVALID, cs_last_error names the count) and writes nothing. */
+typedef struct cs_loop_export_cam {
+    const char* videoFilePath;
+    const double* K;   /* 9 */
+    const double* kc;  /* 5 */
+    int W, H;
+    int startFrameInVideo;
+} cs_loop_export_cam;
+int cs_loop_export_results(const char* dirPath, const cs_track_history* h, void* hip_stream, const cs_feat_ref* d_featRef, int nMap,
+                           const double* d_M, const double* d_cov, const unsigned char* d_mapFlags, const cs_loop_export_cam* cams,
+                           int covAsReference, long long* stats);
 
 /* ------------------------------------------------------------------------------------------
  * Inter-camera NCC matching: blocks and the epipolar / NCC matrices of one camera pair

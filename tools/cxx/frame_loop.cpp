@@ -8,7 +8,10 @@
 //                            [first timed frame: 0]
 // Environment (read once, by read_options): RANK / WORLD_SIZE / LOCAL_RANK, COSLAM_FORCE_DEVICE, COSLAM_COMM, COSLAM_COMM_ID_FILE
 // (ranks); COSLAM_KLT_FUSED=0 (the launch-per-pass tracker); COSLAM_FUSED_ROUNDS=0 (the launch-per-step registration);
-// COSLAM_PIXEL_ERR_STD=1; COSLAM_KEYFRAME_DRIVES=1, COSLAM_KEYFRAME_LAG, COSLAM_KEYFRAME_RATIO (the key-frame decision).
+// COSLAM_PIXEL_ERR_STD=1; COSLAM_KEYFRAME_DRIVES=1, COSLAM_KEYFRAME_LAG, COSLAM_KEYFRAME_RATIO (the key-frame decision);
+// COSLAM_EXPORT_DIR (the run's result files, written there after the drain: cs_loop_export_results) with COSLAM_EXPORT_FRAMES (the
+// whole-run archive behind the pose history, in frames: cs_track_history_set_archive); COSLAM_HIST_STORE (frames of pixels + poses the pose
+// history keeps: 4096, as LoopConfig.hist_store).
 // Per frame (reference call sites in bench.py's docstring): camera-group redetect (+ prefetch of the next frame's front) on the
 // tracker stream; hand-back + intraCamEstimate of all cameras + both registration passes on the pose stream, event-ordered
 // behind the tracker; at key frames the inter-camera solve and the joint local BA (parsed on the device from the window ring) on their
@@ -110,6 +113,9 @@ struct Options {
     bool kfDrives;      // COSLAM_KEYFRAME_DRIVES=1 (see KeyFrameDecision)
     int kfLag;
     double kfRatio;
+    const char* exportDir;   // COSLAM_EXPORT_DIR: nullptr = no export
+    int exportFrames;        // COSLAM_EXPORT_FRAMES: the archive's capacity (0: none)
+    int histStore;           // COSLAM_HIST_STORE: frames the pose history keeps (>= the walks' 64)
 };
 
 static Options read_options(int argc, char** argv) {
@@ -137,6 +143,10 @@ static Options read_options(int argc, char** argv) {
     o.kfLag = std::max(1, envi("COSLAM_KEYFRAME_LAG", 1));
     const char* ratio = getenv("COSLAM_KEYFRAME_RATIO");
     o.kfRatio = ratio ? atof(ratio) : 0.93;   // m_mappedPtsReduceRatio
+    const char* ed = getenv("COSLAM_EXPORT_DIR");
+    o.exportDir = ed && ed[0] ? ed : nullptr;
+    o.exportFrames = std::max(0, envi("COSLAM_EXPORT_FRAMES", 0));
+    o.histStore = std::max(64, envi("COSLAM_HIST_STORE", 4096));
     return o;
 }
 
@@ -239,7 +249,7 @@ struct WindowSchedule {
         std::vector<int> frames;   // the window's key frames where the decision put them (empty: firstKey + j * keyEvery)
     };
     // set up by the loop
-    int rank, world, baLag, keyEvery, nCams;
+    int rank, world, baLag, keyEvery, nCams, histStore;
     hipStream_t s;
     cs_ba* ws;
     cs_ba_window* win;
@@ -274,7 +284,7 @@ struct WindowSchedule {
     // for the worker to publish the record; the host goes on enqueueing
     void apply_due(int i, cs_track_history* hist, const cs_poseupdate_cam* pu, int* dPf, int nMap, double* dMap, double* dCov,
                    unsigned char* dMapFlags, double pix, double* R, double* T) {
-        if (!due.empty() && due.front().frame == i && !due.front().frames.empty() && (i - 1) - due.front().frames.front() + 1 > 4096) {
+        if (!due.empty() && due.front().frame == i && !due.front().frames.empty() && (i - 1) - due.front().frames.front() + 1 > histStore) {
             due.erase(due.begin());   // (the camera graphs would start behind the pose history's oldest frame: the record is consumed, nothing written back)
             ++nNotApplied;
         }
@@ -432,6 +442,7 @@ struct FrameLoop {
     void wait_ws(cs_ba* ws);
     void barrier();
     void report(double dt, double dtHost, int applied0, const int rvCnt0[4]);
+    void export_results();
 };
 
 // frames resident in HBM before the clock starts, like bench.py's headline; the trackers of the rank's own cameras as one group
@@ -496,8 +507,9 @@ void FrameLoop::setup_state() {
     dNewPt = dev_zeros<unsigned char>(nMap);
     dSfn = dev_zeros<int>(nMap);
     dFirstFrm = dev_zeros<int>(nMap);
-    // walks 64 frames deep; 4096 frames of pixels + poses kept behind them for the running whole-track mergability verdict
-    hist = made(cs_track_history_create_ex(o.dev, nCams, N, 64, 4096), "cs_track_history_create_ex");
+    // walks 64 frames deep; 4096 frames (COSLAM_HIST_STORE) of pixels + poses kept behind them for the running whole-track mergability verdict
+    hist = made(cs_track_history_create_ex(o.dev, nCams, N, 64, o.histStore), "cs_track_history_create_ex");
+    if (o.exportFrames > 0) CSCHK(cs_track_history_set_archive(hist, o.exportFrames));   // every frame that leaves the store kept, for the export
 }
 
 // N > 1: rank r owns cameras r * nc .. r * nc + nc - 1: their images, trackers, hand-backs and pose solves; everything behind the per-frame
@@ -600,7 +612,7 @@ void FrameLoop::setup_keyframe_solves() {
     CSCHK(cs_track_history_set_classify_refs(hist, dFref, dRstat));   // mapPointsClassify over the references
     CSCHK(cs_track_history_set_merge_refs(hist, dFref, dRstat));      // ... and the bMerge walks
     WindowSchedule& s = sched;
-    s.rank = o.rank, s.world = o.world, s.baLag = o.baLag, s.keyEvery = keyEvery, s.nCams = nCams, s.s = poseS;
+    s.rank = o.rank, s.world = o.world, s.baLag = o.baLag, s.keyEvery = keyEvery, s.nCams = nCams, s.histStore = o.histStore, s.s = poseS;
     s.ws = jointWs, s.win = win, s.bout = bout, s.comm = comm, s.recordBytes = cs_ba_output_record_bytes(bout);
 }
 
@@ -1087,6 +1099,26 @@ void FrameLoop::report(double dt, double dtHost, int applied0, const int rvCnt0[
     fflush(stdout);
 }
 
+// CoSLAM::exportResults behind the loop (reference src/gui/CoSLAMThread.cpp): the six result files into COSLAM_EXPORT_DIR from the device
+// state, after the drain; every rank holds the same map and history, rank 0 writes.  A failure ends the process with status 3.
+void FrameLoop::export_results() {
+    if (o.rank != 0) return;
+    const double kc[5] = {0, 0, 0, 0, 0};
+    std::vector<std::string> paths(nCams);
+    std::vector<cs_loop_export_cam> cams(nCams);
+    for (int c = 0; c < nCams; ++c) {
+        paths[c] = "camera_" + std::to_string(c);
+        cams[c] = cs_loop_export_cam{paths[c].c_str(), w.K.data(), kc, W, H, 0};
+    }
+    long long stats[3] = {0, 0, 0};
+    const auto t0 = std::chrono::steady_clock::now();
+    CSCHK(cs_loop_export_results(o.exportDir, hist, (void*)poseS, dFref, nMap, dMap, dCov, dMapFlags, cams.data(), 1, stats));
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    fprintf(stderr, "[frame_loop] exported frames %d..%d (%d archived), %lld static points, %lld features (%lld from the archive) to %s in %.3f s\n",
+            cs_track_history_first_frame(hist), cs_track_history_newest_frame(hist), cs_track_history_archive_frames(hist), stats[0], stats[1],
+            stats[2], o.exportDir, dt);
+}
+
 int main(int argc, char** argv) {
     const Options opt = read_options(argc, argv);
     Reader rd{nullptr};
@@ -1134,6 +1166,7 @@ int main(int argc, char** argv) {
     loop.barrier();
     const auto t2 = std::chrono::steady_clock::now();
     loop.report(std::chrono::duration<double>(t2 - t0).count(), std::chrono::duration<double>(t1 - t0).count(), applied0, rvCnt0);
+    if (opt.exportDir) loop.export_results();
 
     if (loop.xchg) cs_exchange_destroy(loop.xchg);
     if (loop.comm) cs_comm_destroy(loop.comm);
