@@ -41,6 +41,7 @@
 
 #include "cs_common.h"
 #include "history_view.h"
+#include "register_rows_dev.h"
 #include "small_ops.h"
 
 #pragma clang fp contract(off)
@@ -349,7 +350,7 @@ __global__ __launch_bounds__(256) void k_pose_update(PuArgs A) {
 // stops at the first failure.  The reference runs it per candidate inside the registration loops on the host, following
 // pointers; here a group of lanes = one (map point, camera) candidate, blockIdx.y = camera, the camera's ring of poses in LDS,
 // the track's past pixels from the history ring (one 16-byte gather per step).
-struct MgArgs {
+struct MgCore {
     int cam0;  // cameras cam0 .. cam0 + gridDim.y - 1
     int nCams, N, P, H, head, nHist;
     double sigma;
@@ -360,6 +361,8 @@ struct MgArgs {
     const double* histXY;
     const double* histR;
     const double* histT;
+};
+struct MgArgs : MgCore {
     cs_poseupdate_cam cam[PU_MAX_CAMS];
 };
 // MG_LPC lanes per candidate: lane r of the group takes the frames j = r, r + MG_LPC, ... of the walk (the verdict is the AND over
@@ -461,8 +464,8 @@ struct MgCache {   // 48 bytes, zero = empty
     int pad;
 };
 static_assert(sizeof(MgCache) == 48, "cs_register_mergability_cache_bytes");
-struct MgRunArgs {
-    MgArgs a;
+struct MgRunCore {
+    MgCore a;
     int W, count, curFrame;  // window depth, frames the ring holds, frame number of the ring's head
     double tolPix;
     MgCache* cache;          // [P][nCams]
@@ -477,6 +480,9 @@ struct MgRunArgs {
     const int* flags;        // null, or the search's flags [P][nCams]: a candidate that already CARRIES a map point (bit 0 clear) is not
                              // judged (verdict 0): the registration walks end at it (:789-790) or ask checkUnify, never this test
 };
+struct MgRunArgs : MgRunCore {
+    cs_poseupdate_cam cam[PU_MAX_CAMS];
+};
 constexpr int MG_GAP_MAX = 2 * MG_LPC;   // a cached tail this many frames behind is caught up by the candidate's own 8 lanes; further: a wave
 struct MgMiss {   // a tail that a whole WAVE walks (phase B)
     int p, s, start, end;
@@ -486,20 +492,21 @@ struct MgMiss {   // a tail that a whole WAVE walks (phase B)
 // longer -- no entry, another slot, another track, a point that moved, a cache that fell behind -- goes on the block's list.
 // Phase B, a WAVE per listed tail: 64 lanes stride over its frames (a 900-frame tail is 15 steps deep instead of 113), any failure
 // ends it.  The verdict and the cache entry are written by whoever finished the candidate.
-__global__ __launch_bounds__(256) void k_register_mergability_running(MgRunArgs B) {
-    extern __shared__ double mg_pose[];  // [W][12]
-    __shared__ MgMiss missList[256 / MG_LPC];
-    __shared__ int nMiss;
-    CS_POSE_STREAM_PRIO();
-    const MgArgs& A = B.a;
-    const int c = A.cam0 + blockIdx.y, tid = threadIdx.x, N = A.N, H = A.H, W = B.W;
+// The body is one block of NT threads (NT / MG_LPC rows of camera c, from row bx * NT / MG_LPC): k_register_mergability_running runs it
+// with NT = 256 as workgroup (blockIdx.x, cam0 + blockIdx.y), k_revisit_rounds with its whole workgroup over the short list's blocks one
+// after the other.  A candidate's verdict and cache entry are its own group's or wave's work whatever NT is.
+template <int NT>
+__device__ __forceinline__ void mg_running_rows(const MgRunCore& B, const cs_poseupdate_cam* cams, const int* list, int nList, int c, int bx,
+                                                double* mg_pose, MgMiss* missList, int& nMiss) {
+    const MgCore& A = B.a;
+    const int tid = threadIdx.x, N = A.N, H = A.H, W = B.W;
     // (a compact list is padded with -1: a workgroup whose first row lies behind the list's end has nothing to do -- before it stages a pose)
-    if (B.list && (int)(blockIdx.x * (256 / MG_LPC)) < B.nList && B.list[blockIdx.x * (256 / MG_LPC)] < 0) return;
-    const cs_poseupdate_cam& C = A.cam[c];
+    if (list && (int)(bx * (NT / MG_LPC)) < nList && list[bx * (NT / MG_LPC)] < 0) return;
+    const cs_poseupdate_cam& C = cams[c];
     const double* hR = A.histR + (size_t)c * H * 9;
     const double* hT = A.histT + (size_t)c * H * 3;
     const double* hXY = A.histXY + (size_t)c * H * 2 * N;
-    for (int q = tid; q < W * 12; q += 256) {
+    for (int q = tid; q < W * 12; q += NT) {
         const int j = q / 12, e = q - 12 * j, rs = (A.head - j + H) % H;
         mg_pose[q] = e < 9 ? hR[(size_t)rs * 9 + e] : hT[(size_t)rs * 3 + (e - 9)];
     }
@@ -507,8 +514,8 @@ __global__ __launch_bounds__(256) void k_register_mergability_running(MgRunArgs 
     __syncthreads();
     const int lane = tid & 63, r = lane % MG_LPC, g = lane / MG_LPC;
     const unsigned long long gmask = ((1ull << MG_LPC) - 1ull) << (MG_LPC * g);
-    const int jj = (blockIdx.x * 256 + tid) / MG_LPC;
-    const int p = B.list ? (jj < B.nList ? B.list[jj] : -1) : (jj < A.P ? jj : -1);
+    const int jj = (bx * NT + tid) / MG_LPC;
+    const int p = list ? (jj < nList ? list[jj] : -1) : (jj < A.P ? jj : -1);
     const bool live = p >= 0 && p < A.P;
     int s = live ? A.slot[(size_t)p * A.nCams + c] : -1;
     bool skipped = false;
@@ -598,7 +605,7 @@ __global__ __launch_bounds__(256) void k_register_mergability_running(MgRunArgs 
     __syncthreads();
     // ---- phase B: a wave per listed tail
     const int wv = tid >> 6, nM = nMiss;
-    for (int k = wv; k < nM; k += 4) {
+    for (int k = wv; k < nM; k += NT / 64) {
         const MgMiss m = missList[k];
         double M[3], cov[9];
 #pragma unroll
@@ -646,6 +653,13 @@ __global__ __launch_bounds__(256) void k_register_mergability_running(MgRunArgs 
             if (terms) atomicAdd(B.counts + 3, terms);
         }
     }
+}
+__global__ __launch_bounds__(256) void k_register_mergability_running(MgRunArgs B) {
+    extern __shared__ double mg_pose[];  // [W][12]
+    __shared__ MgMiss missList[256 / MG_LPC];
+    __shared__ int nMiss;
+    CS_POSE_STREAM_PRIO();
+    mg_running_rows<256>(B, B.cam, B.list, B.nList, B.a.cam0 + blockIdx.y, blockIdx.x, mg_pose, missList, nMiss);
 }
 
 
@@ -2275,7 +2289,7 @@ extern "C" int cs_register_mergability_running_list_dev(const cs_track_history* 
     MgRunArgs B;
     memset(&B, 0, sizeof(B));
     B.list = d_list, B.nList = nList, B.flags = d_flags;
-    MgArgs& A = B.a;
+    MgCore& A = B.a;
     A.cam0 = cam0;
     A.nCams = h->nCams, A.N = h->N, A.P = P, A.H = h->H, A.head = h->head, A.nHist = hist_walk(h);
     A.sigma = pixelErrVar;
@@ -2286,7 +2300,7 @@ extern "C" int cs_register_mergability_running_list_dev(const cs_track_history* 
             cs_set_error("cs_register_mergability_running_dev: null pointer in camera %d", c);
             return CS_ERR_INVALID;
         }
-        A.cam[c] = cams[c];
+        B.cam[c] = cams[c];
     }
     B.W = hist_walk(h), B.count = h->count, B.curFrame = h->lastFrame;
     B.epoch = h->tailEpoch, B.fromMin = h->tailFromMin;
@@ -2872,6 +2886,17 @@ struct ArArgs : UpArgs {
     int blocksA, clearSelect;
     unsigned char* selectW;   // = select (written when clearSelect: the mark is consumed)
 };
+// a refined row, by its own wave (lane r): advanced entry by entry, then re-triangulated from the references it has just written
+__device__ __forceinline__ void ar_refine_row(const ArArgs& A, int m, int r, int (&cnt)[5]) {
+    const bool al = r < A.nCams && fr_advance_entry(A.F, A.cam, m, r, cnt);
+    const bool anyAlive = __builtin_amdgcn_ballot_w64(al) != 0ull;
+    if (r == 0) A.F.alive[m] = anyAlive ? 1 : 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    up_point(A, m, r);
+    if (A.clearSelect && r == 0) A.selectW[m] = 0;
+}
 __global__ __launch_bounds__(256) void k_advance_refine(ArArgs A) {
     int cnt[5] = {0, 0, 0, 0, 0};
     if ((int)blockIdx.x < A.blocksA) {
@@ -2881,16 +2906,7 @@ __global__ __launch_bounds__(256) void k_advance_refine(ArArgs A) {
     } else {
         const int j = ((int)blockIdx.x - A.blocksA) * 4 + (int)threadIdx.x / 64, r = threadIdx.x % 64;
         const int m = j < A.nList ? A.list[j] : -1;
-        if (m >= 0 && m < A.nMap && A.select[m]) {   // (uniform over the wave)
-            const bool al = r < A.nCams && fr_advance_entry(A.F, A.cam, m, r, cnt);
-            const bool anyAlive = __builtin_amdgcn_ballot_w64(al) != 0ull;
-            if (r == 0) A.F.alive[m] = anyAlive ? 1 : 0;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            up_point(A, m, r);
-            if (A.clearSelect && r == 0) A.selectW[m] = 0;
-        }
+        if (m >= 0 && m < A.nMap && A.select[m]) ar_refine_row(A, m, r, cnt);   // (uniform over the wave)
     }
     if (A.F.counts) {
         __shared__ int sCnt[4][5];
@@ -2954,6 +2970,217 @@ extern "C" int cs_feat_ref_advance_refine_dev(cs_track_history* h, void* hip_str
     hist_centres(h, s);
     A.blocksA = ((advanceAll ? nMap : nList) + 255) / 256;
     hipLaunchKernelGGL(k_advance_refine, dim3(A.blocksA + (nList + 3) / 4), dim3(256), 0, s, A);
+    CS_HIP(hipGetLastError());
+    return CS_OK;
+}
+
+// ---- ALL rounds of the second visits of a frame in ONE launch (register.hip, the rounds' account) ------------------------------------------
+// Round r is search + whole-track mergability + the walks + advance / refine over the points of list r (cs_register_search_passes_range_dev,
+// cs_register_mergability_running_list_dev, cs_register_revisit_decide_next_dev, cs_feat_ref_advance_refine_dev: four launches over a list
+// sized for its capacity).  Here one workgroup plays them phase after phase, its barriers between them, with the same per-row code
+// (register_rows_dev.h, mg_running_rows, fr_advance_row, ar_refine_row), and leaves at once when round 0's list is empty -- the usual
+// frame.  Round r reads the count round r - 1 wrote (round 0's: the decide launch's).  The search is a wave per (point, camera) pair: its answer
+// is the lexicographic minimum on (distance, slot), however the feature list is split; the walks' sweeps reach the same fixed point; the
+// mergability blocks are NT rows' worth instead of 256: every verdict is its own candidate's.  No grid barrier: nothing here can time out.
+// 1024 threads = the walks' rows: a thread per row of a list of up to RV_MAX_ROWS.  This does NOT fit beside the tracker's workgroups (they
+// leave 192 VGPRs per SIMD lane; 16 waves of 128 VGPRs need 512), no more than k_revisit_decide did: the launch starts on a compute unit
+// without tracker waves.  256 threads with several rows a thread in the walks were tried: the phases need 248-256 VGPRs a wave, which does
+// not fit either.
+constexpr int RR_THREADS = 1024;
+static_assert(RR_THREADS >= RV_MAX_ROWS, "k_revisit_rounds: a thread per listed row of the walks");
+struct RrArgs {
+    int nRounds, W, H;
+    int* lists;                         // [nRounds][rv.cap]
+    int* rvCounts;                      // [nRounds + 1]: listed per round (round 0's from the decide launch), then the points beyond the lists
+    cs_register_pass pass;              // the search's tables and scales (P / list unused)
+    cs_register_cam rcam[RG_MAX_CAMS];
+    MgRunCore mg;                       // list / nList unused
+    RvArgs rv;                          // list / listCount / nextList / nextCount unused
+    ArArgs ar;                          // list / nList unused; its cameras serve the mergability too
+};
+static_assert(sizeof(RrArgs) <= 4096, "k_revisit_rounds: the arguments must fit the kernel-argument segment");
+template <int MC>
+__global__ __launch_bounds__(RR_THREADS) void k_revisit_rounds(RrArgs A) {
+    extern __shared__ double rr_pose[];   // the mergability's poses [W][12]
+    __shared__ MgMiss missList[RR_THREADS / MG_LPC];
+    __shared__ int nMiss;
+    __shared__ int sCnt[RR_THREADS / 64][5];
+    if (rd_ld(A.rvCounts) == 0) return;   // (uniform, before any barrier: nobody registered in the single pass has a later loop)
+    CS_POSE_STREAM_PRIO();
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, C = A.rv.nCams, cap = A.rv.cap, N = A.rv.N;
+    const cs_register_pass& Q = A.pass;
+    int cnt[5] = {0, 0, 0, 0, 0};   // the feature references' counters (tracked on, first, re-linked, links dropped, detached)
+    for (int r = 0; r < A.nRounds; ++r) {
+        const int listed = rd_ld(A.rvCounts + r);   // (atomics of the previous round's walks: read at agent scope, past any cached line)
+        if (listed == 0) break;
+        const int n = listed < cap ? listed : cap;
+        const int* list = A.lists + (size_t)r * cap;
+        // ---- search: a wave per (point, camera) pair
+        for (int k = wave; k < n * C; k += RR_THREADS / 64) {
+            const int row = k / C, c = k - row * C, p = list[row];
+            if (p < 0) continue;
+            const cs_register_cam& Cm = A.rcam[c];
+            const size_t o = (size_t)p * C + c;
+            int outSlot = -1, outFlags = 0;
+            double m0 = 0, m1 = 0, var[4] = {0, 0, 0, 0}, ivar[4] = {0, 0, 0, 0}, outDist = 0;
+            Proj q;
+            if (rg_pair_begin(Q, Cm, o, p, A.W, A.H, q, m0, m1, var, ivar, outSlot)) {
+                double dMin;
+                int iMin;
+                rg_pair_scan_wave(Cm, N, lane, m0, m1, ivar, dMin, iMin);
+                rg_pair_finish(Q, Cm, p, N, q, m0, m1, dMin, iMin, outSlot, outFlags, outDist);
+            }
+            if (lane == 0) rg_pair_store(Q, o, outSlot, outFlags, outDist, m0, m1, var);
+        }
+        __syncthreads();
+        // ---- whole-track mergability: camera by camera, RR_THREADS / MG_LPC rows a block
+        const int nB = (n * MG_LPC + RR_THREADS - 1) / RR_THREADS;
+        for (int c = 0; c < C; ++c)
+            for (int bx = 0; bx < nB; ++bx) {
+                mg_running_rows<RR_THREADS>(A.mg, A.ar.cam, list, cap, c, bx, rr_pose, missList, nMiss);
+                __syncthreads();
+            }
+        // ---- the walks, the attach, the next round's list
+        {
+            RvArgs R = A.rv;
+            const bool more = r + 1 < A.nRounds;
+            R.list = list, R.listCount = A.rvCounts + r;
+            R.nextList = more ? A.lists + (size_t)(r + 1) * cap : nullptr, R.nextCount = more ? A.rvCounts + r + 1 : nullptr;
+            rv_decide_rows<MC>(R);
+        }
+        __syncthreads();
+        // ---- advance the listed rows' references; the rows that registered again are refined (a wave each) and their marks cleared
+        for (int j = tid; j < n; j += RR_THREADS) {
+            const int m = list[j];
+            if (m >= 0 && m < A.ar.nMap && !A.ar.select[m]) fr_advance_row(A.ar.F, A.ar.cam, m, cnt);
+        }
+        __syncthreads();   // (the refine below clears the marks the advance above reads)
+        for (int j = wave; j < n; j += RR_THREADS / 64) {
+            const int m = list[j];
+            if (m >= 0 && m < A.ar.nMap && A.ar.select[m]) ar_refine_row(A.ar, m, lane, cnt);   // (uniform over the wave)
+        }
+        __syncthreads();
+    }
+    if (A.ar.F.counts) {   // one atomic per counter (k_advance_refine: one per workgroup and round; the sums are the same)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            int v = cnt[k];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) sCnt[wave][k] = v;
+        }
+        __syncthreads();
+        if (tid < 5) {
+            int v = 0;
+            for (int w = 0; w < RR_THREADS / 64; ++w) v += sCnt[w][tid];
+            if (v) atomicAdd(A.ar.F.counts + tid, v);
+        }
+    }
+}
+
+extern "C" int cs_register_revisit_rounds_dev(cs_track_history* h, void* hip_stream, const cs_register_cam* regCams, const cs_poseupdate_cam* cams,
+                                              int W, int H, const cs_register_pass* pass, int nMap, int curFrame, int mapBase, int kinds,
+                                              double* d_mapPts, double* d_mapCov, double pixelErrVar, double tolPix, void* d_mergeCache,
+                                              unsigned char* d_mergeable, int* d_rvLists, int* d_rvCounts, int cap, int nRounds, int* d_visitLoop,
+                                              int* d_nextLoop, const unsigned char* d_mapFlags, int* d_pointFeat, int* const* d_slot2map,
+                                              unsigned char* d_attached, unsigned char* d_regOut, void* d_decideScratch, const int* d_curList,
+                                              const int* d_curCount, int curCap, int* d_rvCnt, cs_feat_ref* d_featRef, unsigned char* d_refStatic,
+                                              int* d_frefCounts) {
+    // the checks of the four calls it replaces (cs_register_search_passes_range_dev, cs_register_mergability_running_list_dev,
+    // cs_register_revisit_decide_next_dev, cs_feat_ref_advance_refine_dev) and of the rounds' lists (cs_register_decide_kinds_rounds_dev)
+    if (!h || !regCams || !cams || !pass) {
+        cs_set_error("cs_register_revisit_rounds_dev: bad arguments (null history, cameras or pass)");
+        return CS_ERR_INVALID;
+    }
+    const int nCams = h->nCams, N = h->N;
+    const cs_register_pass& q = *pass;
+    if (nCams < 1 || nCams > RG_MAX_CAMS || nCams > RD_MAX_CAMS || N < 1 || W < 1 || H < 1 || !(q.maxDist > 0) || !(q.sigmaSearch >= 0) ||
+        !(q.sigmaMerge >= 0) || (q.mapFlags && !(q.maxDistDynamic > 0))) {
+        cs_set_error("cs_register_revisit_rounds_dev: bad arguments (1..%d cameras, N >= 1, maxDist > 0; mapFlags with maxDistDynamic > 0)", RD_MAX_CAMS);
+        return CS_ERR_INVALID;
+    }
+    if (!q.M || !q.cov || !q.pointFeat || !q.slot || !q.m || !q.var || !q.dist || !q.flags || q.M != d_mapPts || q.cov != d_mapCov ||
+        q.pointFeat != d_pointFeat) {
+        cs_set_error("cs_register_revisit_rounds_dev: the pass needs every table, and its map, covariances and feature table are the ones refined");
+        return CS_ERR_INVALID;
+    }
+    if (nMap < 1 || cap < 1 || cap > RV_MAX_ROWS || nRounds < 1 || nRounds > 8 || kinds < 1 || kinds > 3 || mapBase < 0 || !(tolPix >= 0) ||
+        !d_mapPts || !d_mapCov || !d_mergeCache || !d_mergeable || !d_rvLists || !d_rvCounts || !d_visitLoop || !d_nextLoop || !d_mapFlags ||
+        !d_pointFeat || !d_slot2map || !d_attached || !d_regOut || !d_decideScratch || !d_curList || !d_curCount || !d_featRef ||
+        (long long)nCams * N > RD_FEAT || (long long)nCams * nMap * nCams > 0x7fffffffLL) {
+        cs_set_error("cs_register_revisit_rounds_dev: bad arguments (1..%d rows, 1..8 rounds, kinds 1..3, every table)", RV_MAX_ROWS);
+        return CS_ERR_INVALID;
+    }
+    if (h->count < 1 || curFrame != h->lastFrame) {
+        cs_set_error("cs_register_revisit_rounds_dev: the history's newest entry must be frame %d (it holds %d frame(s), the newest %d)", curFrame,
+                     h->count, h->lastFrame);
+        return CS_ERR_INVALID;
+    }
+    RrArgs A;
+    memset((void*)&A, 0, sizeof(A));
+    for (int c = 0; c < nCams; ++c) {
+        const cs_register_cam& rc = regCams[c];
+        if (!rc.K || !rc.R || !rc.t || !rc.xy || !rc.state || !rc.slot2map) {
+            cs_set_error("cs_register_revisit_rounds_dev: null pointer in search camera %d", c);
+            return CS_ERR_INVALID;
+        }
+        if (!cams[c].K || !cams[c].iK || !cams[c].trackSpan) {
+            cs_set_error("cs_register_revisit_rounds_dev: null pointer in camera %d (K, iK, trackSpan are read)", c);
+            return CS_ERR_INVALID;
+        }
+        if (!d_slot2map[c]) {
+            cs_set_error("cs_register_revisit_rounds_dev: null slot2map of camera %d", c);
+            return CS_ERR_INVALID;
+        }
+        A.rcam[c] = rc;
+    }
+    A.nRounds = nRounds, A.W = W, A.H = H, A.lists = d_rvLists, A.rvCounts = d_rvCounts;
+    A.pass = q;
+    A.pass.P = cap, A.pass.list = nullptr;
+    // the mergability (cs_register_mergability_running_list_dev's set-up: no counters)
+    MgCore& G = A.mg.a;
+    G.cam0 = 0, G.nCams = nCams, G.N = N, G.P = nMap, G.H = h->H, G.head = h->head, G.nHist = hist_walk(h);
+    G.sigma = pixelErrVar, G.M = d_mapPts, G.cov = d_mapCov, G.slot = q.slot, G.out = d_mergeable;
+    G.histXY = h->xy, G.histR = h->R, G.histT = h->t;
+    A.mg.W = hist_walk(h), A.mg.count = h->count, A.mg.curFrame = h->lastFrame, A.mg.epoch = h->tailEpoch, A.mg.fromMin = h->tailFromMin;
+    A.mg.tolPix = tolPix, A.mg.cache = (MgCache*)d_mergeCache, A.mg.counts = nullptr, A.mg.flags = q.flags;
+    // the walks (cs_register_revisit_decide_next_dev's)
+    RvArgs& V = A.rv;
+    V.nCams = nCams, V.N = N, V.P = nMap, V.cap = cap, V.mapBase = mapBase, V.kinds = kinds, V.nextLoop = d_nextLoop, V.visitLoop = d_visitLoop;
+    V.slot = q.slot, V.flags = q.flags, V.mergeable = d_mergeable, V.mapFlags = d_mapFlags, V.pointFeat = d_pointFeat;
+    for (int c = 0; c < nCams; ++c) V.slot2map[c] = d_slot2map[c];
+    V.attached = d_attached, V.regOut = d_regOut, V.curList = d_curList, V.curCount = d_curCount, V.curCap = curCap, V.counts = d_rvCnt;
+    V.nextLoopW = d_nextLoop, V.overflow = d_rvCounts + nRounds;
+    V.debug = cs_debug_get(CS_DBG_MERGE_PRINT) == 1;
+    int* scr = (int*)d_decideScratch + (size_t)nCams * nMap + nMap;   // (cs_register_decide_kinds_dev's carve-up: code | base | owner x 3 | ...)
+    for (int k = 0; k < 3; ++k) V.owner[k] = scr, scr += (size_t)nCams * N;
+    // advance + refine (cs_feat_ref_advance_refine_dev's, over a list, the marks consumed)
+    ArArgs& R = A.ar;
+    R.nMap = nMap, R.featRef = (const int4*)d_featRef, R.mapPts = d_mapPts, R.mapCov = d_mapCov, R.sigma = pixelErrVar;
+    R.refine = 1, R.select = d_regOut, R.selectW = d_regOut, R.clearSelect = 1;
+    R.segPool = h->segPool, R.segCap = h->segCap, R.curFrame = h->lastFrame, R.stored = h->count < h->H ? h->count : h->H;
+    R.nCams = nCams, R.N = N, R.H = h->H, R.head = h->head, R.nHist = hist_walk(h);
+    R.histXY = h->xy, R.histR = h->R, R.histT = h->t, R.cen = h->cen;
+    R.F.nCams = nCams, R.F.N = N, R.F.nMap = nMap, R.F.curFrame = curFrame, R.F.segCap = h->segCap;
+    R.F.pointFeat = d_pointFeat, R.F.featRef = (int4*)d_featRef, R.F.refStatic = d_refStatic, R.F.segPool = h->segPool, R.F.segCount = h->segCount;
+    R.F.counts = d_frefCounts;
+    for (int c = 0; c < nCams; ++c) R.cam[c] = cams[c];
+    CS_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (nMap > h->aliveCap) {
+        if (h->alive) CS_HIP(hipFree(h->alive));
+        h->alive = nullptr, h->aliveCap = 0;
+        CS_HIP(hipMalloc((void**)&h->alive, (size_t)nMap));
+        CS_HIP(hipMemsetAsync(h->alive, 1, (size_t)nMap, s));
+        h->aliveCap = nMap;
+    }
+    R.F.alive = h->alive;
+    hist_centres(h, s);
+    const size_t lds = sizeof(double) * 12 * (size_t)A.mg.W;
+    if (nCams <= 8)
+        hipLaunchKernelGGL(k_revisit_rounds<8>, dim3(1), dim3(RR_THREADS), lds, s, A);
+    else
+        hipLaunchKernelGGL(k_revisit_rounds<RD_MAX_CAMS>, dim3(1), dim3(RR_THREADS), lds, s, A);
     CS_HIP(hipGetLastError());
     return CS_OK;
 }

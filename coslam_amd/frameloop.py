@@ -47,7 +47,7 @@ from coslam_amd.pose import intraCamEstimate_batch_dev
 from coslam_amd.poseupdate import TrackHistory, poseupdate_cams
 from coslam_amd.register import (register_cams, register_cur_static_sequential_dev, register_decide_kinds_rounds_dev,
                                  register_decide_scratch_bytes, register_decide_static_dev, register_list_current_dev, register_passes,
-                                 register_revisit_decide_dev, register_revisit_decide_next_dev, register_revisit_list_dev,
+                                 register_revisit_decide_dev, register_revisit_list_dev, register_revisit_rounds_dev,
                                  register_search_passes_dev)
 from coslam_amd.results import loop_export_results
 from coslam_amd.synth import csr_of_problem
@@ -936,8 +936,8 @@ class FrameLoop:
             self._revisit_rounds(i, dst, D)
 
     def _decide_fused(self, i, dst, D):
-        """the single pass, its refine and the second visits' rounds with the launches fused (tools/cxx/frame_loop.cpp's sequence): 2 + 4 per
-        round instead of 3 + 6; the same map, tables and poses"""
+        """the single pass, its refine and the second visits' rounds with the launches fused (tools/cxx/frame_loop.cpp's sequence): 2 + 1
+        launches instead of 3 + 6 per round; the same map, tables and poses"""
         cfg, NA, R, ps, o = self.cfg, self.cfg.n_cams, self.cfg.revisit_rounds, self.pose_s.cuda_stream, self.reg_out
         D["s2m"] = register_decide_kinds_rounds_dev(ps, NA, cfg.n_feat, self.n_map, 0, o["slot"].data_ptr(), o["flags"].data_ptr(), self.d_mergeable.data_ptr(),
                                                     self.d_mapflags.data_ptr(), self.d_pf.data_ptr(), D["s2m"], D["att"].data_ptr(), D["reg"].data_ptr(),
@@ -947,20 +947,14 @@ class FrameLoop:
             ps, self.pu_args, self.n_map, self.d_pf.data_ptr(), i, self.d_fref.data_ptr(), self.d_rstat.data_ptr(), lst, n, all_, sel, clr,
             self.d_map.data_ptr(), self.d_cov.data_ptr(), self.sig_pix, d_counts=self.d_fref_counts.data_ptr())
         adv(self.d_curlist.data_ptr(), cfg.p_reg, True, D["reg"].data_ptr(), False)
-        for r in range(R):
-            lst = self.d_rvlists[r].data_ptr()
-            register_search_passes_dev(ps, self.reg_args[dst], cfg.n_feat, cfg.W, cfg.H, self.rv_passes[r], device=self.device)
-            self.pose_upd.register_mergability_running_dev(ps, self.pu_args, self.n_map, self.d_map.data_ptr(), self.d_cov.data_ptr(), o["slot"].data_ptr(),
-                                                           self.sig_pix, self.d_merge_cache.data_ptr(), self.d_mergeable.data_ptr(), tolPix=0.0, d_counts=0,
-                                                           cam0=0, nCamsRun=NA, d_list=lst, nList=self.RV_CAP, d_flags=o["flags"].data_ptr())
-            more = r + 1 < R
-            register_revisit_decide_next_dev(ps, NA, cfg.n_feat, self.n_map, self.RV_CAP, 0, 3, lst, self.d_rv_next.data_ptr(), self.d_rv_visit.data_ptr(),
-                                             o["slot"].data_ptr(), o["flags"].data_ptr(), self.d_mergeable.data_ptr(), self.d_mapflags.data_ptr(),
-                                             self.d_pf.data_ptr(), D["s2m"], D["att"].data_ptr(), self.d_rv_reg[0].data_ptr(), D["scr"].data_ptr(),
-                                             self.d_curlist.data_ptr(), self.d_curcount.data_ptr(), cfg.p_reg, self.d_rv_counts.data_ptr(), device=self.device,
-                                             d_listCount=self.d_rvcounts[r:].data_ptr(), d_nextList=self.d_rvlists[r + 1].data_ptr() if more else 0,
-                                             d_nextCount=self.d_rvcounts[r + 1:].data_ptr() if more else 0, d_overflow=self.d_rvcounts[R:].data_ptr())
-            adv(lst, self.RV_CAP, False, self.d_rv_reg[0].data_ptr(), True)
+        if R > 0:   # every round in ONE launch, which leaves at once when list 0 is empty (cs_register_revisit_rounds_dev)
+            register_revisit_rounds_dev(ps, self.pose_upd, self.reg_args[dst], self.pu_args, cfg.W, cfg.H, self.rv_passes[0], self.n_map, i, 0, 3,
+                                        self.d_map.data_ptr(), self.d_cov.data_ptr(), self.sig_pix, 0.0, self.d_merge_cache.data_ptr(),
+                                        self.d_mergeable.data_ptr(), self.d_rvlists.data_ptr(), self.d_rvcounts.data_ptr(), self.RV_CAP, R,
+                                        self.d_rv_visit.data_ptr(), self.d_rv_next.data_ptr(), self.d_mapflags.data_ptr(), self.d_pf.data_ptr(), D["s2m"],
+                                        D["att"].data_ptr(), self.d_rv_reg[0].data_ptr(), D["scr"].data_ptr(), self.d_curlist.data_ptr(),
+                                        self.d_curcount.data_ptr(), cfg.p_reg, self.d_rv_counts.data_ptr(), self.d_fref.data_ptr(),
+                                        d_refStatic=self.d_rstat.data_ptr(), d_frefCounts=self.d_fref_counts.data_ptr())
 
     def _revisit_rounds(self, i, dst, D):
         """The reference's SECOND VISITS (src/app/SL_CoSLAM.cpp:864-869, :889-893) behind the single pass and its refine: the points that

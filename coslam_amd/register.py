@@ -229,3 +229,28 @@ def register_cur_static_sequential_dev(stream_ptr, history, pu_cams, reg_cams, N
         if after_loop is not None:
             after_loop(o + (nC if kind == 2 else 0))
     return arr
+
+
+def register_revisit_rounds_dev(stream_ptr, history, reg_cams, pu_cams, W, H, search_pass, nMap, curFrame, mapBase, kinds, d_mapPts, d_mapCov,
+                                pixelErrVar, tolPix, d_mergeCache, d_mergeable, d_rvLists, d_rvCounts, cap, nRounds, d_visitLoop, d_nextLoop,
+                                d_mapFlags, d_pointFeat, d_slot2map, d_attached, d_regOut, d_decideScratch, d_curList, d_curCount, curCap, d_rvCnt,
+                                d_featRef, d_refStatic=0, d_frefCounts=0):
+    """cs_register_revisit_rounds_dev: ALL rounds of the second visits of a frame in ONE launch -- per round the search over list r
+    (search_pass: a cs_register_pass, its P and list ignored), the whole-track mergability, the walks with the next round's list and advance +
+    refine of the listed rows; an empty list ends it (at once when round 0's is).  history: a TrackHistory (coslam_amd.poseupdate)."""
+    from .poseupdate import poseupdate_cams
+
+    vp = C.c_void_p
+    nC = len(reg_cams)
+    arr = d_slot2map if isinstance(d_slot2map, C.Array) else (C.c_void_p * nC)(*[int(x) for x in d_slot2map])
+    sp = search_pass[0] if isinstance(search_pass, C.Array) else search_pass
+    f = lib().cs_register_revisit_rounds_dev
+    f.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, C.c_int,
+                  C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    check(f(vp(history._h), vp(stream_ptr), C.cast(register_cams(reg_cams), vp), C.cast(poseupdate_cams(pu_cams), vp), int(W), int(H),
+            C.cast(C.pointer(sp), vp), int(nMap), int(curFrame), int(mapBase), int(kinds), vp(d_mapPts), vp(d_mapCov), float(pixelErrVar),
+            float(tolPix), vp(d_mergeCache), vp(d_mergeable), vp(d_rvLists), vp(d_rvCounts), int(cap), int(nRounds), vp(d_visitLoop),
+            vp(d_nextLoop), vp(d_mapFlags), vp(d_pointFeat), C.cast(arr, vp), vp(d_attached), vp(d_regOut), vp(d_decideScratch), vp(d_curList),
+            vp(d_curCount), int(curCap), vp(d_rvCnt), vp(d_featRef), vp(d_refStatic), vp(d_frefCounts)),
+          "cs_register_revisit_rounds_dev")
+    return arr

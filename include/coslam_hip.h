@@ -757,6 +757,21 @@ int cs_feat_ref_advance_refine_dev(cs_track_history* h, void* hip_stream, const 
                                    int curFrame, cs_feat_ref* d_featRef, unsigned char* d_refStatic, int* d_counts, const int* d_list, int nList,
                                    int advanceAll, unsigned char* d_select, int clearSelect, double* d_mapPts, double* d_mapCov,
                                    double pixelErrVar);
+/* ALL rounds of the second visits of a frame (cs_register_decide_kinds_rounds_dev's lists) in ONE launch of one workgroup: per round r the
+ * search over list r for every camera (cs_register_search_passes_range_dev with *pass, its P and list ignored), the whole-track mergability
+ * (cs_register_mergability_running_list_dev, no counters), the walks with the next round's list (cs_register_revisit_decide_next_dev with
+ * d_regOut, d_rvCnt its d_counts, d_rvCounts + r its count, d_rvCounts + nRounds the overflow) and advance + refine of the listed rows
+ * (cs_feat_ref_advance_refine_dev: list r, cap rows, advanceAll 0, d_regOut the marks, consumed).  Round r runs over the count round r - 1
+ * left (round 0's: the decide launch's); an empty list ends the launch -- at once when round 0's is empty.  Same bytes as those 4 x nRounds
+ * launches.  The pass's M / cov / pointFeat must be d_mapPts / d_mapCov / d_pointFeat; its slot / flags tables are the walks' candidates.
+ * nCams and N are the history's; regCams: the search's cameras (cs_register_search_dev), cams: the pose update's. */
+int cs_register_revisit_rounds_dev(cs_track_history* h, void* hip_stream, const cs_register_cam* regCams, const cs_poseupdate_cam* cams, int W,
+                                   int H, const cs_register_pass* pass, int nMap, int curFrame, int mapBase, int kinds, double* d_mapPts,
+                                   double* d_mapCov, double pixelErrVar, double tolPix, void* d_mergeCache, unsigned char* d_mergeable,
+                                   int* d_rvLists, int* d_rvCounts, int cap, int nRounds, int* d_visitLoop, int* d_nextLoop,
+                                   const unsigned char* d_mapFlags, int* d_pointFeat, int* const* d_slot2map, unsigned char* d_attached,
+                                   unsigned char* d_regOut, void* d_decideScratch, const int* d_curList, const int* d_curCount, int curCap,
+                                   int* d_rvCnt, cs_feat_ref* d_featRef, unsigned char* d_refStatic, int* d_frefCounts);
 /* the pools: device pointer ([nCams][cap]), capacity per camera, device counters [nCams] */
 int cs_track_history_segments(const cs_track_history* h, cs_feat_seg** d_pool, int* cap, int** d_count);
 /* the counters copied to the host (counts [nCams]); synchronous */

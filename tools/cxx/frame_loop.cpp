@@ -930,23 +930,22 @@ void FrameLoop::register_frame(int i, int dsti) {
     }
     if (o.fusedRounds) {
         // the decision (curStaticPointsRegInGroup, bMerge false: who attaches which feature) with the second visits' lists built by the walks
-        // themselves and advance + refine as one launch: 4 launches per round instead of 6, 2 instead of 3 behind the single pass
-        // (cs_register_decide_kinds_rounds_dev, cs_feat_ref_advance_refine_dev)
+        // themselves and advance + refine as one launch: 2 launches instead of 3 behind the single pass; then every round of the second visits
+        // as ONE launch of one workgroup, which leaves at once when list 0 is empty -- the usual frame (cs_register_decide_kinds_rounds_dev,
+        // cs_feat_ref_advance_refine_dev, cs_register_revisit_rounds_dev: the bytes of a search, a mergability, a walk and an advance + refine
+        // launch per round)
         CSCHK(cs_register_decide_kinds_rounds_dev(o.dev, (void*)poseS, nCams, N, nMap, 0, reg.slot, reg.flags, dMergeable, dMapFlags, dPf, s2mPtrs.data(),
                                                   dAttached, dRegged, dDecScratch, 0, dDecCnt, -1, 3, dRvLists, RV_CAP, RV_ROUNDS, dRvCounts, dRvVisit,
                                                   dRvNext));
         CSCHK(cs_feat_ref_advance_refine_dev(hist, (void*)poseS, pu.data(), nMap, dPf, i, dFref, dRstat, dFrefCnt, dCurList, P_REG, 1, dRegged, 0, dMap, dCov, PIX));
-        for (int r = 0; r < RV_ROUNDS; ++r) {
-            int* list = dRvLists + (size_t)r * RV_CAP;
-            search(RV_CAP, list, 0, nCams);
-            CSCHK(cs_register_mergability_running_list_dev(hist, (void*)poseS, 0, nCams, pu.data(), nMap, list, RV_CAP, dMap, dCov, reg.slot, reg.flags,
-                                                           PIX, 0.0, dMergeCache, dMergeable, nullptr));
-            const bool more = r + 1 < RV_ROUNDS;
-            CSCHK(cs_register_revisit_decide_next_dev(o.dev, (void*)poseS, nCams, N, nMap, RV_CAP, 0, 3, list, dRvNext, dRvVisit, reg.slot, reg.flags, dMergeable,
-                                                      dMapFlags, dPf, s2mPtrs.data(), dAttached, dRvReg[0], dDecScratch, dCurList, dCurCount, P_REG, dRvCnt,
-                                                      dRvCounts + r, more ? list + RV_CAP : nullptr, more ? dRvCounts + r + 1 : nullptr, dRvCounts + RV_ROUNDS));
-            CSCHK(cs_feat_ref_advance_refine_dev(hist, (void*)poseS, pu.data(), nMap, dPf, i, dFref, dRstat, dFrefCnt, list, RV_CAP, 0, dRvReg[0], 1, dMap, dCov, PIX));
-        }
+        cs_register_pass ps;
+        memset(&ps, 0, sizeof(ps));
+        ps.P = RV_CAP, ps.sigmaSearch = PIX, ps.maxDist = 3 * PIXVAR, ps.sigmaMerge = PIX;
+        ps.M = dMap, ps.cov = dCov, ps.pointFeat = dPf, ps.mapFlags = dMapFlags, ps.maxDistDynamic = 4 * PIXVAR;
+        ps.slot = reg.slot, ps.m = reg.m, ps.var = reg.var, ps.dist = reg.dist, ps.flags = reg.flags;
+        CSCHK(cs_register_revisit_rounds_dev(hist, (void*)poseS, rc[dsti].data(), pu.data(), W, H, &ps, nMap, i, 0, 3, dMap, dCov, PIX, 0.0, dMergeCache,
+                                             dMergeable, dRvLists, dRvCounts, RV_CAP, RV_ROUNDS, dRvVisit, dRvNext, dMapFlags, dPf, s2mPtrs.data(),
+                                             dAttached, dRvReg[0], dDecScratch, dCurList, dCurCount, P_REG, dRvCnt, dFref, dRstat, dFrefCnt));
         return;
     }
     // the same launch per step: the decision of the certainly static points, behind them the certainly dynamic ones (kinds 3), one call;
