@@ -35,3 +35,5 @@ from .ncc import (ncc_blocks_dev, ncc_epi_mat_dev, ncc_get_blocks_dev, ncc_match
                   ncc_scaled_dims)
 from .posegraph import PoseGraphs, after_ba_function, after_ba_record, posegraph_set_poses_dev  # noqa: F401,E402
 from .results import ExportCam, LoopExportCam, export_results_v1, loop_export_results  # noqa: F401,E402
+from .grouping import (CameraGroups, GroupingCam, camera_grouping_dev, camera_grouping_scratch_bytes, grouping_cams,  # noqa: F401,E402
+                       view_overlap_costs_dev)

@@ -24,6 +24,7 @@ HIP_SOURCES = [
     "hostview.hip",
     "register.hip",
     "keyframe.hip",
+    "grouping.hip",
     "poseupdate.hip",
     "ncc.hip",
     "newpts.hip",

@@ -38,6 +38,7 @@ import numpy as np
 import coslam_amd
 from coslam_amd._lib import check
 from coslam_amd.ba import BAInterCam, BAOutput, BAWindow, BAWorkspace, intercam_cams
+from coslam_amd.grouping import CameraGroups, camera_grouping_dev, camera_grouping_scratch_bytes, grouping_cams
 from coslam_amd.handback import handback_cams, handback_dev
 from coslam_amd.keyframe import keyframe_cams, keyframe_ready_dev, keyframe_snapshot_dev
 from coslam_amd.ncc import (NCC_PAIR_DTYPE, ncc_cams, ncc_epi_pairs_group_dev, ncc_fmats_dev, ncc_get_blocks_group_dev, ncc_pair_jobs,
@@ -128,6 +129,12 @@ class LoopConfig:
         # wait can only end by timing out (2 s, counted by wait_errors).  The host wait returns once the worker has synchronised its
         # stream behind the pack (the record is complete); with the apply lag the solve is long done by then.
         self.device_wait = False
+        self.camera_grouping = False     # CoSLAM::cameraGrouping per frame on the device (cs_camera_grouping_dev, reference src/app/SL_CoSLAM.cpp:1632-1697),
+        # where the reference has it: behind the pose update, before the registration.  REPORTED (FrameLoop.grouping_stats): the registration,
+        # the inter-camera matcher and the key frame's record still run as if the rig were one group.  It only reads loop state: the digest
+        # is the digest with it off.  Off: nothing allocated, no launch added
+        self.group_min_overlap_num, self.group_min_overlap_area_ratio = 0, 0.0   # getViewOverlapCosts(viewOverlapCost, 0, 0.0), :1635
+        self.group_max_dist_ratio = 6.0   # Param::maxDistRatio (src/app/SL_GlobParam.cpp:18)
         self.export_frames = 0     # > 0: a whole-run archive of that many frames behind the pose history (cs_track_history_set_archive), so that
         # FrameLoop.export_results can write the whole run's trajectory and features; 0: off (nothing allocated, nothing launched)
         for k, v in kw.items():
@@ -183,6 +190,7 @@ class FrameLoop:
         # of every section of a frame, by kind of frame.  Not a valid bench line: two events per section cost a few microseconds each.)
         self._marks = [] if os.environ.get("FRAMELOOP_GPU_SECTIONS") else None
         # (the stages in the order of their device allocations and stream creation: the order is part of what a run computes and how fast)
+        self.grouping = None
         self.setup_state(map_cov)
         self.setup_trackers(klt_cfg)
         self.setup_comm(dist_backend)
@@ -592,6 +600,88 @@ class FrameLoop:
             torch.cuda.synchronize()
         if cfg.keyframe_decision or cfg.intracam_mapping or cfg.keyframe_drives:
             self.enable_keyframe_decision(0, 0)
+        if cfg.camera_grouping:
+            self._enable_camera_grouping()
+
+    GROUP_RING = 128   # frames of grouping results kept on the device; the host takes the older half over when the newer one is full
+
+    def _enable_camera_grouping(self):
+        """m_initCamTranslation -- the mean pairwise distance of ALL cameras' centres at map initialisation (reference
+        src/app/SL_CoSLAM.cpp:280-290), from the initial poses on the host -- and the device ring the per-frame results go into."""
+        torch, cfg, NA, z = self.torch, self.cfg, self.cfg.n_cams, self._z
+        cen = [-np.asarray(self.sc.pose(c, 0)[0], np.float64).reshape(3, 3).T @ np.asarray(self.sc.pose(c, 0)[1], np.float64) for c in range(NA)]
+        dist = [float(np.linalg.norm(cen[a] - cen[c])) for a in range(NA) for c in range(a + 1, NA)]
+        RING = self.GROUP_RING
+        words = C.sizeof(CameraGroups) // 4
+        self.grouping = dict(init_translation=float(np.mean(dist)) if dist else 0.0,
+                             cams=[grouping_cams([dict(xy=self.d_xy[g].data_ptr(), R=self.d_R[q][g].data_ptr(), t=self.d_t[q][g].data_ptr())
+                                                  for g in range(NA)]) for q in range(2)],
+                             groups=z((RING, words), torch.int32), vcosts=z((RING, NA * NA), torch.float64), nshare=z((RING, NA * NA), torch.int32),
+                             scratch=z(camera_grouping_scratch_bytes(NA, cfg.n_feat), torch.uint8),
+                             ev=[torch.cuda.Event(), torch.cuda.Event()], calls=0, taken=0, frames=[], per_frame=[], more_than_one=0, first_such=None,
+                             changes=0, last=None)
+        torch.cuda.synchronize()   # (zero-filled on torch's stream, used on the pose stream)
+
+    def _camera_grouping(self, i, dst):
+        """CoSLAM::cameraGrouping of frame i on the pose stream: this frame's pointFeat, pixels and map flags, the poses just written; rows
+        0 .. map count (the frame's current-points list is built later, by the registration).  One launch, no wait: the result goes into
+        slot calls % GROUP_RING of the device ring; a half of the ring is read when the other half has been filled since (its event is
+        64 frames old by then)."""
+        cfg, g, RING = self.cfg, self.grouping, self.GROUP_RING
+        half = RING // 2
+        if g["calls"] - g["taken"] >= RING:
+            self._grouping_take(half)
+        slot = g["calls"] % RING
+        camera_grouping_dev(self.pose_s.cuda_stream, g["cams"][dst], cfg.n_feat, self.n_map, self.d_mapcount.data_ptr(), self.d_pf.data_ptr(),
+                            self.d_mapflags.data_ptr(), cfg.W, cfg.H, g["vcosts"][slot].data_ptr(), g["nshare"][slot].data_ptr(),
+                            g["scratch"].data_ptr(), g["init_translation"], g["groups"][slot].data_ptr(), maxDistRatio=cfg.group_max_dist_ratio,
+                            minOverlapNum=cfg.group_min_overlap_num, minOverlapAreaRatio=cfg.group_min_overlap_area_ratio, device=self.device)
+        g["frames"].append(i)
+        g["calls"] += 1
+        if g["calls"] % half == 0:
+            g["ev"][(slot // half) & 1].record(self.pose_s)
+
+    def _grouping_take(self, n, synced=False):
+        """the oldest n results of the ring to the host (n = half a ring behind its event, or whatever is left behind a drain)"""
+        g, RING, NA = self.grouping, self.GROUP_RING, self.cfg.n_cams
+        if n <= 0:
+            return
+        s0 = g["taken"] % RING
+        if not synced:
+            g["ev"][(s0 // (RING // 2)) & 1].synchronize()
+        idx = [(s0 + k) % RING for k in range(n)]
+        gr, vc, ns = g["groups"][idx].cpu().numpy(), g["vcosts"][idx].cpu().numpy(), g["nshare"][idx].cpu().numpy()
+        for k in range(n):
+            G = CameraGroups.from_bytes(gr[k].tobytes())
+            groups = G.groups()
+            if len(groups) > 1:
+                g["more_than_one"] += 1
+                if g["first_such"] is None:
+                    g["first_such"] = g["frames"][k]
+            if g["last"] is not None and g["last"]["groups"] != groups:
+                g["changes"] += 1
+            g["per_frame"].append(len(groups))
+            g["last"] = dict(frame=g["frames"][k], groups=groups, vcosts=vc[k].reshape(NA, NA).copy(), nshare=ns[k].reshape(NA, NA).copy())
+        del g["frames"][:n]
+        g["taken"] += n
+
+    def grouping_stats(self):
+        """what CoSLAM::cameraGrouping said over the frames it ran on (LoopConfig.camera_grouping; drains the device first).
+        frames_with_more_than_one_group is the counter that says the later stages' ONE-GROUP ASSUMPTION no longer holds: the registration
+        walks, the inter-camera matcher and the key frame's record of this loop treat the rig as one group on every frame, which is the
+        reference's result exactly as long as this counter is 0.  last_groups: the cameras of every group in the reference's order of
+        discovery; last_vcosts: viewOverlapCost of the last frame (after the distance cut); group_changes: frames whose groups differ from
+        the frame's before."""
+        if self.grouping is None:
+            return None
+        g = self.grouping
+        self.torch.cuda.synchronize()
+        self._grouping_take(g["calls"] - g["taken"], synced=True)
+        last = g["last"]
+        return dict(groups_per_frame=list(g["per_frame"]), last_groups=None if last is None else last["groups"],
+                    frames_with_more_than_one_group=g["more_than_one"], first_such_frame=g["first_such"], group_changes=g["changes"],
+                    last_vcosts=None if last is None else last["vcosts"].tolist(), last_nshare=None if last is None else last["nshare"].tolist(),
+                    last_frame=None if last is None else last["frame"], init_cam_translation=g["init_translation"])
 
     def enable_keyframe_decision(self, frame, b):
         """the key-pose state as CoSLAM::initMap leaves it (reference src/app/SL_CoSLAM.cpp:246-256, :278-291) -- or as a key frame added at
@@ -710,6 +800,9 @@ class FrameLoop:
         if self.pose_upd is not None:
             self._pose_update(i, dst)
         self._mark(i, "pose update + classify")
+        if self.grouping is not None:   # cameraGrouping: behind poseUpdate, before activeMapPointsRegister (CoSLAMThread.cpp:107-109)
+            self._camera_grouping(i, dst)
+            self._mark(i, "camera grouping")
         # poseUpdate (with mapPointsClassify) -> activeMapPointsRegister -> genNewMapPoints -> currentMapPointsRegister: the new map points
         # take their features BEFORE the current points' registration looks at them (a feature that carries a point ends a registration walk)
         if self.kf:

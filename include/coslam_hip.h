@@ -721,6 +721,57 @@ int cs_keyframe_snapshot_dev(int device, void* hip_stream, int nCams, int N, con
                              const double* d_R, const double* d_t, const int* d_word, double* d_xyOut, int* d_stateOut, int* d_slot2mapOut,
                              double* d_ROut, double* d_tOut, int* h_word);
 
+/* ---- camera grouping: CoSLAM::getViewOverlapCosts (src/app/SL_CoSLAM.cpp:1543-1630) and CoSLAM::cameraGrouping (:1632-1697) -------------
+ * The frame's step between poseUpdate and activeMapPointsRegister (src/gui/CoSLAMThread.cpp:100-121); DESIGN.md 3.17.
+ * A map point takes part when its row is below *d_mapCount (NULL: nMap), it is not CS_MAP_FALSE (d_mapFlags, may be NULL) and
+ * d_pointFeat [nMap][nCams] (the hand-back's table: slot of the feature of THIS frame, or < 0) names a feature in at least two cameras.
+ * numVisCam is the count of those entries here, so the reference's `numVisCam == 1` (:1563) needs no test of its own: a point one camera
+ * holds forms no pair.  For every unordered pair of the cameras that hold a point nShare[i][j] and [j][i] go up by one and the feature's
+ * pixel in camera i -- cams[i].xy of its slot, the UNDISTORTED pixel as FeaturePoint::x, y (src/tracking/GPUKLT.cpp:41-48) -- joins
+ * sharedPoints[i][j].  vcosts[i][i] = -1; a pair gets -1 when nShare < minOverlapNum, or area(i,j) < minOverlapAreaRatio * W * H or
+ * area(j,i) < minOverlapAreaRatio * W * H (one image size for the rig, as every rig entry); otherwise vcosts[i][j] = vcosts[j][i] = nShare.
+ * get2DConvexHull / getPolyArea are not in the reference tree: area(i,j) is the shoelace area of the convex hull of sharedPoints[i][j], zero
+ * for fewer than three points or a collinear set.
+ *
+ * d_list / d_listCount (or NULL): the rows to read as a list of map indices (cs_register_list_current_dev's; entries < 0 are skipped;
+ * d_listCount NULL: nMap entries); without a list rows 0 .. *d_mapCount are read.
+ * Outputs: d_vcosts [nCams * nCams] doubles, d_nShare [nCams * nCams] ints, d_hullArea [nCams * nCams] doubles or NULL.
+ * THE HULL PATH RUNS WHEN minOverlapAreaRatio > 0 OR d_hullArea IS NOT NULL, and only then: a ratio <= 0 can never cut a pair (an area is
+ * never < 0), so the call is then one launch that counts (256-thread workgroups, 1 KB of LDS: it fits beside the persistent tracker).
+ * The hull path is a second launch, one workgroup per ordered pair with 32 * N bytes of LDS (N <= 5088); a slot carries one map point, so a
+ * pair shares at most N points -- a table that names more is counted past, never written past, and that pair's area reads -1 (below every
+ * positive threshold, and no hull's area), since an entry waits for nothing and so cannot return what only the device knows.
+ * d_scratch: cs_camera_grouping_scratch_bytes() bytes of device memory, ZEROED ONCE by the caller before its first use (every call leaves
+ * it zeroed); one scratch per stream -- calls that share a scratch must be ordered.  At most two launches, no host wait, no read-back.
+ * nCams: 1..16 (CS_ERR_INVALID otherwise, with cs_last_error() text). */
+typedef struct {
+    const double* xy;   /* 2N: the hand-back's undistorted pixels, x[N] then y[N] (cs_handback_cam::xy, cs_register_cam::xy) */
+    const double* R;    /* 9, 3: m_camPos.current() (read by cs_camera_grouping_dev only) */
+    const double* t;
+} cs_grouping_cam;
+/* CameraGroup m_groups[] / m_groupNum / m_groupId[] (src/app/SL_CoSLAM.h).  Groups are numbered by their lowest camera; camIds[g][0 .. num[g])
+ * is the ORDER OF DISCOVERY of the reference's explicit stack, not ascending (edges 0-2 and 2-1 only: [0, 2, 1]) -- the order in which the
+ * "InGroup" loops run the cameras.  Entries behind num[g], groups behind groupNum and groupId behind nCams are -1 / 0. */
+typedef struct cs_camera_groups {
+    int groupNum;
+    int num[16];
+    int camIds[16][16];
+    int groupId[16];
+} cs_camera_groups;
+size_t cs_camera_grouping_scratch_bytes(int nCams, int N);
+int cs_view_overlap_costs_dev(int device, void* hip_stream, int nCams, const cs_grouping_cam* cams /* host array */, int N, int nMap,
+                              const int* d_mapCount, const int* d_pointFeat, const unsigned char* d_mapFlags, const int* d_list,
+                              const int* d_listCount, int W, int H, int minOverlapNum, double minOverlapAreaRatio, double* d_vcosts, int* d_nShare,
+                              double* d_hullArea, void* d_scratch);
+/* cameraGrouping: the costs (the reference calls them with (0, 0.0)), every pair with a positive cost whose camera centres (getCamCenter:
+ * -R^T t) are further apart than initCamTranslation * maxDistRatio (m_initCamTranslation: the mean pairwise centre distance at map
+ * initialisation, :280-290; Param::maxDistRatio = 6.0) cut, then the connected components over cost > 0 into d_groups (device memory).
+ * d_vcosts holds the costs AFTER the cut (viewOverlapCost), d_nShare is untouched by it.  One camera: one group, nothing counted (:1633). */
+int cs_camera_grouping_dev(int device, void* hip_stream, int nCams, const cs_grouping_cam* cams /* host array */, int N, int nMap,
+                           const int* d_mapCount, const int* d_pointFeat, const unsigned char* d_mapFlags, const int* d_list,
+                           const int* d_listCount, int W, int H, int minOverlapNum, double minOverlapAreaRatio, double* d_vcosts, int* d_nShare,
+                           double* d_hullArea, void* d_scratch, double initCamTranslation, double maxDistRatio, cs_camera_groups* d_groups);
+
 /* ---- MapPoint::pFeatures as the reference holds them: feature references (round 5; VERDICT r04 missing 3) ---------------------------------
  * p->pFeatures[c] is the feature of this frame while camera c tracks the point -- and STAYS what it last was when the camera loses it
  * (nothing clears the pointer): updateStaticPointPosition / updateDynamicPointPosition (src/slam/SL_CoSLAMHelper.cpp:338-394, 455-484),

@@ -11,7 +11,9 @@
 // COSLAM_PIXEL_ERR_STD=1; COSLAM_KEYFRAME_DRIVES=1, COSLAM_KEYFRAME_LAG, COSLAM_KEYFRAME_RATIO (the key-frame decision);
 // COSLAM_EXPORT_DIR (the run's result files, written there after the drain: cs_loop_export_results) with COSLAM_EXPORT_FRAMES (the
 // whole-run archive behind the pose history, in frames: cs_track_history_set_archive); COSLAM_HIST_STORE (frames of pixels + poses the pose
-// history keeps: 4096, as LoopConfig.hist_store).
+// history keeps: 4096, as LoopConfig.hist_store); COSLAM_CAMERA_GROUPING=1 (CoSLAM::cameraGrouping per frame behind the pose update, reported
+// under "camera_grouping": cs_camera_grouping_dev) with COSLAM_GROUP_MIN_OVERLAP_NUM (0), COSLAM_GROUP_MIN_AREA_RATIO (0.0),
+// COSLAM_GROUP_MAX_DIST_RATIO (6.0).
 // Per frame (reference call sites in bench.py's docstring): camera-group redetect (+ prefetch of the next frame's front) on the
 // tracker stream; hand-back + intraCamEstimate of all cameras + both registration passes on the pose stream, event-ordered
 // behind the tracker; at key frames the inter-camera solve and the joint local BA (parsed on the device from the window ring) on their
@@ -116,6 +118,9 @@ struct Options {
     const char* exportDir;   // COSLAM_EXPORT_DIR: nullptr = no export
     int exportFrames;        // COSLAM_EXPORT_FRAMES: the archive's capacity (0: none)
     int histStore;           // COSLAM_HIST_STORE: frames the pose history keeps (>= the walks' 64)
+    bool grouping;           // COSLAM_CAMERA_GROUPING=1 (see FrameLoop::camera_grouping)
+    int groupMinNum;         // getViewOverlapCosts(viewOverlapCost, 0, 0.0), src/app/SL_CoSLAM.cpp:1635
+    double groupMinAreaRatio, groupMaxDistRatio;   // Param::maxDistRatio = 6.0 (src/app/SL_GlobParam.cpp:18)
 };
 
 static Options read_options(int argc, char** argv) {
@@ -147,6 +152,12 @@ static Options read_options(int argc, char** argv) {
     o.exportDir = ed && ed[0] ? ed : nullptr;
     o.exportFrames = std::max(0, envi("COSLAM_EXPORT_FRAMES", 0));
     o.histStore = std::max(64, envi("COSLAM_HIST_STORE", 4096));
+    o.grouping = flag("COSLAM_CAMERA_GROUPING", '1');
+    o.groupMinNum = envi("COSLAM_GROUP_MIN_OVERLAP_NUM", 0);
+    const char* gar = getenv("COSLAM_GROUP_MIN_AREA_RATIO");
+    o.groupMinAreaRatio = gar && gar[0] ? atof(gar) : 0.0;
+    const char* gdr = getenv("COSLAM_GROUP_MAX_DIST_RATIO");
+    o.groupMaxDistRatio = gdr && gdr[0] ? atof(gdr) : 6.0;
     return o;
 }
 
@@ -408,6 +419,23 @@ struct FrameLoop {
     std::vector<int> pairA, pairB;
     std::vector<const double*> pairIK;
     int nccRuns = 0;
+    // CoSLAM::cameraGrouping per frame (COSLAM_CAMERA_GROUPING=1), reported only: a device ring of results, its older half read by the host
+    // when the newer one has been filled since (behind an event that is half a ring old: never a wait for the frame in flight)
+    static constexpr int GROUP_RING = 128;
+    double grpInitTranslation = 0.0;   // m_initCamTranslation (src/app/SL_CoSLAM.cpp:280-290)
+    std::vector<cs_grouping_cam> grpCams[2];
+    cs_camera_groups* dGrpGroups = nullptr;
+    double* dGrpCosts = nullptr;
+    int* dGrpShare = nullptr;
+    void* dGrpScratch = nullptr;
+    hipEvent_t grpEv[2];
+    hipStream_t grpCopyS = nullptr;
+    long long grpCalls = 0, grpTaken = 0;
+    std::vector<int> grpPerFrame;
+    int grpMoreThanOne = 0, grpFirstSuch = -1, grpChanges = 0;
+    bool grpHaveLast = false;
+    cs_camera_groups grpLast;
+    std::vector<double> grpLastCosts;
     // drain
     int* dBar;
     int nEmptySolves = 0;
@@ -436,6 +464,10 @@ struct FrameLoop {
     void register_frame(int i, int dsti);
     void key_frame_actions(int f, const cs_handback_cam* cams, const double* Rk, const double* tk, bool placed, int dsti);
     void keyframe_decision_step(int i, int dsti);
+    void setup_camera_grouping();
+    void camera_grouping(int i, int dsti);
+    void grouping_take(int n, bool synced);
+    std::string grouping_json();
     void run(int n) {
         for (int q = 0; q < n; ++q, ++nDone) step(nDone + 1, keyEvery > 0 && nDone % keyEvery == 0);
     }
@@ -743,6 +775,100 @@ void FrameLoop::setup_decision_scratch() {
     dMergeCnt = dev_zeros<int>(4);
 }
 
+// m_initCamTranslation from the initial poses of ALL cameras (the mean pairwise distance of their centres, on the host) and the device ring
+void FrameLoop::setup_camera_grouping() {
+    double sum = 0.0;
+    int n = 0;
+    auto centre = [&](int c, double C[3]) {
+        const double *R = w.R0.data() + 9 * c, *t = w.t0.data() + 3 * c;
+        for (int k = 0; k < 3; ++k) C[k] = -((R[k] * t[0] + R[3 + k] * t[1]) + R[6 + k] * t[2]);
+    };
+    for (int a = 0; a < nCams; ++a)
+        for (int b = a + 1; b < nCams; ++b, ++n) {
+            double A[3], B[3];
+            centre(a, A), centre(b, B);
+            sum += std::sqrt((A[0] - B[0]) * (A[0] - B[0]) + (A[1] - B[1]) * (A[1] - B[1]) + (A[2] - B[2]) * (A[2] - B[2]));
+        }
+    grpInitTranslation = n ? sum / n : 0.0;
+    for (int q = 0; q < 2; ++q) {
+        grpCams[q].resize(nCams);
+        for (int c = 0; c < nCams; ++c) grpCams[q][c] = cs_grouping_cam{dXY + (size_t)c * 2 * N, dR[q] + 9 * c, dT[q] + 3 * c};
+    }
+    dGrpGroups = dev_zeros<cs_camera_groups>(GROUP_RING);
+    dGrpCosts = dev_zeros<double>((size_t)GROUP_RING * nCams * nCams);
+    dGrpShare = dev_zeros<int>((size_t)GROUP_RING * nCams * nCams);
+    dGrpScratch = dev_zeros<unsigned char>(cs_camera_grouping_scratch_bytes(nCams, N));   // (zeroed once: every call leaves it zeroed)
+    for (int h = 0; h < 2; ++h) HIPCHK(hipEventCreateWithFlags(&grpEv[h], hipEventDisableTiming));
+    HIPCHK(hipStreamCreateWithFlags(&grpCopyS, hipStreamNonBlocking));
+    grpLastCosts.assign((size_t)nCams * nCams, 0.0);
+}
+
+// CoSLAM::cameraGrouping of frame i where the reference has it (src/gui/CoSLAMThread.cpp:107-109): this frame's pointFeat, pixels and map
+// flags, the poses just written; rows 0 .. map count (the frame's current-points list is built later, by the registration).  One launch
+void FrameLoop::camera_grouping(int i, int dsti) {
+    (void)i;
+    const int half = GROUP_RING / 2;
+    if (grpCalls - grpTaken >= GROUP_RING) grouping_take(half, false);
+    const int slot = (int)(grpCalls % GROUP_RING);
+    CSCHK(cs_camera_grouping_dev(o.dev, (void*)poseS, nCams, grpCams[dsti].data(), N, nMap, dMapCount, dPf, dMapFlags, nullptr, nullptr, W, H,
+                                 o.groupMinNum, o.groupMinAreaRatio, dGrpCosts + (size_t)slot * nCams * nCams, dGrpShare + (size_t)slot * nCams * nCams,
+                                 nullptr, dGrpScratch, grpInitTranslation, o.groupMaxDistRatio, dGrpGroups + slot));
+    if (++grpCalls % half == 0) HIPCHK(hipEventRecord(grpEv[(slot / half) & 1], poseS));
+}
+
+// the oldest n results of the ring to the host: one copy of the records and one of the costs per stretch of the ring, one wait
+void FrameLoop::grouping_take(int n, bool synced) {
+    const int half = GROUP_RING / 2;
+    const size_t nn = (size_t)nCams * nCams;
+    std::vector<cs_camera_groups> g;
+    std::vector<double> costs;
+    for (int k = 0; k < n;) {
+        const int slot = (int)((grpTaken + k) % GROUP_RING), seg = std::min(n - k, GROUP_RING - slot);
+        if (!synced && k == 0) HIPCHK(hipEventSynchronize(grpEv[(slot / half) & 1]));
+        g.resize(seg), costs.resize(seg * nn);
+        HIPCHK(hipMemcpyAsync(g.data(), dGrpGroups + slot, sizeof(cs_camera_groups) * seg, hipMemcpyDeviceToHost, grpCopyS));
+        HIPCHK(hipMemcpyAsync(costs.data(), dGrpCosts + (size_t)slot * nn, sizeof(double) * seg * nn, hipMemcpyDeviceToHost, grpCopyS));
+        HIPCHK(hipStreamSynchronize(grpCopyS));
+        for (int q = 0; q < seg; ++q) {
+            if (g[q].groupNum > 1) {
+                ++grpMoreThanOne;
+                if (grpFirstSuch < 0) grpFirstSuch = (int)(grpTaken + k + q) + 1;   // (the loop's frames are 1, 2, ...: one call per frame)
+            }
+            if (grpHaveLast && memcmp(&grpLast, &g[q], sizeof(cs_camera_groups)) != 0) ++grpChanges;
+            grpPerFrame.push_back(g[q].groupNum);
+            grpLast = g[q], grpHaveLast = true;
+        }
+        std::copy(costs.end() - nn, costs.end(), grpLastCosts.begin());
+        k += seg;
+    }
+    grpTaken += n;
+}
+
+std::string FrameLoop::grouping_json() {
+    if (!o.grouping) return "null";
+    grouping_take((int)(grpCalls - grpTaken), true);   // (behind the barrier)
+    std::string s = "{\"groups_per_frame\": [";
+    for (size_t q = 0; q < grpPerFrame.size(); ++q) s += (q ? ", " : "") + std::to_string(grpPerFrame[q]);
+    s += "], \"last_groups\": [";
+    if (grpHaveLast)
+        for (int g = 0; g < grpLast.groupNum; ++g) {
+            s += g ? ", [" : "[";
+            for (int k = 0; k < grpLast.num[g]; ++k) s += (k ? ", " : "") + std::to_string(grpLast.camIds[g][k]);
+            s += "]";
+        }
+    s += "], \"frames_with_more_than_one_group\": " + std::to_string(grpMoreThanOne) + ", \"first_such_frame\": " +
+         (grpFirstSuch < 0 ? std::string("null") : std::to_string(grpFirstSuch)) + ", \"group_changes\": " + std::to_string(grpChanges) +
+         ", \"last_vcosts\": [";
+    for (int a = 0; a < nCams; ++a) {
+        s += a ? ", [" : "[";
+        for (int b = 0; b < nCams; ++b) s += (b ? ", " : "") + std::to_string((long long)grpLastCosts[(size_t)a * nCams + b]);
+        s += "]";
+    }
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%.17g", grpInitTranslation);
+    return s + "], \"init_cam_translation\": " + buf + "}";
+}
+
 // first frame: detect, map association, first hand-back (GPUKLT::first + map initialisation stand-in)
 void FrameLoop::first_frame() {
     for (int b = 0; b < 2; ++b) {
@@ -785,6 +911,7 @@ void FrameLoop::first_frame() {
         HIPCHK(hipMemcpy(dKfSelfR, dR[0], sizeof(double) * 9 * nCams, hipMemcpyDeviceToDevice));
         HIPCHK(hipMemcpy(dKfSelfT, dT[0], sizeof(double) * 3 * nCams, hipMemcpyDeviceToDevice));
     }
+    if (o.grouping) setup_camera_grouping();
 }
 
 // every tracked slot of the first frame onto the nearest projected map point within 1 px
@@ -843,6 +970,7 @@ void FrameLoop::step(int i, bool key) {
     // launches (the gate's lane of a point also lists it for the classification)
     CSCHK(cs_pose_update_classify_frame_dev(hist, (void*)poseS, pu.data(), dPf, nMap, dR[dsti], dT[dsti], dMap, dCov, dMapFlags, 0, PIX, i, 20, 5,
                                             3, 6.0, nullptr, nullptr, nullptr, nullptr, nullptr, dNewPt, dSfn, dFirstFrm, PIX_CLASSIFY, nullptr));
+    if (o.grouping) camera_grouping(i, dsti);   // cameraGrouping: behind poseUpdate, before activeMapPointsRegister
     if (o.kfDrives)   // genNewMapPoints' first half (:1294-1346): is a camera ready for a key frame; addKeyFrame's bookkeeping when `decrease` holds
         CSCHK(cs_keyframe_ready_dev(o.dev, (void*)poseS, nCams, N, kfCams[dsti].data(), nMap, dMap, dMapFlags, dFirstFrm, i, o.kfRatio, 5.0,
                                     kfMinTranslation, 1, dKfReady, dKfCnt, dKfCen, dKfStats));
@@ -1080,6 +1208,7 @@ void FrameLoop::report(double dt, double dtHost, int applied0, const int rvCnt0[
     int decUnsettled = 0;   // (the decision scratch's last int: sticky "some call's sweeps did not settle")
     HIPCHK(hipMemcpy(&decUnsettled, (char*)dDecScratch + cs_register_decide_scratch_bytes(nCams, N, nMap) - sizeof(int), sizeof(int),
                      hipMemcpyDeviceToHost));
+    const std::string groupingJson = grouping_json();
     const char* transport = o.world == 1 ? "none" : o.hostSegment ? "host segment (test)" : "rccl";
     printf("{\"frames_per_s\": %.3f, \"ms_per_step\": %.5f, \"steps\": %d, \"warmup\": %d, \"host_enqueue_ms_per_step\": %.5f, "
            "\"cams_per_tracker_launch\": %d, \"pose_ok\": %s, \"min_live_features\": %d, \"joint_lm_steps\": %d, \"joint_cost\": %.6f, "
@@ -1089,12 +1218,12 @@ void FrameLoop::report(double dt, double dtHost, int applied0, const int rvCnt0[
            "\"map_capacity\": %d, \"new_map_points_last_run\": %d, \"register_decisions_unsettled\": %s, \"bmerge_frames\": %d, \"current_points_beyond_the_cap\": %d, \"second_visit_rounds\": %d, \"second_visit_features_attached\": %d, "
            "\"second_visit_conflicts\": %d, \"second_visit_conflicts_in_timed_region\": %d, \"second_visit_points_beyond_the_list\": %d, "
            "\"key_frames_placed_by_the_decision\": %s, \"keyframe_lag\": %d, \"frames_run\": %d, \"windows_requested\": %lld, \"windows_applied\": %d, \"windows_not_applied_history_too_short\": %d, "
-           "\"rank\": %d, \"world\": %d, \"cameras_per_rank\": %d, \"transport\": \"%s\", \"digest\": \"%016llx\"}\n",
+           "\"camera_grouping\": %s, \"rank\": %d, \"world\": %d, \"cameras_per_rank\": %d, \"transport\": \"%s\", \"digest\": \"%016llx\"}\n",
            steps / dt, dt / steps * 1e3, steps, o.warmup, dtHost / steps * 1e3, w.camsPerLaunch, okAll ? "true" : "false", minLive,
            sj.nIterTotal, sj.cost, si.nIterTotal, si.cost, nccRuns, jC, jP, jO, o.baLag, sched.nApplied - applied0,
            cs_ba_output_wait_errors(bout), iS, iP - iS, w.nPts, mapCountNow, nMap, npCounts[0], decUnsettled ? "true" : "false", nMergeFrames, curOverflow,
            RV_ROUNDS, rvCnt[0], rvCnt[2], rvCnt[2] - rvCnt0[2], rvListCnt[1], o.kfDrives ? placedJson.c_str() : "null", o.kfDrives ? o.kfLag : 0, nDone,
-           sched.nRequested, sched.nApplied, sched.nNotApplied, o.rank, o.world, nc, transport, digest);
+           sched.nRequested, sched.nApplied, sched.nNotApplied, groupingJson.c_str(), o.rank, o.world, nc, transport, digest);
     fflush(stdout);
 }
 
