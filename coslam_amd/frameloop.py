@@ -40,6 +40,7 @@ from coslam_amd._lib import check
 from coslam_amd.ba import BAInterCam, BAOutput, BAWindow, BAWorkspace, intercam_cams
 from coslam_amd.grouping import CameraGroups, camera_grouping_dev, camera_grouping_scratch_bytes, grouping_cams
 from coslam_amd.handback import handback_cams, handback_dev
+from coslam_amd.liveview import LiveView
 from coslam_amd.keyframe import keyframe_cams, keyframe_ready_dev, keyframe_snapshot_dev
 from coslam_amd.ncc import (NCC_PAIR_DTYPE, ncc_cams, ncc_epi_pairs_group_dev, ncc_fmats_dev, ncc_get_blocks_group_dev, ncc_pair_jobs,
                             ncc_scaled_dims)
@@ -135,6 +136,13 @@ class LoopConfig:
         # is the digest with it off.  Off: nothing allocated, no launch added
         self.group_min_overlap_num, self.group_min_overlap_area_ratio = 0, 0.0   # getViewOverlapCosts(viewOverlapCost, 0, 0.0), :1635
         self.group_max_dist_ratio = 6.0   # Param::maxDistRatio (src/app/SL_GlobParam.cpp:18)
+        self.live_view = False           # the frame's last step (cs_liveview_frame_dev: CoSLAM::getNumDynamicStaticPoints, storeDynamicPoints,
+        # reference src/app/SL_CoSLAM.cpp:1447-1471, :1900-1911, and the display's copy) at the end of the frame's pose work: the counts, the
+        # dynamic points into a device ring of live_view_trail_depth frames, and every live_view_every-th frame a snapshot (poses, groups,
+        # the current map points) into a pinned ring of live_view_depth slots, read by FrameLoop.live_snapshot / live_trails when somebody
+        # wants them.  It only reads loop state: the digest is the digest with it off.  Off: nothing allocated, no launch added
+        self.live_view_every, self.live_view_depth, self.live_view_trail_depth = 1, 8, 150   # (150: the display's m_nTrjLen, GLScenePane.h:26)
+        self.live_view_cur_cap, self.live_view_dyn_cap = 0, 0    # 0: the map's capacity / a quarter of it
         self.export_frames = 0     # > 0: a whole-run archive of that many frames behind the pose history (cs_track_history_set_archive), so that
         # FrameLoop.export_results can write the whole run's trajectory and features; 0: off (nothing allocated, nothing launched)
         for k, v in kw.items():
@@ -191,6 +199,7 @@ class FrameLoop:
         self._marks = [] if os.environ.get("FRAMELOOP_GPU_SECTIONS") else None
         # (the stages in the order of their device allocations and stream creation: the order is part of what a run computes and how fast)
         self.grouping = None
+        self.live = None
         self.setup_state(map_cov)
         self.setup_trackers(klt_cfg)
         self.setup_comm(dist_backend)
@@ -602,6 +611,10 @@ class FrameLoop:
             self.enable_keyframe_decision(0, 0)
         if cfg.camera_grouping:
             self._enable_camera_grouping()
+        if cfg.live_view:
+            self.live = LiveView(cfg.n_cams, cfg.live_view_cur_cap or self.n_map, cfg.live_view_dyn_cap or max(1, self.n_map // 4),
+                                 depth=cfg.live_view_depth, trail_depth=cfg.live_view_trail_depth, every=cfg.live_view_every, device=self.device)
+            self.live_frames, self.live_published = 0, 0
 
     GROUP_RING = 128   # frames of grouping results kept on the device; the host takes the older half over when the newer one is full
 
@@ -664,6 +677,44 @@ class FrameLoop:
             g["last"] = dict(frame=g["frames"][k], groups=groups, vcosts=vc[k].reshape(NA, NA).copy(), nshare=ns[k].reshape(NA, NA).copy())
         del g["frames"][:n]
         g["taken"] += n
+
+    def _live_view(self, i, dst):
+        """storeDynamicPoints + the display's copy of frame i on the pose stream, behind the registration (CoSLAMThread.cpp:117-120): the
+        loop's tables as they stand, the poses just written, the frame's groups when the grouping runs.  One launch, no wait."""
+        g = self.grouping
+        d_groups = g["groups"][(g["calls"] - 1) % self.GROUP_RING].data_ptr() if g is not None and g["calls"] else None
+        self.live.frame_dev(self.pose_s.cuda_stream, i, self.n_map, self.d_mapcount.data_ptr(), self.d_pf.data_ptr(), self.d_mapflags.data_ptr(),
+                            self.d_map.data_ptr(), self.d_R[dst].data_ptr(), self.d_t[dst].data_ptr(), d_groups)
+        self.live_frames += 1
+        self.live_published += i % self.cfg.live_view_every == 0
+
+    def live_snapshot(self, frame=None):
+        """a published frame of the live view (LoopConfig.live_view) as a dict of copies -- frame, mapCount, nCur, nDyn, the overflow counts,
+        nStatic / nDynamic / nStaticFeat / nDynamicFeat (getNumDynamicStaticPoints), R, t, groups, points (records with M, id, camMask, flags,
+        numVisCam in map order).  frame None: the newest one that HAS LANDED (no wait; None when none has); a frame number: that frame, waited
+        for if it is still on its way; a frame that was never published or has been overwritten raises."""
+        if self.live is None:
+            return None
+        return self.live.snapshot(frame)
+
+    def live_trails(self, trj_len=150):
+        """getDynTracks (reference src/gui/GLScenePane.cpp:19-52; 150: GLScenePane.h:26) over the dynamic points of the last
+        live_view_trail_depth frames: [(id, positions newest first [n][3]), ...] in ascending id order.  Waits for the pose stream."""
+        if self.live is None:
+            return None
+        return self.live.trails(self.pose_s.cuda_stream, min(int(trj_len), self.cfg.live_view_trail_depth))
+
+    def live_stats(self):
+        """what the C++ loop's report says under "live_view": frames, frames published, the newest snapshot's counts, the trails
+        (drains the device first)"""
+        if self.live is None:
+            return None
+        self.torch.cuda.synchronize()
+        s, tr = self.live.snapshot(), self.live_trails()
+        out = dict(frames=self.live_frames, frames_published=self.live_published, trails=len(tr), longest_trail=max([len(p) for _, p in tr], default=0))
+        if s is not None:
+            out.update({k: s[k] for k in ("frame", "nCur", "nDyn", "curOverflow", "dynOverflow", "curOverflowTotal", "dynOverflowTotal", "nStatic", "nDynamic", "nStaticFeat", "nDynamicFeat")})
+        return out
 
     def grouping_stats(self):
         """what CoSLAM::cameraGrouping said over the frames it ran on (LoopConfig.camera_grouping; drains the device first).
@@ -819,6 +870,9 @@ class FrameLoop:
         # kernels -- measured 1978-1986 (behind the hand-back) / 1928-1934 (behind the gate) / 1894-1903 (behind the classification)
         # against 2173-2193 frames/s here, 2119-2123 behind the key-frame requests (profiles/r04_ab_runs.txt)
         self.dest_free[b].record(self.pose_s)
+        if self.live is not None:   # storeDynamicPoints + updateDisplayData: the end of the frame (CoSLAMThread.cpp:117-120), behind the
+            self._live_view(i, dst)   # tracker's release, which therefore does not move
+            self._mark(i, "live view")
         if cfg.keyframe_drives and cfg.keyframe_lag > 0 and self.kf:
             self._kf_lag_record(i, dst)
             self._kf_lag_act(i, dst)

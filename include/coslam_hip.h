@@ -772,6 +772,88 @@ int cs_camera_grouping_dev(int device, void* hip_stream, int nCams, const cs_gro
                            const int* d_listCount, int W, int H, int minOverlapNum, double minOverlapAreaRatio, double* d_vcosts, int* d_nShare,
                            double* d_hullArea, void* d_scratch, double initCamTranslation, double maxDistRatio, cs_camera_groups* d_groups);
 
+/* ---- live view: CoSLAM::getNumDynamicStaticPoints (src/app/SL_CoSLAM.cpp:1447-1471), CoSLAM::storeDynamicPoints (:1900-1911) and the
+ * display's getDynTracks (src/gui/GLScenePane.cpp:19-52) -------------------------------------------------------------------------------------
+ * The frame's last step (src/gui/CoSLAMThread.cpp:117-120, behind currentMapPointsRegister); DESIGN.md 3.18.  A map point TAKES PART when
+ * its row is below *d_mapCount (NULL: nMap) and d_pointFeat [nMap][nCams] (the hand-back's table: slot of the feature of THIS frame, or < 0)
+ * names a feature in at least one camera -- the loops' curMapPts.  False points take part (the reference keeps them on curMapPts until they
+ * lose their features, :1182-1197) and carry their flag.  d_mapFlags: CS_MAP_* bytes (NULL: all 0).  The id of a point is its map index.
+ *   counts    nStatic: points with flags == 0 (isCertainStatic), nDynamic: flags == CS_MAP_DYNAMIC exactly (isCertainDynamic); uncertain and
+ *             false points count in neither.  nStaticFeat[c] / nDynamicFeat[c]: the same, of the points camera c holds a feature of.
+ *   dynamic   {x, y, z, id} of every point with flags == CS_MAP_DYNAMIC, in map order, into slot (number of frame calls so far) % trailDepth
+ *             of a DEVICE ring, at most dynCap per frame, every frame.  One camera: the list is empty whatever the map holds (:1901-1902).
+ *   snapshot  on frames with frame % every == 0: a cs_live_header and the points that take part as cs_live_point records in map order, at
+ *             most curCap, into the next of `depth` slots of a ring in PINNED HOST memory, with stores from the kernel; an event per slot
+ *             says when it has landed.  A slot is sizeof(cs_live_header) + curCap * sizeof(cs_live_point) bytes, header first.
+ * Past a cap the first curCap / dynCap entries in map order are kept and the rest counted (curOverflow / dynOverflow); nothing is written
+ * past a cap.  One launch per frame, no host wait; integers and copied doubles only, so two calls over the same tables give the same bytes. */
+typedef struct {
+    int nStatic, nDynamic;                      /* m_nStatic, m_nDynamic */
+    int nStaticFeat[16], nDynamicFeat[16];      /* m_nStaticFeat[], m_nDynamicFeat[] */
+} cs_map_counts;
+typedef struct {
+    int frame, mapCount;          /* *d_mapCount, clamped to 0 .. nMap */
+    int nCur, nDyn;               /* records in this slot's list / entries in the frame's dynamic list (both after the caps) */
+    int curOverflow, dynOverflow; /* entries that did not fit */
+    int nCams, every;
+    cs_map_counts counts;
+    double R[16][9], t[16][3];    /* the frame's poses; cameras behind nCams: 0 */
+    cs_camera_groups groups;      /* the frame's record, or groupNum = 0 (all zero) when none was given */
+    int curOverflowTotal;         /* curOverflow summed over the frames published so far, this one included */
+    int dynOverflowTotal;         /* dynOverflow summed over ALL frames so far */
+    int reserved;                 /* (size a multiple of 8) */
+} cs_live_header;
+typedef struct {
+    double M[3];
+    int id;                       /* the map index */
+    unsigned short camMask;       /* bit c: camera c holds a feature of the point in this frame */
+    unsigned char flags;          /* CS_MAP_* */
+    unsigned char numVisCam;      /* the mask's bit count */
+} cs_live_point;                  /* 32 bytes */
+typedef struct {
+    double x, y, z;
+    int id, reserved;
+} cs_live_dyn;                    /* Point3dId; 32 bytes */
+typedef struct cs_liveview cs_liveview;
+/* nCams 1..16, curCap >= 1, dynCap >= 1, depth >= 2 snapshots, trailDepth >= 1 frames of dynamic lists, every >= 1.  NULL on failure. */
+cs_liveview* cs_liveview_create(int device, int nCams, int curCap, int dynCap, int depth, int trailDepth, int every);
+void cs_liveview_destroy(cs_liveview* v);
+/* One frame, enqueued on hip_stream; never waits.  Frames must increase; every call of one view goes to one stream (or to streams ordered
+ * one behind the other).  d_mapPts [nMap][3], d_R [nCams][9], d_t [nCams][3], d_groups: the frame's cs_camera_groups on the device or NULL.
+ * The view's staging rows are sized for 65536 map rows at creation; the first call with a larger nMap allocates (it waits, once). */
+int cs_liveview_frame_dev(cs_liveview* v, void* hip_stream, int frame, int nMap, const int* d_mapCount, const int* d_pointFeat,
+                          const unsigned char* d_mapFlags, const double* d_mapPts, const double* d_R, const double* d_t,
+                          const cs_camera_groups* d_groups);
+/* the newest published frame whose snapshot HAS LANDED on the host (an event query, never a wait), or -1 */
+int cs_liveview_newest(cs_liveview* v);
+/* Pointers into the pinned ring, valid until `depth` more snapshots have been published.  CS_ERR_INVALID for a frame that was never
+ * published or has been overwritten; blocks only while the frame is enqueued and has not landed. */
+int cs_liveview_fetch(cs_liveview* v, int frame, const cs_live_header** header, const cs_live_point** points);
+/* the pinned ring itself (depth slots of *slotBytes) and the device ring of dynamic lists: d_entries [trailDepth][dynCap],
+ * d_counts [trailDepth] (entries kept), d_frames [trailDepth] (the frame a slot holds, -1: none).  Any of the outputs may be NULL. */
+int cs_liveview_rings(cs_liveview* v, const unsigned char** h_ring, size_t* slotBytes, const cs_live_dyn** d_entries, const int** d_counts,
+                      const int** d_frames);
+/* The dynamic list of the frame `framesBack` calls before the newest (0: the newest), from the device ring to the host: m_dynPts[size - 1 -
+ * framesBack].  Waits for hip_stream (which must be ordered behind the frame calls).  At most maxEntries entries are copied; *count is the
+ * number the slot holds, *frame the frame it belongs to.  CS_ERR_INVALID when the ring does not hold that frame. */
+int cs_liveview_dyn_fetch(cs_liveview* v, void* hip_stream, int framesBack, int maxEntries, cs_live_dyn* h_entries, int* count, int* frame);
+/* getDynTracks(m_dynPts, dynTracks, trjLen) over the device ring as it stands behind the calls enqueued so far (hip_stream must be ordered
+ * behind them: the same stream, or an event).  For every id of the NEWEST stored frame a trail, newest first: the id's position in each of
+ * the last min(trjLen, frames stored) frames whose list holds it -- a frame without it is skipped, it does not end the trail.  Ids that are
+ * not in the newest frame get no trail; trjLen == 0 or an empty ring: no trails.  Trails come in ascending id order (the reference's
+ * std::map).  trjLen > trailDepth: CS_ERR_INVALID.  The _dev form enqueues one launch and writes d_nTrails [1], d_trailId [dynCap],
+ * d_trailLen [dynCap], d_trailPts [dynCap][trjLen][3] (device or pinned memory; entries behind a trail's length are left as they were).
+ * The host form waits for hip_stream and fills at most maxTrails trails: h_trailPts [maxTrails][trjLen][3]; *nTrails is the number there are. */
+int cs_liveview_trails_dev(cs_liveview* v, void* hip_stream, int trjLen, int* d_nTrails, int* d_trailId, int* d_trailLen, double* d_trailPts);
+int cs_liveview_trails(cs_liveview* v, void* hip_stream, int trjLen, int maxTrails, int* nTrails, int* h_trailId, int* h_trailLen,
+                       double* h_trailPts);
+/* getNumDynamicStaticPoints alone, where the reference has it (the first line of genNewMapPoints, :1296): the frame kernel in a counts-only
+ * mode, one launch, into d_counts (device memory).  d_scratch: cs_map_counts_scratch_bytes() bytes of device memory, ZEROED ONCE by the
+ * caller (every call leaves them zeroed); calls that share a scratch must be ordered. */
+size_t cs_map_counts_scratch_bytes(void);
+int cs_map_counts_dev(int device, void* hip_stream, int nCams, int nMap, const int* d_mapCount, const int* d_pointFeat,
+                      const unsigned char* d_mapFlags, cs_map_counts* d_counts, void* d_scratch);
+
 /* ---- MapPoint::pFeatures as the reference holds them: feature references (round 5; VERDICT r04 missing 3) ---------------------------------
  * p->pFeatures[c] is the feature of this frame while camera c tracks the point -- and STAYS what it last was when the camera loses it
  * (nothing clears the pointer): updateStaticPointPosition / updateDynamicPointPosition (src/slam/SL_CoSLAMHelper.cpp:338-394, 455-484),

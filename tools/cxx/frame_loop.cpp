@@ -13,7 +13,9 @@
 // whole-run archive behind the pose history, in frames: cs_track_history_set_archive); COSLAM_HIST_STORE (frames of pixels + poses the pose
 // history keeps: 4096, as LoopConfig.hist_store); COSLAM_CAMERA_GROUPING=1 (CoSLAM::cameraGrouping per frame behind the pose update, reported
 // under "camera_grouping": cs_camera_grouping_dev) with COSLAM_GROUP_MIN_OVERLAP_NUM (0), COSLAM_GROUP_MIN_AREA_RATIO (0.0),
-// COSLAM_GROUP_MAX_DIST_RATIO (6.0).
+// COSLAM_GROUP_MAX_DIST_RATIO (6.0); COSLAM_LIVE_VIEW=1 (the frame's last step, cs_liveview_frame_dev: the counts, the dynamic points and
+// every COSLAM_LIVE_VIEW_EVERY-th (1) frame a snapshot, reported under "live_view") with COSLAM_LIVE_VIEW_DEPTH (8), COSLAM_LIVE_VIEW_TRAIL_DEPTH
+// (150), COSLAM_LIVE_VIEW_CUR_CAP / COSLAM_LIVE_VIEW_DYN_CAP (0: the map's capacity / a quarter of it).
 // Per frame (reference call sites in bench.py's docstring): camera-group redetect (+ prefetch of the next frame's front) on the
 // tracker stream; hand-back + intraCamEstimate of all cameras + both registration passes on the pose stream, event-ordered
 // behind the tracker; at key frames the inter-camera solve and the joint local BA (parsed on the device from the window ring) on their
@@ -121,6 +123,8 @@ struct Options {
     bool grouping;           // COSLAM_CAMERA_GROUPING=1 (see FrameLoop::camera_grouping)
     int groupMinNum;         // getViewOverlapCosts(viewOverlapCost, 0, 0.0), src/app/SL_CoSLAM.cpp:1635
     double groupMinAreaRatio, groupMaxDistRatio;   // Param::maxDistRatio = 6.0 (src/app/SL_GlobParam.cpp:18)
+    bool liveView;           // COSLAM_LIVE_VIEW=1 (see FrameLoop::live_view)
+    int liveEvery, liveDepth, liveTrailDepth, liveCurCap, liveDynCap;
 };
 
 static Options read_options(int argc, char** argv) {
@@ -158,6 +162,12 @@ static Options read_options(int argc, char** argv) {
     o.groupMinAreaRatio = gar && gar[0] ? atof(gar) : 0.0;
     const char* gdr = getenv("COSLAM_GROUP_MAX_DIST_RATIO");
     o.groupMaxDistRatio = gdr && gdr[0] ? atof(gdr) : 6.0;
+    o.liveView = flag("COSLAM_LIVE_VIEW", '1');
+    o.liveEvery = std::max(1, envi("COSLAM_LIVE_VIEW_EVERY", 1));
+    o.liveDepth = std::max(2, envi("COSLAM_LIVE_VIEW_DEPTH", 8));
+    o.liveTrailDepth = std::max(1, envi("COSLAM_LIVE_VIEW_TRAIL_DEPTH", 150));   // (150: the display's m_nTrjLen, src/gui/GLScenePane.h:26)
+    o.liveCurCap = std::max(0, envi("COSLAM_LIVE_VIEW_CUR_CAP", 0));
+    o.liveDynCap = std::max(0, envi("COSLAM_LIVE_VIEW_DYN_CAP", 0));
     return o;
 }
 
@@ -436,6 +446,9 @@ struct FrameLoop {
     bool grpHaveLast = false;
     cs_camera_groups grpLast;
     std::vector<double> grpLastCosts;
+    // the frame's last step (COSLAM_LIVE_VIEW=1): storeDynamicPoints + the display's copy, one launch per frame on the pose stream, no wait
+    cs_liveview* live = nullptr;
+    int liveFrames = 0, livePublished = 0;
     // drain
     int* dBar;
     int nEmptySolves = 0;
@@ -468,6 +481,8 @@ struct FrameLoop {
     void camera_grouping(int i, int dsti);
     void grouping_take(int n, bool synced);
     std::string grouping_json();
+    void live_view(int i, int dsti);
+    std::string live_json();
     void run(int n) {
         for (int q = 0; q < n; ++q, ++nDone) step(nDone + 1, keyEvery > 0 && nDone % keyEvery == 0);
     }
@@ -869,6 +884,46 @@ std::string FrameLoop::grouping_json() {
     return s + "], \"init_cam_translation\": " + buf + "}";
 }
 
+// CoSLAM::storeDynamicPoints + updateDisplayData of frame i where the reference has them (src/gui/CoSLAMThread.cpp:117-120): the tables as
+// the registration left them, the poses just written, the frame's groups when the grouping runs
+void FrameLoop::live_view(int i, int dsti) {
+    const cs_camera_groups* g = o.grouping && grpCalls ? dGrpGroups + (int)((grpCalls - 1) % GROUP_RING) : nullptr;
+    CSCHK(cs_liveview_frame_dev(live, (void*)poseS, i, nMap, dMapCount, dPf, dMapFlags, dMap, dR[dsti], dT[dsti], g));
+    ++liveFrames;
+    livePublished += i % o.liveEvery == 0;
+}
+
+// (behind the barrier) the newest snapshot's header and getDynTracks over the ring, as FrameLoop.live_stats of the Python loop
+std::string FrameLoop::live_json() {
+    if (!o.liveView) return "";
+    const int dynCap = o.liveDynCap ? o.liveDynCap : std::max(1, nMap / 4);
+    int nTr = 0, longest = 0;
+    std::vector<int> ids(dynCap), lens(dynCap);
+    std::vector<double> pts((size_t)dynCap * o.liveTrailDepth * 3);
+    CSCHK(cs_liveview_trails(live, (void*)poseS, o.liveTrailDepth, dynCap, &nTr, ids.data(), lens.data(), pts.data()));
+    for (int q = 0; q < nTr && q < dynCap; ++q) longest = std::max(longest, lens[q]);
+    std::string s = "\"live_view\": {\"frames\": " + std::to_string(liveFrames) + ", \"frames_published\": " + std::to_string(livePublished) +
+                    ", \"trails\": " + std::to_string(nTr) + ", \"longest_trail\": " + std::to_string(longest);
+    const int newest = cs_liveview_newest(live);
+    if (newest >= 0) {
+        const cs_live_header* h = nullptr;
+        const cs_live_point* p = nullptr;
+        CSCHK(cs_liveview_fetch(live, newest, &h, &p));
+        auto arr = [&](const int* a) {
+            std::string r = "[";
+            for (int c = 0; c < nCams; ++c) r += (c ? ", " : "") + std::to_string(a[c]);
+            return r + "]";
+        };
+        s += ", \"frame\": " + std::to_string(h->frame) + ", \"nCur\": " + std::to_string(h->nCur) + ", \"nDyn\": " + std::to_string(h->nDyn) +
+             ", \"curOverflow\": " + std::to_string(h->curOverflow) + ", \"dynOverflow\": " + std::to_string(h->dynOverflow) +
+             ", \"curOverflowTotal\": " + std::to_string(h->curOverflowTotal) + ", \"dynOverflowTotal\": " + std::to_string(h->dynOverflowTotal) +
+             ", \"nStatic\": " + std::to_string(h->counts.nStatic) + ", \"nDynamic\": " + std::to_string(h->counts.nDynamic) +
+             ", \"nStaticFeat\": " + arr(h->counts.nStaticFeat) + ", \"nDynamicFeat\": " + arr(h->counts.nDynamicFeat) +
+             ", \"bytes_per_published_frame\": " + std::to_string(sizeof(cs_live_header) + sizeof(cs_live_point) * (size_t)h->nCur);
+    }
+    return s + "}, ";
+}
+
 // first frame: detect, map association, first hand-back (GPUKLT::first + map initialisation stand-in)
 void FrameLoop::first_frame() {
     for (int b = 0; b < 2; ++b) {
@@ -912,6 +967,14 @@ void FrameLoop::first_frame() {
         HIPCHK(hipMemcpy(dKfSelfT, dT[0], sizeof(double) * 3 * nCams, hipMemcpyDeviceToDevice));
     }
     if (o.grouping) setup_camera_grouping();
+    if (o.liveView) {
+        live = cs_liveview_create(o.dev, nCams, o.liveCurCap ? o.liveCurCap : nMap, o.liveDynCap ? o.liveDynCap : std::max(1, nMap / 4), o.liveDepth,
+                                  o.liveTrailDepth, o.liveEvery);
+        if (!live) {
+            fprintf(stderr, "cs_liveview_create: %s\n", cs_last_error());
+            exit(2);
+        }
+    }
 }
 
 // every tracked slot of the first frame onto the nearest projected map point within 1 px
@@ -981,6 +1044,7 @@ void FrameLoop::step(int i, bool key) {
     // the tracker of frame i + 2 is released at the END of the frame's pose work (released right behind the hand-back it runs two frames
     // ahead and under more of the pose stream's kernels: -10 %, profiles/r04_ab_runs.txt)
     HIPCHK(hipEventRecord(destFree[b], poseS));
+    if (o.liveView) live_view(i, dsti);   // storeDynamicPoints + updateDisplayData: the end of the frame, behind the tracker's release
     if (o.kfDrives)
         keyframe_decision_step(i, dsti);
     else if (key)
@@ -1208,7 +1272,7 @@ void FrameLoop::report(double dt, double dtHost, int applied0, const int rvCnt0[
     int decUnsettled = 0;   // (the decision scratch's last int: sticky "some call's sweeps did not settle")
     HIPCHK(hipMemcpy(&decUnsettled, (char*)dDecScratch + cs_register_decide_scratch_bytes(nCams, N, nMap) - sizeof(int), sizeof(int),
                      hipMemcpyDeviceToHost));
-    const std::string groupingJson = grouping_json();
+    const std::string groupingJson = grouping_json(), liveJson = live_json();
     const char* transport = o.world == 1 ? "none" : o.hostSegment ? "host segment (test)" : "rccl";
     printf("{\"frames_per_s\": %.3f, \"ms_per_step\": %.5f, \"steps\": %d, \"warmup\": %d, \"host_enqueue_ms_per_step\": %.5f, "
            "\"cams_per_tracker_launch\": %d, \"pose_ok\": %s, \"min_live_features\": %d, \"joint_lm_steps\": %d, \"joint_cost\": %.6f, "
@@ -1218,12 +1282,12 @@ void FrameLoop::report(double dt, double dtHost, int applied0, const int rvCnt0[
            "\"map_capacity\": %d, \"new_map_points_last_run\": %d, \"register_decisions_unsettled\": %s, \"bmerge_frames\": %d, \"current_points_beyond_the_cap\": %d, \"second_visit_rounds\": %d, \"second_visit_features_attached\": %d, "
            "\"second_visit_conflicts\": %d, \"second_visit_conflicts_in_timed_region\": %d, \"second_visit_points_beyond_the_list\": %d, "
            "\"key_frames_placed_by_the_decision\": %s, \"keyframe_lag\": %d, \"frames_run\": %d, \"windows_requested\": %lld, \"windows_applied\": %d, \"windows_not_applied_history_too_short\": %d, "
-           "\"camera_grouping\": %s, \"rank\": %d, \"world\": %d, \"cameras_per_rank\": %d, \"transport\": \"%s\", \"digest\": \"%016llx\"}\n",
+           "\"camera_grouping\": %s, %s\"rank\": %d, \"world\": %d, \"cameras_per_rank\": %d, \"transport\": \"%s\", \"digest\": \"%016llx\"}\n",
            steps / dt, dt / steps * 1e3, steps, o.warmup, dtHost / steps * 1e3, w.camsPerLaunch, okAll ? "true" : "false", minLive,
            sj.nIterTotal, sj.cost, si.nIterTotal, si.cost, nccRuns, jC, jP, jO, o.baLag, sched.nApplied - applied0,
            cs_ba_output_wait_errors(bout), iS, iP - iS, w.nPts, mapCountNow, nMap, npCounts[0], decUnsettled ? "true" : "false", nMergeFrames, curOverflow,
            RV_ROUNDS, rvCnt[0], rvCnt[2], rvCnt[2] - rvCnt0[2], rvListCnt[1], o.kfDrives ? placedJson.c_str() : "null", o.kfDrives ? o.kfLag : 0, nDone,
-           sched.nRequested, sched.nApplied, sched.nNotApplied, groupingJson.c_str(), o.rank, o.world, nc, transport, digest);
+           sched.nRequested, sched.nApplied, sched.nNotApplied, groupingJson.c_str(), liveJson.c_str(), o.rank, o.world, nc, transport, digest);
     fflush(stdout);
 }
 
