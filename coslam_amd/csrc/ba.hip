@@ -2235,6 +2235,22 @@ static int ba_run_followup(cs_ba* b, hipStream_t s) {
     return rc;
 }
 
+// one of the workspace's own allocations (pairPtr, pairEnt, waveStart, cholBuf, syrkBuf) again with room for n elements: the old
+// block is freed first (its contents are rebuilt by whoever grows it); a caller whose graphs bake the address in drops them
+template <class T>
+static int ba_regrow(T** buf, size_t* cap, size_t n, int failCode, const char* what) {
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    if (hipMalloc((void**)buf, sizeof(T) * n) != hipSuccess) {
+        *buf = nullptr;
+        cs_set_error("cs_ba: cannot allocate %zu KB for %s", (sizeof(T) * n) >> 10, what);
+        return failCode;
+    }
+    *cap = n;
+    return CS_OK;
+}
+
 static void ba_worker_drop_graphs(cs_ba* b);
 static void ba_drop_graph(cs_ba* b) {
     // (callers on the API thread have drained the worker's queue -- cs_ba_wait -- before they get here; the worker itself gets
@@ -2480,14 +2496,8 @@ static int ba_make_plan(cs_ba* b, int C, int P, int nObs, int nCamsCon, int nPts
                          bF = pad(sizeof(int) * 2 * (size_t)NB);
             const size_t need = bPub + bX + bF;
             if (need > b->cholCap) {
-                if (b->cholBuf) (void)hipFree(b->cholBuf);
-                b->cholBuf = nullptr;
-                b->cholCap = 0;
-                if (hipMalloc((void**)&b->cholBuf, need) != hipSuccess) {
-                    cs_set_error("cs_ba: cannot allocate %zu KB for the Cholesky columns", need >> 10);
-                    return CS_ERR_ALLOC;
-                }
-                b->cholCap = need;
+                const int rc = ba_regrow(&b->cholBuf, &b->cholCap, need, CS_ERR_ALLOC, "the Cholesky columns");
+                if (rc) return rc;
                 ba_drop_graph(b);
             }
             L.F.pub = (double*)b->cholBuf;
@@ -2525,14 +2535,8 @@ static int ba_make_plan(cs_ba* b, int C, int P, int nObs, int nCamsCon, int nPts
                          bC = pad(sizeof(double) * (size_t)sl * Y.nTiles * SY_TB * SY_TB), bU = pad(sizeof(double) * 33 * SY_US * (size_t)D.nc);
             const size_t need = bZt + bT + bC + bU;
             if (need > b->syrkCap) {
-                if (b->syrkBuf) (void)hipFree(b->syrkBuf);
-                b->syrkBuf = nullptr;
-                b->syrkCap = 0;
-                if (hipMalloc((void**)&b->syrkBuf, need) != hipSuccess) {
-                    cs_set_error("cs_ba: cannot allocate %zu MB for the Schur contraction", need >> 20);
-                    return CS_ERR_ALLOC;
-                }
-                b->syrkCap = need;
+                const int rc = ba_regrow(&b->syrkBuf, &b->syrkCap, need, CS_ERR_ALLOC, "the Schur contraction");
+                if (rc) return rc;
                 ba_drop_graph(b);  // captured graphs hold the old addresses
             }
             Y.Zt = (double*)b->syrkBuf;
@@ -2619,6 +2623,13 @@ static void ba_enqueue_lin_schur(hipStream_t stream, const BaPlan& L) {
     }
 }
 
+// the update of a sliced order N (the register Cholesky is part of it): eight lanes per point or a wave per point
+template <int N>
+static void ba_launch_update_sliced(hipStream_t stream, const BaPlan& L) {
+    void (*const kernel)(BaDev) = L.seg8 ? k_update_seg8<N> : k_update<N>;
+    hipLaunchKernelGGL(kernel, dim3(L.gUpd), dim3(256), 0, stream, L.D);
+}
+
 // solve of the reduced system + tentative step + its cost
 static void ba_enqueue_solve_update(hipStream_t stream, const BaPlan& L) {
     const BaDev& D = L.D;
@@ -2629,27 +2640,15 @@ static void ba_enqueue_solve_update(hipStream_t stream, const BaPlan& L) {
         hipLaunchKernelGGL(k_update_packed, dim3(L.gPack), blk, 0, stream, L.DB);
         return;
     }
-    if (L.seg8) {
+    if (L.sliced) {  // + solve + tentative cost (a sliced order is one of 6, 12 .. 36)
         switch (D.n) {
-            case 6: hipLaunchKernelGGL(k_update_seg8<6>, dim3(gUpd), blk, 0, stream, D); break;
-            case 12: hipLaunchKernelGGL(k_update_seg8<12>, dim3(gUpd), blk, 0, stream, D); break;
-            case 18: hipLaunchKernelGGL(k_update_seg8<18>, dim3(gUpd), blk, 0, stream, D); break;
-            case 24: hipLaunchKernelGGL(k_update_seg8<24>, dim3(gUpd), blk, 0, stream, D); break;
-            case 30: hipLaunchKernelGGL(k_update_seg8<30>, dim3(gUpd), blk, 0, stream, D); break;
-            default: hipLaunchKernelGGL(k_update_seg8<36>, dim3(gUpd), blk, 0, stream, D); break;
+            case 6: ba_launch_update_sliced<6>(stream, L); break;
+            case 12: ba_launch_update_sliced<12>(stream, L); break;
+            case 18: ba_launch_update_sliced<18>(stream, L); break;
+            case 24: ba_launch_update_sliced<24>(stream, L); break;
+            case 30: ba_launch_update_sliced<30>(stream, L); break;
+            default: ba_launch_update_sliced<36>(stream, L); break;
         }
-    } else if (L.sliced && D.n == 6) {
-        hipLaunchKernelGGL(k_update<6>, dim3(gUpd), blk, 0, stream, D);  // + solve + tentative cost
-    } else if (L.sliced && D.n == 12) {
-        hipLaunchKernelGGL(k_update<12>, dim3(gUpd), blk, 0, stream, D);
-    } else if (L.sliced && D.n == 18) {
-        hipLaunchKernelGGL(k_update<18>, dim3(gUpd), blk, 0, stream, D);
-    } else if (L.sliced && D.n == 24) {
-        hipLaunchKernelGGL(k_update<24>, dim3(gUpd), blk, 0, stream, D);
-    } else if (L.sliced && D.n == 30) {
-        hipLaunchKernelGGL(k_update<30>, dim3(gUpd), blk, 0, stream, D);
-    } else if (L.sliced && D.n == 36) {
-        hipLaunchKernelGGL(k_update<36>, dim3(gUpd), blk, 0, stream, D);
     } else {
         if (D.n <= SB_MAX_ORDER) {
             sb_launch_solve(stream, D);
@@ -2694,6 +2693,44 @@ static void ba_enqueue_lm_run(hipStream_t stream, const BaPlan& L, int steps) {
     ba_enqueue_control_final(stream, L);
 }
 
+// The schedule of a robust solve is head, then per round [round start, chunks of LM steps, tail], then finish.  This is the one
+// body of every segment kind: every entry point puts these on its stream, directly or through a captured graph.
+//   'H'ead: the start estimate (init, null = already in the workspace) + the first round's start
+//   'R'ound start: cost + LM state          'C'hunk: up to `chunk` LM steps
+//   'T'ail: outlier flags + round end       'F'inish: final cost + statistics
+// A chunk and a tail end with the copy of {inner_done, all_done} into stateTo (pinned); null: nobody reads the word between
+// segments, or the segment's last kernel stores it itself (ba_state_in_kernel).
+struct BaHeadInit {
+    bool rebuildTopology;
+    const double *Rs0, *Ts0, *pts0;
+};
+static void ba_enqueue_segment(cs_ba* b, hipStream_t s, const BaPlan& L, char kind, int chunk, int* stateTo,
+                               const BaHeadInit& init = {false, nullptr, nullptr, nullptr}) {
+    const BaDev& D = L.D;
+    const dim3 blk(256);
+    switch (kind) {
+        case 'H':
+            ba_enqueue_init(b, s, L, init.rebuildTopology, init.Rs0, init.Ts0, init.pts0);
+            [[fallthrough]];
+        case 'R':
+            hipLaunchKernelGGL(k_cost, dim3(L.cb), blk, 0, s, D, 0);
+            hipLaunchKernelGGL(k_control, dim3(1), blk, 0, s, D);
+            return;
+        case 'C':
+            ba_enqueue_lm_run(s, L, chunk);  // (the state word is exact at every chunk boundary)
+            break;
+        case 'T':
+            hipLaunchKernelGGL(k_flag, dim3(L.cb), blk, 0, s, D);  // (its counters were zeroed by k_control phase 0)
+            hipLaunchKernelGGL(k_outer_end, dim3(1), dim3(1), 0, s, D);
+            break;
+        default:
+            hipLaunchKernelGGL(k_cost_force, dim3(L.cb), blk, 0, s, D);
+            hipLaunchKernelGGL(k_finish, dim3(1), blk, 0, s, D, b->stats);
+            return;
+    }
+    if (stateTo) (void)hipMemcpyAsync(stateTo, &b->st->inner_done, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
+}
+
 // enqueue the whole solve on `stream`; every array already resident in b's device buffers
 static int ba_enqueue(cs_ba* b, hipStream_t stream, int C, int P, int nObs, int nCamsCon, int nPtsCon, double maxErr,
                       int maxIter, int innerMaxIter, bool rebuildTopology = true, const double* d_Rs0 = nullptr,
@@ -2701,20 +2738,14 @@ static int ba_enqueue(cs_ba* b, hipStream_t stream, int C, int P, int nObs, int 
     BaPlan L;
     int rc = ba_make_plan(b, C, P, nObs, nCamsCon, nPtsCon, maxErr, innerMaxIter, false, &L);
     if (rc) return rc;
-    const BaDev& D = L.D;
-    const int cb = L.cb;
-    const dim3 blk(256);
+    // (the head without its round start: a solve of no rounds -- cs_ba_upload -- launches neither k_cost nor k_control)
     ba_enqueue_init(b, stream, L, rebuildTopology, d_Rs0, d_Ts0, d_pts0);
-
     for (int outer = 0; outer < maxIter; ++outer) {
-        hipLaunchKernelGGL(k_cost, dim3(cb), blk, 0, stream, D, 0);
-        hipLaunchKernelGGL(k_control, dim3(1), blk, 0, stream, D);
-        ba_enqueue_lm_run(stream, L, innerMaxIter);
-        hipLaunchKernelGGL(k_flag, dim3(cb), blk, 0, stream, D);  // (its counters were zeroed by k_control phase 0)
-        hipLaunchKernelGGL(k_outer_end, dim3(1), dim3(1), 0, stream, D);
+        ba_enqueue_segment(b, stream, L, 'R', 0, nullptr);
+        ba_enqueue_segment(b, stream, L, 'C', innerMaxIter, nullptr);
+        ba_enqueue_segment(b, stream, L, 'T', 0, nullptr);
     }
-    hipLaunchKernelGGL(k_cost_force, dim3(cb), blk, 0, stream, D);
-    hipLaunchKernelGGL(k_finish, dim3(1), blk, 0, stream, D, b->stats);
+    ba_enqueue_segment(b, stream, L, 'F', 0, nullptr);
     CS_CHECK_LAUNCH();
     return CS_OK;
 }
@@ -2889,6 +2920,128 @@ static int ba_run_segments(BaWorker* w, hipStream_t s, int maxIter, int innerMax
     return CS_OK;
 }
 
+// LM steps per chunk segment: `steps`, at most a round's
+static void ba_worker_set_chunk(BaWorker* w, int steps, int innerMaxIter) {
+    w->chunk = steps;
+    if (w->chunk > innerMaxIter && innerMaxIter > 0) w->chunk = innerMaxIter;
+    if (w->chunk < 1) w->chunk = 1;
+}
+
+// the segments' kernels enqueued directly (a problem built on the device: the sizes change with every request, no graph to replay);
+// the estimate already in Rs / Ts / pts is the start
+static int ba_run_segments_direct(cs_ba* b, BaWorker* w, hipStream_t s, BaPlan& L, const BaAsyncJob& J, int chunkSteps) {
+    ba_worker_set_chunk(w, chunkSteps, J.innerMaxIter);
+    int* const stateTo = ba_state_in_kernel(w, L) ? nullptr : w->h_state;
+    return ba_run_segments(w, s, J.maxIter, J.innerMaxIter, [&](char kind) {
+        ba_enqueue_segment(b, s, L, kind, w->chunk, stateTo);
+        return hipGetLastError();
+    });
+}
+
+// Every worker job starts here: the workspace's device and stream, behind the work the request waits for, without graphs another
+// thread has invalidated.  resC > 0 (a problem built on the device): the workspace for up to (resC, resP, resObs), bound at its
+// capacity -- no whole-solve graph survives that.
+static int ba_worker_begin(cs_ba* b, BaWorker* w, const BaAsyncJob& J, int resC = 0, int resP = 0, int resObs = 0) {
+    CS_HIP(hipSetDevice(b->device));
+    CS_HIP(hipStreamWaitEvent(b->own_stream, J.ready, 0));
+    {
+        std::lock_guard<std::mutex> lk(w->mu);
+        if (w->stale) {
+            ba_worker_destroy_graphs(w);
+            w->stale = false;
+        }
+    }
+    if (resC <= 0) return CS_OK;
+    const int rc = ba_reserve(b, resC, resP, resObs);
+    if (rc) return rc;
+    ba_bind_io(b, b->capC, b->capP, b->capObs);
+    ba_drop_graph(b);
+    return CS_OK;
+}
+
+// Lane plan of the packed kernels (ba_packed_dev.h): whole points back to back, at most 64 measurements per wave, in point order --
+// a wave is then a contiguous range of the measurement arrays.  ws (P + 2 ints) receives the first measurement of every wave and
+// nObs behind the last; returns the number of entries (waves + 1).  Not for a point with more than 64 measurements.
+static int ba_lane_plan(const int* obs_ptr, int P, int nObs, int* ws) {
+    int nw = 0, fill = 0;
+    ws[nw++] = 0;
+    for (int i = 0; i < P; ++i) {
+        const int k = obs_ptr[i + 1] - obs_ptr[i];
+        if (k == 0) continue;
+        if (fill + k > 64) {
+            ws[nw++] = obs_ptr[i];
+            fill = 0;
+        }
+        fill += k;
+    }
+    ws[nw++] = nObs;
+    return nw;
+}
+
+// ---- the topology of a problem that was built on the device -----------------------------------------------------------------
+// obs_ptr / obs_cam / obs_pt / obs_of are in the workspace and `totals` {P, nObs, largest measurement count of a point, static
+// points} on the device; the host knows only C.  This builds what cs_ba_upload builds on the host -- the camera lists of the small
+// orders, the camera-pair lists, the lane plan -- with ONE round trip for the sizes.
+struct BaTopoSrc {
+    const char* who;         // the entry point, for error messages
+    const int* totals;       // device
+    int *pairCnt, *pairTotal;  // device scratch: C (C + 1) / 2 + 1 counts, their sum
+    int *h_totals, *h_plan;  // pinned: [8 + nPtr] totals | pair total | obs_ptr, [nPtr + 1] the lane plan on its way to the device
+    size_t nPtr;             // obs_ptr entries read back: 1 + the most points the builder can produce
+    bool camLists;
+};
+struct BaTopoSizes {
+    int P, nObs, maxObs, nStatic;
+};
+// afterSync(sizes): called right behind the round trip -- the builder's inputs have been read -- and refuses a problem it cannot
+// solve; entCap(nEnt): the pair-entry capacity to allocate when nEnt entries do not fit.
+template <class AfterSync, class EntCap>
+static int ba_device_topology(cs_ba* b, BaWorker* w, hipStream_t s, int C, const BaTopoSrc& T, BaTopoSizes* out, AfterSync&& afterSync,
+                              EntCap&& entCap) {
+    if (T.camLists)   // (the small-order solver's Schur kernels walk camera-indexed lists)
+        hipLaunchKernelGGL(k_cam_lists, dim3(1), dim3(1024), 0, s, C, T.totals, b->obs_cam, b->cam_ptr, b->cam_obs);
+    // the camera-pair lists' sizes, still without the host knowing P (one wave per pair; P read on the device)
+    const int nPairsAll = C * (C + 1) / 2;
+    int rc = CS_OK;
+    if ((size_t)nPairsAll + 1 > b->pairPtrCap) rc = ba_regrow(&b->pairPtr, &b->pairPtrCap, (size_t)nPairsAll + 1, CS_ERR_HIP, "the camera-pair index");
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_pairs_count, dim3(nPairsAll), dim3(64), 0, s, C, T.totals, b->obs_of, T.pairCnt);
+    hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(1024), 0, s, nPairsAll, T.pairCnt, b->pairPtr, T.pairTotal);
+    // ONE round trip: the sizes (launch dimensions of everything that follows), the pair total, obs_ptr for the lane plan
+    CS_HIP(hipMemcpyAsync(T.h_totals, T.totals, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+    CS_HIP(hipMemcpyAsync(T.h_totals + 4, T.pairTotal, sizeof(int), hipMemcpyDeviceToHost, s));
+    const int* h_optr = T.h_totals + 8;
+    CS_HIP(hipMemcpyAsync(T.h_totals + 8, b->obs_ptr, sizeof(int) * T.nPtr, hipMemcpyDeviceToHost, s));
+    if (w->tmEv[2]) {
+        (void)hipEventRecord(w->tmEv[2], s);
+        w->parseStamped = true;
+    }
+    CS_HIP(hipStreamSynchronize(s));  // (this is the worker thread: the frame loop does not wait)
+    *out = {T.h_totals[0], T.h_totals[1], T.h_totals[2], T.h_totals[3]};
+    rc = afterSync(*out);
+    b->maxObs = out->maxObs;
+    b->havePairs = false;
+    if (rc) return rc;
+    b->nPackWaves = 0;
+    if (b->maxObs <= 64) {
+        if (T.nPtr + 1 > b->waveStartCap) rc = ba_regrow(&b->waveStart, &b->waveStartCap, T.nPtr + 1, CS_ERR_HIP, "the lane plan");
+        if (rc) return rc;
+        const int nw = ba_lane_plan(h_optr, out->P, out->nObs, T.h_plan);
+        CS_HIP(hipMemcpyAsync(b->waveStart, T.h_plan, sizeof(int) * nw, hipMemcpyHostToDevice, s));  // (h_plan is pinned and outlives the copy)
+        b->nPackWaves = nw - 1;
+    }
+    const size_t nEnt = (size_t)T.h_totals[4];
+    if (nEnt == 0 || nEnt > ((size_t)8 << 20)) {  // (the camera-indexed lists k_schur would need are not built on the device)
+        cs_set_error("%s: %zu camera-pair entries, where the lists built on the device hold 1 .. 8 M", T.who, nEnt);
+        return CS_ERR_INVALID;
+    }
+    if (nEnt > b->pairEntCap) rc = ba_regrow(&b->pairEnt, &b->pairEntCap, entCap(nEnt), CS_ERR_HIP, "the camera-pair lists");
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_pairs_fill, dim3(nPairsAll), dim3(64), 0, s, C, out->P, b->obs_of, b->pairPtr, b->pairEnt);
+    b->havePairs = true;
+    return CS_OK;
+}
+
 // The ring holds WIN_SLACK key frames more than a window: a request's window (its slots are fixed when the solve is REQUESTED)
 // stays intact while up to WIN_SLACK newer key frames are pushed -- the frame loop's thread may run that far ahead of the
 // worker's parse; one further push waits (on the host) for the oldest outstanding parse.
@@ -2988,16 +3141,6 @@ static int ba_worker_run_window(cs_ba* b, BaWorker* w, const BaAsyncJob& J) {
 }
 static int ba_worker_run_window_inner(cs_ba* b, BaWorker* w, const BaAsyncJob& J, bool* packed) {
     cs_ba_window* win = J.win;
-    CS_HIP(hipSetDevice(b->device));
-    hipStream_t s = b->own_stream;
-    CS_HIP(hipStreamWaitEvent(s, J.ready, 0));
-    {
-        std::lock_guard<std::mutex> lk(w->mu);
-        if (w->stale) {
-            ba_worker_destroy_graphs(w);
-            w->stale = false;
-        }
-    }
     struct ParseDone {   // whatever way this function is left: the ring is free for the pushes that wait for this parse
         cs_ba_window* w;
         long long newest;
@@ -3024,10 +3167,9 @@ static int ba_worker_run_window_inner(cs_ba* b, BaWorker* w, const BaAsyncJob& J
     }
     const int C = J.winCount * win->nCams;
     // the workspace for the largest problem this window can produce: every slot of every key camera a measurement
-    int rc = ba_reserve(b, win->nKf * win->nCams, win->nMap, win->nKf * win->nCams * win->N);
+    int rc = ba_worker_begin(b, w, J, win->nKf * win->nCams, win->nMap, win->nKf * win->nCams * win->N);
     if (rc) return rc;
-    ba_bind_io(b, b->capC, b->capP, b->capObs);
-    ba_drop_graph(b);
+    hipStream_t s = b->own_stream;
     WinDev Wd;
     memset(&Wd, 0, sizeof(Wd));
     Wd.nCams = win->nCams, Wd.nKf = win->nKf, Wd.N = win->N, Wd.nMap = win->nMap, Wd.count = J.winCount;
@@ -3041,127 +3183,37 @@ static int ba_worker_run_window_inner(cs_ba* b, BaWorker* w, const BaAsyncJob& J
     WinFillOut O = {b->Ks, b->Rs, b->Ts, b->pts, b->obs_xy, b->obs_ptr, b->obs_cam, win->pointMap, b->obs_pt, b->obs_of};
     const int gF = (win->nMap + 3) / 4 > (C + 255) / 256 ? (win->nMap + 3) / 4 : (C + 255) / 256;   // a wave per map point; a thread per key camera
     hipLaunchKernelGGL(k_win_fill, dim3(gF), dim3(256), 0, s, Wd, O);
-    if (6 * (C - J.nCamsCon) <= 36 && C <= 256)   // (the small-order solver's Schur kernels walk camera-indexed lists)
-        hipLaunchKernelGGL(k_cam_lists, dim3(1), dim3(1024), 0, s, C, win->totals, b->obs_cam, b->cam_ptr, b->cam_obs);
-    // the camera-pair lists' sizes, still without the host knowing P (one wave per pair; P read on the device)
-    const int nPairsAll = C * (C + 1) / 2;
-    if ((size_t)nPairsAll + 1 > b->pairPtrCap) {
-        if (b->pairPtr) (void)hipFree(b->pairPtr);
-        b->pairPtr = nullptr;
-        CS_HIP(hipMalloc((void**)&b->pairPtr, sizeof(int) * ((size_t)nPairsAll + 1)));
-        b->pairPtrCap = (size_t)nPairsAll + 1;
-    }
-    hipLaunchKernelGGL(k_pairs_count, dim3(nPairsAll), dim3(64), 0, s, C, win->totals, b->obs_of, win->pairCnt);
-    hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(1024), 0, s, nPairsAll, win->pairCnt, b->pairPtr, win->pairTotal);
-    // ONE round trip: the sizes (launch dimensions of everything that follows), the pair total, obs_ptr for the lane plan
-    CS_HIP(hipMemcpyAsync(win->h_totals, win->totals, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    CS_HIP(hipMemcpyAsync(win->h_totals + 4, win->pairTotal, sizeof(int), hipMemcpyDeviceToHost, s));
-    int* h_optr = win->h_totals + 8;
-    CS_HIP(hipMemcpyAsync(h_optr, b->obs_ptr, sizeof(int) * ((size_t)win->nMap + 1), hipMemcpyDeviceToHost, s));
-    if (w->tmEv[2]) {
-        (void)hipEventRecord(w->tmEv[2], s);
-        w->parseStamped = true;
-    }
-    CS_HIP(hipStreamSynchronize(s));  // (this is the worker thread: the frame loop does not wait)
-    parseDone.release();              // the ring has been read
-    const int P = win->h_totals[0], nObs = win->h_totals[1];
-    {
-        std::lock_guard<std::mutex> lk(win->mu);
-        win->lastC = C, win->lastP = P, win->lastObs = nObs;
-        win->lastCount = J.winCount;
-        for (int j = 0; j < J.winCount; ++j) win->lastFrames[j] = J.winFrames[j];
-    }
-    b->maxObs = win->h_totals[2];
-    b->havePairs = false;
-    if (P == 0 || nObs == 0) {
-        cs_set_error("cs_ba_solve_window_async: no map point has two feature points in the window");
-        return CS_ERR_INVALID;
-    }
-    // lane plan of the packed kernels (as cs_ba_upload builds it): whole points back to back, at most 64 measurements per wave
-    b->nPackWaves = 0;
-    if (b->maxObs <= 64) {
-        if ((size_t)win->nMap + 2 > b->waveStartCap) {
-            if (b->waveStart) (void)hipFree(b->waveStart);
-            b->waveStart = nullptr;
-            b->waveStartCap = 0;
-            CS_HIP(hipMalloc((void**)&b->waveStart, sizeof(int) * ((size_t)win->nMap + 2)));
-            b->waveStartCap = (size_t)win->nMap + 2;
-        }
-        int* ws = win->h_plan;
-        int nw = 0, fill = 0;
-        ws[nw++] = 0;
-        for (int i = 0; i < P; ++i) {
-            const int k = h_optr[i + 1] - h_optr[i];
-            if (k == 0) continue;
-            if (fill + k > 64) {
-                ws[nw++] = h_optr[i];
-                fill = 0;
+    const BaTopoSrc T = {"cs_ba_solve_window_async", win->totals, win->pairCnt, win->pairTotal, win->h_totals, win->h_plan,
+                         (size_t)win->nMap + 1, 6 * (C - J.nCamsCon) <= 36 && C <= 256};
+    BaTopoSizes Z;
+    rc = ba_device_topology(
+        b, w, s, C, T, &Z,
+        [&](const BaTopoSizes& z) {
+            parseDone.release();  // the ring has been read
+            {
+                std::lock_guard<std::mutex> lk(win->mu);
+                win->lastC = C, win->lastP = z.P, win->lastObs = z.nObs;
+                win->lastCount = J.winCount;
+                for (int j = 0; j < J.winCount; ++j) win->lastFrames[j] = J.winFrames[j];
             }
-            fill += k;
-        }
-        ws[nw++] = nObs;
-        CS_HIP(hipMemcpyAsync(b->waveStart, ws, sizeof(int) * nw, hipMemcpyHostToDevice, s));  // (h_plan is pinned and outlives the copy)
-        b->nPackWaves = nw - 1;
-    }
-    const size_t nEnt = (size_t)win->h_totals[4];
-    if (nEnt > 0 && nEnt <= ((size_t)8 << 20)) {
-        if (nEnt > b->pairEntCap) {
-            // sized ONCE for the largest list this path accepts (128 MB of 288 GB): a later, larger window never frees -- hipFree
-            // synchronises the device, which would wait for a pose stream that is itself waiting for this solve (k_ba_output_wait)
-            if (b->pairEnt) (void)hipFree(b->pairEnt);
-            b->pairEnt = nullptr;
-            const size_t cap = (size_t)8 << 20;
-            CS_HIP(hipMalloc((void**)&b->pairEnt, sizeof(int4) * cap));
-            b->pairEntCap = cap;
-        }
-        hipLaunchKernelGGL(k_pairs_fill, dim3(nPairsAll), dim3(64), 0, s, C, P, b->obs_of, b->pairPtr, b->pairEnt);
-        b->havePairs = true;
-    }
-    if (!b->havePairs) {  // (the camera-indexed lists k_schur would need are not built on the device)
-        cs_set_error("cs_ba_solve_window_async: %zu camera-pair entries exceed what the window path supports", nEnt);
-        return CS_ERR_INVALID;
-    }
-    // the robust solve in the same segments as cs_ba_solve_async's, the kernels enqueued directly (the sizes change with every
-    // key frame: no graph to replay); the estimate the fill kernel wrote into Rs / Ts / pts is the start (the key poses as
-    // tracked, the map as it stands)
+            if (z.P == 0 || z.nObs == 0) {
+                cs_set_error("cs_ba_solve_window_async: no map point has two feature points in the window");
+                return CS_ERR_INVALID;
+            }
+            return CS_OK;
+        },
+        // sized ONCE for the largest list this path accepts (128 MB of 288 GB): a later, larger window never frees -- hipFree
+        // synchronises the device, which would wait for a pose stream that is itself waiting for this solve (k_ba_output_wait)
+        [](size_t) { return (size_t)8 << 20; });
+    if (rc) return rc;
+    const int P = Z.P, nObs = Z.nObs;
+    // the robust solve in the same segments as cs_ba_solve_async's; the estimate the fill kernel wrote into Rs / Ts / pts is the
+    // start (the key poses as tracked, the map as it stands)
     BaPlan L;
     rc = ba_make_plan(b, C, P, nObs, J.nCamsCon, J.nPtsCon, J.maxErr, J.innerMaxIter, false, &L);
     if (rc) return rc;
-    {
-        w->chunk = 2;   // LM steps per segment (measured in the frame loop: 1 -> 1.85, 2 -> 1.81, 3 -> 1.89 ms per joint solve)
-        if (w->chunk > J.innerMaxIter && J.innerMaxIter > 0) w->chunk = J.innerMaxIter;
-        if (w->chunk < 1) w->chunk = 1;
-    }
-    const bool stateInKernel = ba_state_in_kernel(w, L);
-    const BaDev& D = L.D;
-    const dim3 blk(256);
-    rc = ba_run_segments(w, s, J.maxIter, J.innerMaxIter, [&](char kind) {
-        switch (kind) {
-            case 'H':
-                ba_enqueue_init(b, s, L, false, nullptr, nullptr, nullptr);
-                hipLaunchKernelGGL(k_cost, dim3(L.cb), blk, 0, s, D, 0);
-                hipLaunchKernelGGL(k_control, dim3(1), blk, 0, s, D);
-                break;
-            case 'R':
-                hipLaunchKernelGGL(k_cost, dim3(L.cb), blk, 0, s, D, 0);
-                hipLaunchKernelGGL(k_control, dim3(1), blk, 0, s, D);
-                break;
-            case 'C':
-                ba_enqueue_lm_run(s, L, w->chunk);
-                if (!stateInKernel) (void)hipMemcpyAsync(w->h_state, &b->st->inner_done, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
-                break;
-            case 'T':
-                hipLaunchKernelGGL(k_flag, dim3(L.cb), blk, 0, s, D);
-                hipLaunchKernelGGL(k_outer_end, dim3(1), dim3(1), 0, s, D);
-                if (!stateInKernel) (void)hipMemcpyAsync(w->h_state, &b->st->inner_done, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
-                break;
-            default:
-                hipLaunchKernelGGL(k_cost_force, dim3(L.cb), blk, 0, s, D);
-                hipLaunchKernelGGL(k_finish, dim3(1), blk, 0, s, D, b->stats);
-                break;
-        }
-        return hipGetLastError();
-    });
+    // 2 LM steps per segment (measured in the frame loop: 1 -> 1.85, 2 -> 1.81, 3 -> 1.89 ms per joint solve)
+    rc = ba_run_segments_direct(b, w, s, L, J, 2);
     if (rc) return rc;
     rc = ba_run_followup(b, s);
     if (b->output) {   // RobustBundleRTS::output(), first half: the result into the next record, behind the solve's last kernel
@@ -3198,16 +3250,6 @@ struct cs_ba_intercam {
 
 static int ba_worker_run_intercam(cs_ba* b, BaWorker* w, const BaAsyncJob& J) {
     cs_ba_intercam* ic = J.ic;
-    CS_HIP(hipSetDevice(b->device));
-    hipStream_t s = b->own_stream;
-    CS_HIP(hipStreamWaitEvent(s, J.ready, 0));
-    {
-        std::lock_guard<std::mutex> lk(w->mu);
-        if (w->stale) {
-            ba_worker_destroy_graphs(w);
-            w->stale = false;
-        }
-    }
     struct Consumed {   // whatever way this function is left: the staging record is free again
         cs_ba_intercam* ic;
         bool done = false;
@@ -3223,10 +3265,9 @@ static int ba_worker_run_intercam(cs_ba* b, BaWorker* w, const BaAsyncJob& J) {
         ~Consumed() { release(); }
     } consumed{ic};
     const int C = ic->nCams;
-    int rc = ba_reserve(b, C, ic->maxP, ic->maxObs);
+    int rc = ba_worker_begin(b, w, J, C, ic->maxP, ic->maxObs);
     if (rc) return rc;
-    ba_bind_io(b, b->capC, b->capP, b->capObs);
-    ba_drop_graph(b);
+    hipStream_t s = b->own_stream;
     const IcStage& st = ic->st[J.icSlot];
     const size_t P1 = (size_t)ic->maxP, O1 = (size_t)ic->maxObs;
     {   // the staged problem into the workspace: one launch (small_ops.h)
@@ -3237,116 +3278,33 @@ static int ba_worker_run_intercam(cs_ba* b, BaWorker* w, const BaAsyncJob& J) {
         ops.copy(ic->lastPointMap, st.pointMap, 4 * P1);
         CS_HIP(ops.run(s));
     }
-    if (6 * C <= 36)   // (the small-order solver's Schur kernels walk camera-indexed lists)
-        hipLaunchKernelGGL(k_cam_lists, dim3(1), dim3(1024), 0, s, C, st.totals, b->obs_cam, b->cam_ptr, b->cam_obs);
-    const int nPairsAll = C * (C + 1) / 2;
-    if ((size_t)nPairsAll + 1 > b->pairPtrCap) {
-        if (b->pairPtr) (void)hipFree(b->pairPtr);
-        b->pairPtr = nullptr;
-        CS_HIP(hipMalloc((void**)&b->pairPtr, sizeof(int) * ((size_t)nPairsAll + 1)));
-        b->pairPtrCap = (size_t)nPairsAll + 1;
-    }
-    hipLaunchKernelGGL(k_pairs_count, dim3(nPairsAll), dim3(64), 0, s, C, st.totals, b->obs_of, ic->pairCnt);
-    hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(1024), 0, s, nPairsAll, ic->pairCnt, b->pairPtr, ic->pairTotal);
-    CS_HIP(hipMemcpyAsync(ic->h_totals, st.totals, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    CS_HIP(hipMemcpyAsync(ic->h_totals + 4, ic->pairTotal, sizeof(int), hipMemcpyDeviceToHost, s));
-    int* h_optr = ic->h_totals + 8;
-    CS_HIP(hipMemcpyAsync(h_optr, b->obs_ptr, sizeof(int) * (P1 + 1), hipMemcpyDeviceToHost, s));
-    if (w->tmEv[2]) {
-        (void)hipEventRecord(w->tmEv[2], s);
-        w->parseStamped = true;
-    }
-    CS_HIP(hipStreamSynchronize(s));
-    consumed.release();
-    const int P = ic->h_totals[0], nObs = ic->h_totals[1], nStatic = ic->h_totals[3];
-    {
-        std::lock_guard<std::mutex> lk(ic->mu);
-        ic->lastC = C, ic->lastP = P, ic->lastObs = nObs, ic->lastStatic = nStatic;
-    }
-    b->maxObs = ic->h_totals[2];
-    b->havePairs = false;
-    if (P == 0 || nObs == 0 || nStatic == 0) {   // (the reference asserts m_numStatic > 0, :93)
-        cs_set_error("cs_ba_solve_intercam_async: no static feature point carries a map point");
-        return CS_ERR_INVALID;
-    }
-    b->nPackWaves = 0;
-    if (b->maxObs <= 64) {
-        if ((size_t)ic->maxP + 2 > b->waveStartCap) {
-            if (b->waveStart) (void)hipFree(b->waveStart);
-            b->waveStart = nullptr;
-            b->waveStartCap = 0;
-            CS_HIP(hipMalloc((void**)&b->waveStart, sizeof(int) * ((size_t)ic->maxP + 2)));
-            b->waveStartCap = (size_t)ic->maxP + 2;
-        }
-        int* ws = ic->h_plan;
-        int nw = 0, fill = 0;
-        ws[nw++] = 0;
-        for (int i = 0; i < P; ++i) {
-            const int k = h_optr[i + 1] - h_optr[i];
-            if (k == 0) continue;
-            if (fill + k > 64) {
-                ws[nw++] = h_optr[i];
-                fill = 0;
+    const BaTopoSrc T = {"cs_ba_solve_intercam_async", st.totals, ic->pairCnt, ic->pairTotal, ic->h_totals, ic->h_plan, P1 + 1, 6 * C <= 36};
+    BaTopoSizes Z;
+    rc = ba_device_topology(
+        b, w, s, C, T, &Z,
+        [&](const BaTopoSizes& z) {
+            consumed.release();
+            {
+                std::lock_guard<std::mutex> lk(ic->mu);
+                ic->lastC = C, ic->lastP = z.P, ic->lastObs = z.nObs, ic->lastStatic = z.nStatic;
             }
-            fill += k;
-        }
-        ws[nw++] = nObs;
-        CS_HIP(hipMemcpyAsync(b->waveStart, ws, sizeof(int) * nw, hipMemcpyHostToDevice, s));
-        b->nPackWaves = nw - 1;
-    }
-    const size_t nEnt = (size_t)ic->h_totals[4];
-    if (nEnt == 0 || nEnt > ((size_t)8 << 20)) {
-        cs_set_error("cs_ba_solve_intercam_async: %zu camera-pair entries", nEnt);
-        return CS_ERR_INVALID;
-    }
-    if (nEnt > b->pairEntCap) {
+            if (z.P == 0 || z.nObs == 0 || z.nStatic == 0) {   // (the reference asserts m_numStatic > 0, :93)
+                cs_set_error("cs_ba_solve_intercam_async: no static feature point carries a map point");
+                return CS_ERR_INVALID;
+            }
+            return CS_OK;
+        },
         // sized once for the largest problem addMapPoints can build (a static point: one entry; a dynamic one: every camera pair),
         // so that no later solve frees (hipFree synchronises the device: see the window path)
-        if (b->pairEnt) (void)hipFree(b->pairEnt);
-        b->pairEnt = nullptr;
-        const size_t bound = (size_t)ic->nCams * ic->ptsStride + (size_t)(ic->maxDyn + 1) * ic->nCams * (ic->nCams + 1) / 2 + 1024;
-        const size_t cap = nEnt + nEnt / 4 + 1024 > bound ? nEnt + nEnt / 4 + 1024 : bound;
-        CS_HIP(hipMalloc((void**)&b->pairEnt, sizeof(int4) * cap));
-        b->pairEntCap = cap;
-    }
-    hipLaunchKernelGGL(k_pairs_fill, dim3(nPairsAll), dim3(64), 0, s, C, P, b->obs_of, b->pairPtr, b->pairEnt);
-    b->havePairs = true;
-    BaPlan L;
-    rc = ba_make_plan(b, C, P, nObs, 0, nStatic, J.maxErr, J.innerMaxIter, false, &L);   // nCamsCon 0, nPtsCon = m_numStatic (:95)
+        [&](size_t nEnt) {
+            const size_t bound = (size_t)ic->nCams * ic->ptsStride + (size_t)(ic->maxDyn + 1) * ic->nCams * (ic->nCams + 1) / 2 + 1024;
+            return nEnt + nEnt / 4 + 1024 > bound ? nEnt + nEnt / 4 + 1024 : bound;
+        });
     if (rc) return rc;
-    w->chunk = 5;
-    if (w->chunk > J.innerMaxIter && J.innerMaxIter > 0) w->chunk = J.innerMaxIter;
-    if (w->chunk < 1) w->chunk = 1;
-    const bool stateInKernel = ba_state_in_kernel(w, L);
-    const BaDev& D = L.D;
-    const dim3 blk(256);
-    rc = ba_run_segments(w, s, J.maxIter, J.innerMaxIter, [&](char kind) {
-        switch (kind) {
-            case 'H':
-                ba_enqueue_init(b, s, L, false, nullptr, nullptr, nullptr);
-                hipLaunchKernelGGL(k_cost, dim3(L.cb), blk, 0, s, D, 0);
-                hipLaunchKernelGGL(k_control, dim3(1), blk, 0, s, D);
-                break;
-            case 'R':
-                hipLaunchKernelGGL(k_cost, dim3(L.cb), blk, 0, s, D, 0);
-                hipLaunchKernelGGL(k_control, dim3(1), blk, 0, s, D);
-                break;
-            case 'C':
-                ba_enqueue_lm_run(s, L, w->chunk);
-                if (!stateInKernel) (void)hipMemcpyAsync(w->h_state, &b->st->inner_done, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
-                break;
-            case 'T':
-                hipLaunchKernelGGL(k_flag, dim3(L.cb), blk, 0, s, D);
-                hipLaunchKernelGGL(k_outer_end, dim3(1), dim3(1), 0, s, D);
-                if (!stateInKernel) (void)hipMemcpyAsync(w->h_state, &b->st->inner_done, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
-                break;
-            default:
-                hipLaunchKernelGGL(k_cost_force, dim3(L.cb), blk, 0, s, D);
-                hipLaunchKernelGGL(k_finish, dim3(1), blk, 0, s, D, b->stats);
-                break;
-        }
-        return hipGetLastError();
-    });
+    BaPlan L;
+    rc = ba_make_plan(b, C, Z.P, Z.nObs, 0, Z.nStatic, J.maxErr, J.innerMaxIter, false, &L);   // nCamsCon 0, nPtsCon = m_numStatic (:95)
+    if (rc) return rc;
+    rc = ba_run_segments_direct(b, w, s, L, J, 5);
     if (rc) return rc;
     rc = ba_run_followup(b, s);
     CS_HIP(hipStreamSynchronize(s));
@@ -3385,56 +3343,26 @@ static int ba_worker_run(cs_ba* b, BaWorker* w, const BaAsyncJob& J) {
 static int ba_worker_run_inner(cs_ba* b, BaWorker* w, const BaAsyncJob& J) {
     if (J.win) return ba_worker_run_window(b, w, J);
     if (J.ic) return ba_worker_run_intercam(b, w, J);
-    CS_HIP(hipSetDevice(b->device));
-    hipStream_t s = b->own_stream;
-    CS_HIP(hipStreamWaitEvent(s, J.ready, 0));
-    cs_ba::GraphKey key = {J.C, J.P, J.nObs, J.nCamsCon, J.nPtsCon, J.maxIter, J.innerMaxIter, J.maxErr, J.R0, J.T0, J.M0};
-    {
-        std::lock_guard<std::mutex> lk(w->mu);
-        if (w->stale) {
-            ba_worker_destroy_graphs(w);
-            w->stale = false;
-        }
-    }
-    BaPlan L;
-    int rc = ba_make_plan(b, J.C, J.P, J.nObs, J.nCamsCon, J.nPtsCon, J.maxErr, J.innerMaxIter, false, &L);
+    int rc = ba_worker_begin(b, w, J);
     if (rc) return rc;
-    const bool stateInKernel = ba_state_in_kernel(w, L);
-    const BaDev& D = L.D;
-    const dim3 blk(256);
+    hipStream_t s = b->own_stream;
+    cs_ba::GraphKey key = {J.C, J.P, J.nObs, J.nCamsCon, J.nPtsCon, J.maxIter, J.innerMaxIter, J.maxErr, J.R0, J.T0, J.M0};
+    BaPlan L;
+    rc = ba_make_plan(b, J.C, J.P, J.nObs, J.nCamsCon, J.nPtsCon, J.maxErr, J.innerMaxIter, false, &L);
+    if (rc) return rc;
+    int* const stateTo = ba_state_in_kernel(w, L) ? nullptr : w->h_state;
     if (!w->haveGraphs || memcmp(&key, &w->key, sizeof(key)) != 0) {
         ba_worker_destroy_graphs(w);
-        w->chunk = 5;   // LM steps per captured segment
-        if (w->chunk > J.innerMaxIter && J.innerMaxIter > 0) w->chunk = J.innerMaxIter;
-        // head: initial estimate into the workspace, cost and LM state of the first round
-        rc = ba_capture(s, &w->gHead, [&] {
-            ba_enqueue_init(b, s, L, false, J.R0, J.T0, J.M0);
-            hipLaunchKernelGGL(k_cost, dim3(L.cb), blk, 0, s, D, 0);
-            hipLaunchKernelGGL(k_control, dim3(1), blk, 0, s, D);
-        });
-        if (rc) return rc;
-        rc = ba_capture(s, &w->gChunk, [&] {
-            ba_enqueue_lm_run(s, L, w->chunk);  // (the state word read back below is exact at every chunk boundary)
-            if (!stateInKernel) (void)hipMemcpyAsync(w->h_state, &b->st->inner_done, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
-        });
-        if (rc) return rc;
-        // tail of a round: outlier flags, round bookkeeping; start of the next round: cost + LM state
-        rc = ba_capture(s, &w->gTail, [&] {
-            hipLaunchKernelGGL(k_flag, dim3(L.cb), blk, 0, s, D);
-            hipLaunchKernelGGL(k_outer_end, dim3(1), dim3(1), 0, s, D);
-            if (!stateInKernel) (void)hipMemcpyAsync(w->h_state, &b->st->inner_done, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
-        });
-        if (rc) return rc;
-        rc = ba_capture(s, &w->gRound, [&] {
-            hipLaunchKernelGGL(k_cost, dim3(L.cb), blk, 0, s, D, 0);
-            hipLaunchKernelGGL(k_control, dim3(1), blk, 0, s, D);
-        });
-        if (rc) return rc;
-        rc = ba_capture(s, &w->gFinish, [&] {
-            hipLaunchKernelGGL(k_cost_force, dim3(L.cb), blk, 0, s, D);
-            hipLaunchKernelGGL(k_finish, dim3(1), blk, 0, s, D, b->stats);
-        });
-        if (rc) return rc;
+        ba_worker_set_chunk(w, 5, J.innerMaxIter);   // LM steps per captured segment
+        // the segments captured once (the sizes are those of the upload); the head copies the start estimate into the workspace
+        const struct {
+            char kind;
+            hipGraphExec_t* g;
+        } parts[] = {{'H', &w->gHead}, {'C', &w->gChunk}, {'T', &w->gTail}, {'R', &w->gRound}, {'F', &w->gFinish}};
+        for (const auto& q : parts) {
+            rc = ba_capture(s, q.g, [&] { ba_enqueue_segment(b, s, L, q.kind, w->chunk, stateTo, {false, J.R0, J.T0, J.M0}); });
+            if (rc) return rc;
+        }
         w->key = key;
         w->haveGraphs = true;
     }
@@ -3515,6 +3443,33 @@ static void ba_worker_stop(cs_ba* b) {
         if (e) (void)hipEventDestroy(e);
     delete w;
     b->worker = nullptr;
+}
+
+// Queue a request for the workspace's worker (created with the first one): it starts when the work enqueued on after_stream so far
+// is done.  beforePush runs behind everything that can fail, right before the worker can see the job.
+template <class F>
+static int ba_worker_submit(cs_ba* b, BaAsyncJob& J, void* after_stream, const char* who, F&& beforePush) {
+    if (!b->worker) {
+        BaWorker* w = new BaWorker();
+        if (hipHostMalloc((void**)&w->h_state, 4 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+            delete w;
+            cs_set_error("%s: cannot allocate the pinned state word", who);
+            return CS_ERR_ALLOC;
+        }
+        w->h_state[0] = w->h_state[1] = 0;
+        b->worker = w;
+        w->th = std::thread(ba_worker_main, b, w);
+    }
+    CS_HIP(hipEventCreateWithFlags(&J.ready, hipEventDisableTiming));
+    CS_HIP(hipEventRecord(J.ready, (hipStream_t)after_stream));
+    beforePush();
+    {
+        std::lock_guard<std::mutex> lk(b->worker->mu);
+        b->worker->q.push_back(J);
+        b->worker->inflight += 1;
+    }
+    b->worker->cv.notify_one();
+    return CS_OK;
 }
 
 extern "C" {
@@ -3656,33 +3611,16 @@ int cs_ba_robust_h(cs_ba* b, int C, int P, int nObs, const double* Ks, double* R
         memcpy(b->h_io + L.ocam, obs_cam, sizeof(int) * nObs);
     }
     hipStream_t s = b->own_stream;
-    // Lane plan of the packed kernels (ba_packed_dev.h): whole points back to back, at most 64 measurements per wave, in point
-    // order -- a wave is then a contiguous range of the measurement arrays.  Not for a point with more than 64 measurements.
+    // lane plan of the packed kernels: only on the upload path, like the pair lists below
     b->nPackWaves = 0;
     if (maxIter == 0 && nObs > 0 && b->maxObs <= 64) {
-        std::vector<int> ws;
-        ws.push_back(0);
-        int fill = 0;
-        for (int i = 0; i < P; ++i) {
-            const int k = obs_ptr[i + 1] - obs_ptr[i];
-            if (k == 0) continue;
-            if (fill + k > 64) {
-                ws.push_back(obs_ptr[i]);
-                fill = 0;
-            }
-            fill += k;
-        }
-        ws.push_back(nObs);
-        if (ws.size() > b->waveStartCap) {
-            if (b->waveStart) (void)hipFree(b->waveStart);
-            b->waveStart = nullptr;
-            b->waveStartCap = 0;
-            CS_HIP(hipMalloc((void**)&b->waveStart, sizeof(int) * ws.size()));
-            b->waveStartCap = ws.size();
-        }
-        CS_HIP(hipMemcpyAsync(b->waveStart, ws.data(), sizeof(int) * ws.size(), hipMemcpyHostToDevice, s));
+        std::vector<int> ws((size_t)P + 2);
+        const size_t nw = (size_t)ba_lane_plan(obs_ptr, P, nObs, ws.data());
+        if (nw > b->waveStartCap) rc = ba_regrow(&b->waveStart, &b->waveStartCap, nw, CS_ERR_HIP, "the lane plan");
+        if (rc) return rc;
+        CS_HIP(hipMemcpyAsync(b->waveStart, ws.data(), sizeof(int) * nw, hipMemcpyHostToDevice, s));
         CS_HIP(hipStreamSynchronize(s));  // (the vector goes out of scope)
-        b->nPackWaves = (int)ws.size() - 1;
+        b->nPackWaves = (int)nw - 1;
     }
     // Camera-pair lists for k_schur_pairs: which measurements meet in which block of the reduced system is fixed by the
     // topology, so the kernel's index chain (camera list -> point -> partner measurement, three dependent loads per entry,
@@ -3713,18 +3651,9 @@ int cs_ba_robust_h(cs_ba* b, int C, int P, int nObs, const double* Ks, double* R
                     for (int o2 = obs_ptr[i]; o2 < obs_ptr[i + 1]; ++o2)
                         if (obs_cam[o1] <= obs_cam[o2] && (obs_cam[o1] != obs_cam[o2] || o1 == o2))
                             ent[(size_t)fill[pid(obs_cam[o1], obs_cam[o2])]++] = make_int4(o1, o2, i, 0);
-            if (ptr.size() > b->pairPtrCap) {
-                if (b->pairPtr) (void)hipFree(b->pairPtr);
-                b->pairPtr = nullptr;
-                CS_HIP(hipMalloc((void**)&b->pairPtr, sizeof(int) * ptr.size()));
-                b->pairPtrCap = ptr.size();
-            }
-            if (ent.size() > b->pairEntCap) {
-                if (b->pairEnt) (void)hipFree(b->pairEnt);
-                b->pairEnt = nullptr;
-                CS_HIP(hipMalloc((void**)&b->pairEnt, sizeof(int4) * ent.size()));
-                b->pairEntCap = ent.size();
-            }
+            if (ptr.size() > b->pairPtrCap) rc = ba_regrow(&b->pairPtr, &b->pairPtrCap, ptr.size(), CS_ERR_HIP, "the camera-pair index");
+            if (!rc && ent.size() > b->pairEntCap) rc = ba_regrow(&b->pairEnt, &b->pairEntCap, ent.size(), CS_ERR_HIP, "the camera-pair lists");
+            if (rc) return rc;
             CS_HIP(hipMemcpyAsync(b->pairPtr, ptr.data(), sizeof(int) * ptr.size(), hipMemcpyHostToDevice, s));
             CS_HIP(hipMemcpyAsync(b->pairEnt, ent.data(), sizeof(int4) * ent.size(), hipMemcpyHostToDevice, s));
             CS_HIP(hipStreamSynchronize(s));  // (the vectors go out of scope)
@@ -3996,29 +3925,10 @@ int cs_ba_solve_async(cs_ba* b, void* after_stream, int C, int P, int nObs, cons
         return CS_ERR_INVALID;
     }
     CS_HIP(hipSetDevice(b->device));
-    if (!b->worker) {
-        BaWorker* w = new BaWorker();
-        if (hipHostMalloc((void**)&w->h_state, 4 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-            delete w;
-            cs_set_error("cs_ba_solve_async: cannot allocate the pinned state word");
-            return CS_ERR_ALLOC;
-        }
-        w->h_state[0] = w->h_state[1] = 0;
-        b->worker = w;
-        w->th = std::thread(ba_worker_main, b, w);
-    }
     BaAsyncJob J;
     J.C = C, J.P = P, J.nObs = nObs, J.nCamsCon = nCamsCon, J.nPtsCon = nPtsCon, J.maxIter = maxIter, J.innerMaxIter = innerMaxIter;
     J.maxErr = maxErr, J.R0 = d_Rs0, J.T0 = d_Ts0, J.M0 = d_pts0, J.ready = nullptr;
-    CS_HIP(hipEventCreateWithFlags(&J.ready, hipEventDisableTiming));
-    CS_HIP(hipEventRecord(J.ready, (hipStream_t)after_stream));
-    {
-        std::lock_guard<std::mutex> lk(b->worker->mu);
-        b->worker->q.push_back(J);
-        b->worker->inflight += 1;
-    }
-    b->worker->cv.notify_one();
-    return CS_OK;
+    return ba_worker_submit(b, J, after_stream, "cs_ba_solve_async", [] {});
 }
 
 // ---- sliding window of key frames: the BA's inputs from the tracker's own records (ba_window_dev.h) ---------------------------
@@ -4169,17 +4079,6 @@ static int ba_solve_window_async(cs_ba* b, cs_ba_window* w, void* after_stream, 
         return CS_ERR_INVALID;
     }
     CS_HIP(hipSetDevice(b->device));
-    if (!b->worker) {
-        BaWorker* wk = new BaWorker();
-        if (hipHostMalloc((void**)&wk->h_state, 4 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-            delete wk;
-            cs_set_error("cs_ba_solve_window_async: cannot allocate the pinned state word");
-            return CS_ERR_ALLOC;
-        }
-        wk->h_state[0] = wk->h_state[1] = 0;
-        b->worker = wk;
-        wk->th = std::thread(ba_worker_main, b, wk);
-    }
     BaAsyncJob J;
     J.C = J.P = J.nObs = 0;
     J.nCamsCon = nCamsCon, J.nPtsCon = nPtsCon, J.maxIter = maxIter, J.innerMaxIter = innerMaxIter, J.maxErr = maxErr;
@@ -4213,21 +4112,13 @@ static int ba_solve_window_async(cs_ba* b, cs_ba_window* w, void* after_stream, 
         J.winSlotOf[j] = (w->head - w->count + j + 2 * w->ring) % w->ring;
         J.winFrames[j] = w->frameOf[J.winSlotOf[j]];
     }
-    CS_HIP(hipEventCreateWithFlags(&J.ready, hipEventDisableTiming));
-    CS_HIP(hipEventRecord(J.ready, (hipStream_t)after_stream));
-    {   // (behind everything that can fail: a request that is counted is a request the worker will release)
+    return ba_worker_submit(b, J, after_stream, "cs_ba_solve_window_async", [&] {
+        // (behind everything that can fail: a request that is counted is a request the worker will release)
         std::lock_guard<std::mutex> lk(w->mu);
         w->parsesPending += 1;
         w->pendingNewest.push_back(w->pushCount - 1);
         J.winNewest = w->pushCount - 1;
-    }
-    {
-        std::lock_guard<std::mutex> lk(b->worker->mu);
-        b->worker->q.push_back(J);
-        b->worker->inflight += 1;
-    }
-    b->worker->cv.notify_one();
-    return CS_OK;
+    });
 }
 
 // Size and bind the workspace for the largest problem the window can produce NOW (cs_ba_solve_window_async does it on first
@@ -4693,17 +4584,6 @@ int cs_ba_solve_intercam_async(cs_ba* b, cs_ba_intercam* ic, void* after_stream,
         return CS_ERR_INVALID;
     }
     CS_HIP(hipSetDevice(b->device));
-    if (!b->worker) {
-        BaWorker* wk = new BaWorker();
-        if (hipHostMalloc((void**)&wk->h_state, 4 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-            delete wk;
-            cs_set_error("cs_ba_solve_intercam_async: cannot allocate the pinned state word");
-            return CS_ERR_ALLOC;
-        }
-        wk->h_state[0] = wk->h_state[1] = 0;
-        b->worker = wk;
-        wk->th = std::thread(ba_worker_main, b, wk);
-    }
     IcArgs A;
     memset(&A, 0, sizeof(A));
     A.nCams = ic->nCams, A.N = ic->N, A.W = W, A.H = H, A.nColBlk = nColBlk, A.nRowBlk = nRowBlk;
@@ -4736,15 +4616,7 @@ int cs_ba_solve_intercam_async(cs_ba* b, cs_ba_intercam* ic, void* after_stream,
     J.nCamsCon = 0, J.nPtsCon = 0, J.maxIter = maxIter, J.innerMaxIter = innerMaxIter, J.maxErr = maxErr;
     J.R0 = J.T0 = J.M0 = nullptr;
     J.ic = ic, J.icSlot = slot;
-    CS_HIP(hipEventCreateWithFlags(&J.ready, hipEventDisableTiming));
-    CS_HIP(hipEventRecord(J.ready, as));
-    {
-        std::lock_guard<std::mutex> lk(b->worker->mu);
-        b->worker->q.push_back(J);
-        b->worker->inflight += 1;
-    }
-    b->worker->cv.notify_one();
-    return CS_OK;
+    return ba_worker_submit(b, J, after_stream, "cs_ba_solve_intercam_async", [] {});
 }
 
 // sizes of the last problem a worker solved from ic (call after cs_ba_wait): cameras, points (static first), measurements, m_numStatic,

@@ -470,16 +470,29 @@ def test_ba_rejects_malformed_problems(hip):
         call(cam_=dup)
 
 
-def test_ba_window_parses_the_problem_on_the_device_and_solves_it(hip):
-    """cs_ba_window_* + cs_ba_solve_window_async: RobustBundleRTS::addKeyFrames / addPoints / parseInputs (reference
-    src/app/SL_CoSLAMRobustBA.cpp:37-78,109-165) on the device.  Seven key frames pushed into a ring of five (the two oldest
-    drop out), records with unmapped, dead, dropped and doubled slots; the flat problem the device builds must equal the
-    numpy restatement array for array (cameras, kept points in map order, measurements in camera order, the map indices), and
-    its robust solve the oracle's on that flat problem (flags, iteration counts, 1e-6)."""
+def _push_key_frame(win, stream, recs, frame):
+    """one key frame (a record per camera: xy, state, slot2map, K, R, t) into the window -> the tensors the push reads"""
     import torch
 
     from coslam_amd.handback import handback_cams
-    from coslam_amd.multicam import _DevArray
+
+    dev = torch.device("cuda:0")
+    t_xy = [torch.from_numpy(r["xy"]).to(dev) for r in recs]
+    t_st = [torch.from_numpy(r["state"]).to(dev) for r in recs]
+    t_sm = [torch.from_numpy(r["slot2map"]).to(dev) for r in recs]
+    hb = handback_cams([dict(xy=t_xy[c].data_ptr(), state=t_st[c].data_ptr(), slot2map=t_sm[c].data_ptr()) for c in range(len(recs))])
+    d_K = torch.from_numpy(np.stack([r["K"] for r in recs])).to(dev)
+    d_R = torch.from_numpy(np.stack([r["R"] for r in recs])).to(dev)
+    d_t = torch.from_numpy(np.stack([r["t"] for r in recs])).to(dev)
+    win.push_dev(stream.cuda_stream, hb, d_K.data_ptr(), 0, d_R.data_ptr(), d_t.data_ptr(), frame)
+    stream.synchronize()
+    return t_xy, t_st, t_sm, d_K, d_R, d_t
+
+
+def _solved_window_scene():
+    """Seven key frames pushed into a ring of five (the two oldest drop out), records with unmapped, dead, dropped and doubled slots,
+    and the robust solve of that window requested and waited for."""
+    import torch
 
     rng = np.random.default_rng(77)
     n_cams, n_kf, n_push, N, n_map = 3, 5, 7, 320, 400
@@ -520,23 +533,33 @@ def test_ba_window_parses_the_problem_on_the_device_and_solves_it(hip):
     d_map = torch.from_numpy(pr["pts0"].copy()).to(dev)
     s = torch.cuda.Stream(device=dev)
     for j in range(n_push):
-        t_xy = [torch.from_numpy(r["xy"]).to(dev) for r in key_frames[j]]
-        t_st = [torch.from_numpy(r["state"]).to(dev) for r in key_frames[j]]
-        t_sm = [torch.from_numpy(r["slot2map"]).to(dev) for r in key_frames[j]]
-        hb = handback_cams([dict(xy=t_xy[c].data_ptr(), state=t_st[c].data_ptr(), slot2map=t_sm[c].data_ptr()) for c in range(n_cams)])
-        d_K = torch.from_numpy(np.stack([r["K"] for r in key_frames[j]])).to(dev)
-        d_R = torch.from_numpy(np.stack([r["R"] for r in key_frames[j]])).to(dev)
-        d_t = torch.from_numpy(np.stack([r["t"] for r in key_frames[j]])).to(dev)
-        win.push_dev(s.cuda_stream, hb, d_K.data_ptr(), 0, d_R.data_ptr(), d_t.data_ptr(), 5 * j)
-        s.synchronize()
-        keep.append((t_xy, t_st, t_sm, d_K, d_R, d_t))
+        keep.append(_push_key_frame(win, s, key_frames[j], 5 * j))
     ref = oracle.parse_inputs_window(key_frames[n_push - n_kf:], pr["pts0"])
     ncon, npcon = 2 * n_cams, 2
     win.solve_async(ws, s.cuda_stream, d_map.data_ptr(), ncon, npcon, 6.0, 2, 10)
     ws.wait()
+    return dict(win=win, ws=ws, ref=ref, ncon=ncon, npcon=npcon, n_cams=n_cams, n_kf=n_kf, dev=dev, keep=(keep, d_map, s))
+
+
+def _dev_view(ptr, n, ty):
+    import torch
+
+    from coslam_amd.multicam import _DevArray
+
+    return torch.as_tensor(_DevArray(ptr, n, ty), device=torch.device("cuda:0")).cpu().numpy()
+
+
+def test_ba_window_parses_the_problem_on_the_device_and_solves_it(hip):
+    """cs_ba_window_* + cs_ba_solve_window_async: RobustBundleRTS::addKeyFrames / addPoints / parseInputs (reference
+    src/app/SL_CoSLAMRobustBA.cpp:37-78,109-165) on the device.  Seven key frames pushed into a ring of five (the two oldest
+    drop out), records with unmapped, dead, dropped and doubled slots; the flat problem the device builds must equal the
+    numpy restatement array for array (cameras, kept points in map order, measurements in camera order, the map indices), and
+    its robust solve the oracle's on that flat problem (flags, iteration counts, 1e-6)."""
+    D = _solved_window_scene()
+    win, ws, ref, ncon, npcon, n_cams, n_kf = (D[k] for k in ("win", "ws", "ref", "ncon", "npcon", "n_cams", "n_kf"))
     Cw, Pw, Ow, pm_ptr, kfs = win.last_problem()
     assert (Cw, Pw, Ow) == (n_kf * n_cams, len(ref["pts"]), len(ref["obs_cam"])) and Pw > 150 and kfs == [5 * j for j in range(2, 7)]
-    view = lambda ptr, n, ty: torch.as_tensor(_DevArray(ptr, n, ty), device=dev).cpu().numpy()   # noqa: E731
+    view = _dev_view
     pK, pptr, pcam, pxy = ws.problem_buffers()
     assert np.array_equal(view(pptr, Pw + 1, "<i4"), ref["obs_ptr"])
     assert np.array_equal(view(pcam, Ow, "<i4"), ref["obs_cam"])
@@ -553,6 +576,96 @@ def test_ba_window_parses_the_problem_on_the_device_and_solves_it(hip):
     assert abs(st.cost - st_o.cost) <= 1e-7 * max(1.0, st_o.cost) and st.cost < 0.2 * st.cost0
     win.close()
     ws.close()
+
+
+def test_the_direct_launch_schedule_of_the_window_solve_equals_the_up_front_one(hip):
+    """cs_ba_solve_window_async launches the segments of the robust solve itself, two LM steps at a time, on a problem whose pair
+    lists and lane plan the device built; cs_ba_solve_dev enqueues the whole schedule up front on an uploaded problem whose lists
+    the host built.  The flat problem of the window read back, uploaded into a second workspace and solved from the same start
+    with the same budgets: the same bits (both list builders keep ascending point order inside a camera pair, and every sum in
+    the kernels has a fixed order)."""
+    import torch
+
+    D = _solved_window_scene()
+    win, ws, ref, ncon, npcon = (D[k] for k in ("win", "ws", "ref", "ncon", "npcon"))
+    Cw, Pw, Ow, _, _ = win.last_problem()
+    pK, pptr, pcam, pxy = ws.problem_buffers()
+    Ks, ptr = _dev_view(pK, 9 * Cw, "<f8").reshape(-1, 3, 3), _dev_view(pptr, Pw + 1, "<i4")
+    cam, xy = _dev_view(pcam, Ow, "<i4"), _dev_view(pxy, 2 * Ow, "<f8").reshape(-1, 2)
+    ws.set_sizes(Cw, Pw, Ow)
+    res_win = ws.download()
+    R0, T0, M0 = ref["Rs"].reshape(-1, 3, 3), ref["Ts"], ref["pts"]   # (the start the window's fill kernel wrote: checked bit for bit above)
+    ws2 = coslam_amd.BAWorkspace(0)
+    ws2.upload(Ks, R0, T0, M0, ptr, cam, xy)
+    d0 = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1).copy()).to(D["dev"]) for a in (R0, T0, M0)]
+    ws2.solve_dev(torch.cuda.current_stream().cuda_stream, d0[0].data_ptr(), d0[1].data_ptr(), d0[2].data_ptr(), ncon, npcon, 6.0, 2, 10)
+    res_dev = ws2.download()
+    for a, b in zip(res_win[:4], res_dev[:4]):
+        assert np.array_equal(a, b)
+    tup = lambda st: (st.cost0, st.cost, st.nIterTotal, st.nOuter, st.nOutliers, st.flags)   # noqa: E731
+    assert tup(res_win[4]) == tup(res_dev[4]) and res_win[4].nIterTotal > 0
+    ws2.close()
+    win.close()
+    ws.close()
+
+
+def test_a_failed_window_solve_still_yields_a_record_and_the_sequence_goes_on(hip):
+    """A window in which no map point is seen twice cannot be solved: cs_ba_wait reports it, and the worker still packs an EMPTY
+    record (ok = 0, no cameras / points / measurements) and publishes it, so that records stay one per request; the next window,
+    whose points are seen twice, is solved into the next record.  The smallest window that can fail: 2 cameras, 2 key frames,
+    64 slots, 32 map points."""
+    import ctypes as C
+
+    import torch
+
+    from coslam_amd.ba import BAOutput
+
+    n_cams, n_kf, N, n_map = 2, 2, 64, 32
+    pr = make_ba_problem(n_cams=n_kf * n_cams, n_pts=n_map, noise=0.3, outlier_frac=0.0, n_cams_con=n_cams, n_pts_con=2, seed=23)
+    xy_of = {(int(c), int(i)): pr["obs_xy"][o] for o, (c, i) in enumerate(zip(pr["obs_cam"], pr["obs_pt"]))}
+
+    def key_frame(j, points_of_cam):
+        recs = []
+        for c in range(n_cams):
+            ci = j * n_cams + c
+            xy, state, s2m = np.zeros(2 * N), np.full(N, -1, np.int32), np.full(N, -1, np.int32)
+            for s_, m in enumerate(points_of_cam(ci)):
+                state[s_], s2m[s_] = 0, m
+                xy[s_], xy[N + s_] = xy_of[(ci, m)]
+            recs.append(dict(xy=xy, state=state, slot2map=s2m, K=pr["Ks"][ci].reshape(9), R=pr["Rs0"][ci].reshape(9), t=pr["ts0"][ci]))
+        return recs
+
+    dev = torch.device("cuda:0")
+    win = coslam_amd.BAWindow(n_cams, n_kf, N, n_map)
+    ws = coslam_amd.BAWorkspace(0)
+    out = BAOutput(n_cams, n_kf, n_map, n_slots=4)
+    out.attach(ws)
+    d_map = torch.from_numpy(pr["pts0"].copy()).to(dev)
+    s = torch.cuda.Stream(device=dev)
+
+    def header(rec):
+        h8, kf = (C.c_int * 8)(), (C.c_int * 16)()
+        assert out._L.cs_ba_output_header(out._h, C.c_void_p(rec), C.c_void_p(s.cuda_stream), h8, kf) == 0
+        return list(h8)
+
+    # every camera of the window sees its own eight map points: no point has two feature points
+    keep = [_push_key_frame(win, s, key_frame(j, lambda ci: range(8 * ci, 8 * ci + 8)), 5 * j) for j in range(n_kf)]
+    win.solve_async(ws, s.cuda_stream, d_map.data_ptr(), n_cams, 2, 6.0, 2, 10)
+    with pytest.raises(coslam_amd.CoslamHipError):
+        ws.wait()
+    hdr = header(out.wait(0))
+    assert hdr[0:3] == [0, 0, 0] and hdr[5] == 0 and hdr[6] == 0 and hdr[7] == 1
+    assert out.packed() == 1
+    # two more key frames (the ring holds two: the first ones drop out) in which every camera sees every point
+    keep += [_push_key_frame(win, s, key_frame(j, lambda ci: range(n_map)), 10 + 5 * j) for j in range(n_kf)]
+    win.solve_async(ws, s.cuda_stream, d_map.data_ptr(), n_cams, 2, 6.0, 2, 10)
+    ws.wait()
+    hdr = header(out.wait(1))
+    assert hdr[6] == 1 and hdr[1] > 0 and hdr[5] == 1 and hdr[7] == 2
+    assert (hdr[0], hdr[1], hdr[2]) == win.last_problem()[:3] == (n_kf * n_cams, n_map, n_kf * n_cams * n_map)
+    ws.close()
+    out.close()
+    win.close()
 
 
 def test_ba_window_requests_queue_up_behind_a_frame_loop_that_runs_ahead(hip):
