@@ -25,6 +25,7 @@ HIP_SOURCES = [
     "register.hip",
     "keyframe.hip",
     "grouping.hip",
+    "merge.hip",
     "liveview.hip",
     "poseupdate.hip",
     "ncc.hip",

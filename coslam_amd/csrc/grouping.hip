@@ -12,7 +12,7 @@
 //              integers per workgroup, integer vector atomics to the global table.  Integers only: the result does not depend on the order
 //              of arrival.  minOverlapAreaRatio <= 0 can never cut a pair (an area is never < 0), so the per-frame call stops here.
 //   hull       k_group_hull: one workgroup per ORDERED camera pair compacts camera i's pixels of the shared points into LDS in row order and
-//              runs Quickhull rounds over them in parallel: every point outside the current polygon belongs to one edge, every edge takes
+//              runs Quickhull rounds over them in parallel (hull_quick, hull_dev.h: shared with merge.hip): every point outside the current polygon belongs to one edge, every edge takes
 //              its farthest point (LDS 64-bit max of the f64 distance's bits, lowest index among equals) and splits, points inside the
 //              new polygon drop out.  An edge is named by its start vertex and keeps its data in that point's slot, so the whole state is
 //              32 bytes per point.  Each split adds the triangle (a, f, b) to the polygon: the area is half the sum of the winners' cross
@@ -20,6 +20,7 @@
 // The thresholds, the distance cut and the component walk are a few hundred scalar operations: the workgroup whose ticket (an integer
 // vector atomic on global memory) comes last does them.  It also leaves the scratch counters zero for the next call.
 #include "cs_common.h"
+#include "hull_dev.h"
 
 namespace {
 
@@ -27,7 +28,7 @@ constexpr int GR_MAX_CAMS = 16;
 constexpr int GR_TAB = GR_MAX_CAMS * GR_MAX_CAMS;
 constexpr int GR_COUNT_THREADS = 256;
 constexpr int GR_HULL_THREADS = 1024;
-constexpr int GR_HULL_POINT_BYTES = 32;           // xy 16, label 4, best distance 8, best index 4
+constexpr int GR_HULL_POINT_BYTES = HULL_POINT_BYTES;   // (hull_dev.h)
 constexpr size_t GR_MAX_LDS = 160u * 1024u - 1024u;   // a workgroup's LDS on gfx950, less the hull kernel's static words
 constexpr int GR_REC = 336;                       // ints: gr_finish's neighbour masks, stack and cs_camera_groups record
 constexpr size_t GR_FINISH_LDS = GR_TAB * (sizeof(int) + sizeof(double)) + GR_REC * sizeof(int);   // gr_finish's tables
@@ -220,16 +221,6 @@ __global__ __launch_bounds__(GR_COUNT_THREADS) void k_group_finish(GrArgs A) {
     gr_finish(A, sTab, sCost, sRec);
 }
 
-// order-preserving 64-bit key of a double
-__device__ __forceinline__ unsigned long long gr_key(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return b >> 63 ? ~b : b | 0x8000000000000000ull;
-}
-// how far p lies OUTSIDE the edge a -> b of a counter-clockwise polygon (> 0: outside)
-__device__ __forceinline__ double gr_out(double px, double py, double ax, double ay, double bx, double by) {
-    return (px - ax) * (by - ay) - (py - ay) * (bx - ax);
-}
-
 __global__ __launch_bounds__(GR_HULL_THREADS) void k_group_hull(GrArgs A, int cap) {
     extern __shared__ double sDyn[];
     // per point: xy, the label (alive: its edge = that edge's start vertex >= 0; dead: -1; a vertex: -2 - next vertex), and in a vertex's
@@ -238,13 +229,12 @@ __global__ __launch_bounds__(GR_HULL_THREADS) void k_group_hull(GrArgs A, int ca
     unsigned long long* sBestD = (unsigned long long*)(sXY + 2 * (size_t)cap);   // [cap]
     int* sLabel = (int*)(sBestD + cap);                          // [cap]
     int* sBestI = sLabel + cap;                                  // [cap]
-    __shared__ int sWave[GR_HULL_THREADS / 64], sN, sFlag, sA, sB;
-    __shared__ unsigned long long sKey[2];
+    __shared__ int sWave[GR_HULL_THREADS / 64], sN, sFlag;
     __shared__ double sRed[GR_HULL_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nC = A.nCams, T = GR_HULL_THREADS;
     const int pi = blockIdx.x / (nC - 1), q = blockIdx.x % (nC - 1), pj = q + (q >= pi);   // the ordered pair (pi, pj), pi != pj
     const int mapCount = A.mapCount ? min(max(*A.mapCount, 0), A.nMap) : A.nMap, rows = gr_rows(A);
-    if (tid == 0) sN = 0, sKey[0] = ~0ull, sKey[1] = 0ull, sA = 0x7fffffff, sB = 0x7fffffff;
+    if (tid == 0) sN = 0;
     __syncthreads();
     // camera pi's pixels of the points both cameras hold, in row order; counted past cap, never written past it
     for (int base = 0; base < rows; base += T) {
@@ -272,80 +262,7 @@ __global__ __launch_bounds__(GR_HULL_THREADS) void k_group_hull(GrArgs A, int ca
     }
     const int nAll = sN, n = nAll < cap ? nAll : cap;
     double acc = 0.0;
-    if (nAll <= cap && n >= 3) {
-        // a first two-gon: a point of least x and a point of greatest x (lowest index among equals); both lie on the hull's boundary
-        for (int k = tid; k < n; k += T) {
-            const unsigned long long key = gr_key(sXY[2 * k]);
-            atomicMin(&sKey[0], key), atomicMax(&sKey[1], key);
-            sBestD[k] = 0ull, sBestI[k] = 0x7fffffff;
-        }
-        __syncthreads();
-        for (int k = tid; k < n; k += T) {
-            const unsigned long long key = gr_key(sXY[2 * k]);
-            if (key == sKey[0]) atomicMin(&sA, k);
-            if (key == sKey[1]) atomicMin(&sB, k);
-        }
-        __syncthreads();
-        const int a0 = sA, b0 = sB;
-        int alive = 0;
-        if (sKey[0] != sKey[1]) {   // (all x equal: a vertical line or one point, area 0)
-            const double ax = sXY[2 * a0], ay = sXY[2 * a0 + 1], bx = sXY[2 * b0], by = sXY[2 * b0 + 1];
-            for (int k = tid; k < n; k += T) {
-                const double px = sXY[2 * k], py = sXY[2 * k + 1];
-                int lab = -1;
-                if (k == a0) lab = -2 - b0;
-                else if (k == b0) lab = -2 - a0;
-                else if (gr_out(px, py, ax, ay, bx, by) > 0) lab = a0;
-                else if (gr_out(px, py, bx, by, ax, ay) > 0) lab = b0;
-                sLabel[k] = lab;
-                alive |= lab >= 0;
-            }
-        }
-        alive = __syncthreads_or(alive);
-        while (alive) {   // one Quickhull round; every edge with a point outside it splits, so a round retires at least one point per edge
-            for (int k = tid; k < n; k += T) {
-                const int e = sLabel[k];
-                if (e < 0) continue;
-                const int b = -2 - sLabel[e];
-                const double d = gr_out(sXY[2 * k], sXY[2 * k + 1], sXY[2 * e], sXY[2 * e + 1], sXY[2 * b], sXY[2 * b + 1]);
-                atomicMax(&sBestD[e], (unsigned long long)__double_as_longlong(d));   // (d > 0: its bits order as the values do)
-            }
-            __syncthreads();
-            for (int k = tid; k < n; k += T) {
-                const int e = sLabel[k];
-                if (e < 0) continue;
-                const int b = -2 - sLabel[e];
-                const double d = gr_out(sXY[2 * k], sXY[2 * k + 1], sXY[2 * e], sXY[2 * e + 1], sXY[2 * b], sXY[2 * b + 1]);
-                if ((unsigned long long)__double_as_longlong(d) == sBestD[e]) atomicMin(&sBestI[e], k);
-            }
-            __syncthreads();
-            // the alive points' new labels: only their own slots are written, only vertices' slots are read
-            alive = 0;
-            for (int k = tid; k < n; k += T) {
-                const int e = sLabel[k];
-                if (e < 0) continue;
-                const int b = -2 - sLabel[e], f = sBestI[e];
-                const double px = sXY[2 * k], py = sXY[2 * k + 1], ax = sXY[2 * e], ay = sXY[2 * e + 1], bx = sXY[2 * b], by = sXY[2 * b + 1];
-                const double fx = sXY[2 * f], fy = sXY[2 * f + 1];
-                int lab = -1;
-                if (k == f) {
-                    lab = -2 - b;                                   // the edge f -> b
-                    acc += gr_out(px, py, ax, ay, bx, by);          // twice the triangle (a, f, b) that the polygon gains
-                } else if (gr_out(px, py, ax, ay, fx, fy) > 0) lab = e;   // outside a -> f
-                else if (gr_out(px, py, fx, fy, bx, by) > 0) lab = f;     // outside f -> b
-                sLabel[k] = lab;
-                alive |= lab >= 0;
-            }
-            alive = __syncthreads_or(alive);
-            // the split edges' start vertices point at their winners; every vertex's round state is cleared
-            for (int k = tid; k < n; k += T) {
-                if (sLabel[k] > -2) continue;
-                if (sBestI[k] != 0x7fffffff) sLabel[k] = -2 - sBestI[k];
-                sBestD[k] = 0ull, sBestI[k] = 0x7fffffff;
-            }
-            __syncthreads();
-        }
-    }
+    if (nAll <= cap && n >= 3) acc = hull_quick<GR_HULL_THREADS>(sXY, sBestD, sLabel, sBestI, n);   // (the rounds: hull_dev.h)
     // the threads' sums up a fixed tree
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);

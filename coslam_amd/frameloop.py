@@ -39,6 +39,7 @@ import coslam_amd
 from coslam_amd._lib import check
 from coslam_amd.ba import BAInterCam, BAOutput, BAWindow, BAWorkspace, intercam_cams
 from coslam_amd.grouping import CameraGroups, camera_grouping_dev, camera_grouping_scratch_bytes, grouping_cams
+from coslam_amd.merge import MergeCandidates, merge_cams, merge_check_dev, merge_check_scratch_bytes
 from coslam_amd.handback import handback_cams, handback_dev
 from coslam_amd.liveview import LiveView
 from coslam_amd.keyframe import keyframe_cams, keyframe_ready_dev, keyframe_snapshot_dev
@@ -136,6 +137,11 @@ class LoopConfig:
         # is the digest with it off.  Off: nothing allocated, no launch added
         self.group_min_overlap_num, self.group_min_overlap_area_ratio = 0, 0.0   # getViewOverlapCosts(viewOverlapCost, 0, 0.0), :1635
         self.group_max_dist_ratio = 6.0   # Param::maxDistRatio (src/app/SL_GlobParam.cpp:18)
+        self.merge_check = False         # MergeCameraGroup::checkPossibleMergable at every key frame on the device (cs_merge_check_dev, reference
+        # src/app/SL_MergeCameraGroup.cpp:56-177; the gate of CoSLAM::mergeCamGroups, src/app/SL_CoSLAM.cpp:1375-1384) over that frame's group
+        # record: needs camera_grouping.  REPORTED (FrameLoop.merge_stats): nothing behind the gate is built.  It only reads loop state.
+        self.merge_min_in_num, self.merge_min_in_area_ratio = 10, 0.5   # checkPossibleMergable(10, 0.5, Param::maxDistRatio), :1380
+        self.merge_max_cam_dist = 6.0    # Param::maxDistRatio, taken as a distance (as the reference does)
         self.live_view = False           # the frame's last step (cs_liveview_frame_dev: CoSLAM::getNumDynamicStaticPoints, storeDynamicPoints,
         # reference src/app/SL_CoSLAM.cpp:1447-1471, :1900-1911, and the display's copy) at the end of the frame's pose work: the counts, the
         # dynamic points into a device ring of live_view_trail_depth frames, and every live_view_every-th frame a snapshot (poses, groups,
@@ -199,6 +205,7 @@ class FrameLoop:
         self._marks = [] if os.environ.get("FRAMELOOP_GPU_SECTIONS") else None
         # (the stages in the order of their device allocations and stream creation: the order is part of what a run computes and how fast)
         self.grouping = None
+        self.merge = None
         self.live = None
         self.setup_state(map_cov)
         self.setup_trackers(klt_cfg)
@@ -609,8 +616,12 @@ class FrameLoop:
             torch.cuda.synchronize()
         if cfg.keyframe_decision or cfg.intracam_mapping or cfg.keyframe_drives:
             self.enable_keyframe_decision(0, 0)
+        if cfg.merge_check and not cfg.camera_grouping:
+            raise ValueError("LoopConfig.merge_check needs LoopConfig.camera_grouping: the check reads the key frame's record of the groups")
         if cfg.camera_grouping:
             self._enable_camera_grouping()
+        if cfg.merge_check:
+            self._enable_merge_check()
         if cfg.live_view:
             self.live = LiveView(cfg.n_cams, cfg.live_view_cur_cap or self.n_map, cfg.live_view_dyn_cap or max(1, self.n_map // 4),
                                  depth=cfg.live_view_depth, trail_depth=cfg.live_view_trail_depth, every=cfg.live_view_every, device=self.device)
@@ -677,6 +688,88 @@ class FrameLoop:
             g["last"] = dict(frame=g["frames"][k], groups=groups, vcosts=vc[k].reshape(NA, NA).copy(), nshare=ns[k].reshape(NA, NA).copy())
         del g["frames"][:n]
         g["taken"] += n
+
+    MERGE_RING = 32   # key frames of merge-check records kept on the device; the host takes the older half over when the newer one is full
+
+    def _enable_merge_check(self):
+        """the device ring the key frames' records go into (KeyFrame::setCamGroups plus the check's result), the camera tables per pose buffer"""
+        torch, cfg, NA, z = self.torch, self.cfg, self.cfg.n_cams, self._z
+        cams = [merge_cams([dict(xy=self.d_xy[g].data_ptr(), state=self.d_state[g].data_ptr(), slot2map=self.d_slot2map[g].data_ptr(),
+                                 K=self.d_K1.data_ptr(), R=self.d_R[q][g].data_ptr(), t=self.d_t[q][g].data_ptr()) for g in range(NA)])
+                for q in range(2)]
+        self.merge = dict(cams=cams, snap_cams={}, ring=z((self.MERGE_RING, C.sizeof(MergeCandidates)), torch.uint8),
+                          scratch=z(merge_check_scratch_bytes(NA, cfg.n_feat), torch.uint8), ev=[torch.cuda.Event(), torch.cuda.Event()], calls=0,
+                          taken=0, frames=[], split=0, with_candidate=0, first_such=None, last=None)
+        torch.cuda.synchronize()   # (zero-filled on torch's stream, used on the pose stream)
+
+    def _merge_check(self, f, dst, snap=None):
+        """checkPossibleMergable of key frame f on the pose stream, at its push: the frame's records and poses as they stand (dst) or as kept
+        in `snap` for a lagged decision, the map as it stands, the group record cameraGrouping wrote for frame f.  One launch, no wait: the
+        result goes into slot calls % MERGE_RING of the device ring, read as the grouping's ring is."""
+        cfg, m, g, RING = self.cfg, self.merge, self.grouping, self.MERGE_RING
+        half = RING // 2
+        if m["calls"] - m["taken"] >= RING:
+            self._merge_take(half)
+        slot = m["calls"] % RING
+        behind = self._frame_now - f                       # (the grouping runs once per frame: frame f's record is `behind` calls back)
+        if behind < 0 or behind >= min(g["calls"], self.GROUP_RING):
+            raise RuntimeError(f"FrameLoop: the group record of key frame {f} is no longer in the ring")
+        if snap is None:
+            cams = m["cams"][dst]
+        else:
+            if id(snap) not in m["snap_cams"]:
+                NA = cfg.n_cams
+                m["snap_cams"][id(snap)] = merge_cams([dict(xy=snap["xy"][c].data_ptr(), state=snap["st"][c].data_ptr(), slot2map=snap["s2m"][c].data_ptr(),
+                                                            K=self.d_K1.data_ptr(), R=snap["R"][c].data_ptr(), t=snap["t"][c].data_ptr())
+                                                       for c in range(NA)])
+            cams = m["snap_cams"][id(snap)]
+        merge_check_dev(self.pose_s.cuda_stream, cams, cfg.n_feat, self.n_map, self.d_mapcount.data_ptr(), self.d_map.data_ptr(),
+                        self.d_mapflags.data_ptr(), cfg.W, cfg.H, g["groups"][(g["calls"] - 1 - behind) % self.GROUP_RING].data_ptr(), f,
+                        m["ring"][slot].data_ptr(), m["scratch"].data_ptr(), minInNum=cfg.merge_min_in_num,
+                        minInAreaRatio=cfg.merge_min_in_area_ratio, maxCamDist=cfg.merge_max_cam_dist, allPairs=False, device=self.device)
+        m["frames"].append(f)
+        m["calls"] += 1
+        if m["calls"] % half == 0:
+            m["ev"][(slot // half) & 1].record(self.pose_s)
+
+    def _merge_take(self, n, synced=False):
+        """the oldest n records of the ring to the host (n = half a ring behind its event, or whatever is left behind a drain)"""
+        m, RING = self.merge, self.MERGE_RING
+        if n <= 0:
+            return
+        s0 = m["taken"] % RING
+        if not synced:
+            m["ev"][(s0 // (RING // 2)) & 1].synchronize()
+        recs = m["ring"][[(s0 + k) % RING for k in range(n)]].cpu().numpy()
+        for k in range(n):
+            r = MergeCandidates.from_bytes(recs[k].tobytes())
+            m["split"] += r.groupNum > 1
+            if r.nMergeInfo > 0:
+                m["with_candidate"] += 1
+                if m["first_such"] is None:
+                    m["first_such"] = m["frames"][k]
+            m["last"] = r
+        del m["frames"][:n]
+        m["taken"] += n
+
+    def merge_stats(self):
+        """what checkPossibleMergable said over the key frames it ran on (LoopConfig.merge_check; drains the device first): key frames
+        checked, those with more than one group (only then is a pair evaluated), those with at least one MergeInfo and the first of them,
+        the last record's list [(frame1, cam1, gid1, frame2, cam2, gid2)] and tables (cs_merge_candidates, cut to the rig)."""
+        if self.merge is None:
+            return None
+        m = self.merge
+        self.torch.cuda.synchronize()
+        self._merge_take(m["calls"] - m["taken"], synced=True)
+        last = m["last"]
+        out = dict(key_frames_checked=m["taken"], key_frames_with_more_than_one_group=int(m["split"]),
+                   key_frames_with_a_candidate=m["with_candidate"], first_such_frame=m["first_such"],
+                   last_frame=None if last is None else int(last.frame), last_group_num=None if last is None else int(last.groupNum),
+                   last_info=None if last is None else [list(x) for x in last.infos()],
+                   min_in_num=self.cfg.merge_min_in_num, min_in_area_ratio=self.cfg.merge_min_in_area_ratio, max_cam_dist=self.cfg.merge_max_cam_dist)
+        if last is not None:
+            out.update({"last_" + k: v for k, v in last.tables(self.cfg.n_cams).items()})
+        return out
 
     def _live_view(self, i, dst):
         """storeDynamicPoints + the display's copy of frame i on the pose stream, behind the registration (CoSLAMThread.cpp:117-120): the
@@ -1170,6 +1263,8 @@ class FrameLoop:
         cfg, ps = self.cfg, self.pose_s.cuda_stream
         k_ic = self.n_key
         self.n_key += 1
+        if self.merge is not None:   # CoSLAM::mergeCamGroups' gate at the key frame (genNewMapPoints, src/app/SL_CoSLAM.cpp:1339-1342)
+            self._merge_check(i, dst, snap)
         if cfg.with_intercam and (k_ic + self.world // 2) % self.world == self.rank:
             # InterCamPoseEstimator::addMapPoints + apply (reference src/app/SL_InterCamPoseEstimator.cpp:18-95): every camera's CURRENT
             # pose (own: just solved; others: this frame's all-gather), the static features chosen per block with their map points

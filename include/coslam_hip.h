@@ -772,6 +772,56 @@ int cs_camera_grouping_dev(int device, void* hip_stream, int nCams, const cs_gro
                            const int* d_listCount, int W, int H, int minOverlapNum, double minOverlapAreaRatio, double* d_vcosts, int* d_nShare,
                            double* d_hullArea, void* d_scratch, double initCamTranslation, double maxDistRatio, cs_camera_groups* d_groups);
 
+/* ---- merge candidates: MergeCameraGroup::checkPossibleMergable (src/app/SL_MergeCameraGroup.cpp:56-177) ----------------------------------
+ * The gate of CoSLAM::mergeCamGroups (src/app/SL_CoSLAM.cpp:1375-1384), run at a key frame with more than one camera group; DESIGN.md 3.19.
+ * d_groups is the key frame's record of the groups (KeyFrame::setCamGroups) as cs_camera_grouping_dev wrote it, in DEVICE memory.  For every
+ * pair of groups g1 < g2, every camera i of g1 and every camera j of g2 in group order, (i, j) becomes a MergeInfo {frame, i, g1, frame, j, g2}
+ * when fromTo[i][j] && fromTo[j][i] (checkViewOverlap) and camDist[i][j] <= maxCamDist (checkCamDist: the distance of the centres -R^T t,
+ * against the caller's number taken as an ABSOLUTE distance -- the reference passes Param::maxDistRatio = 6.0 unscaled).
+ * fromTo[i][j] (checkViewOverlapFromTo): camera i's features of the key frame -- slots with state 0 or 1 whose slot2map is >= 0, below
+ * *d_mapCount (NULL: nMap) and not CS_MAP_FALSE in d_mapFlags (NULL: no point is false) -- are projected with camera j's K, R, t
+ * (d_mapPts [nMap][3]); those with 0 <= m0 < W and 0 <= m1 < H count as nInCam (no depth test).  With nInCam >= minInNum their convex hull
+ * is taken as a mask: the pixel (x, y) is set when the integer point lies inside or ON the hull polygon; a hull with fewer than three
+ * vertices (fewer than three points, all x equal, a collinear set) sets none.  Over camera j's features (the same predicate; their count is
+ * nFeat[j], the reference's totalNum) inNum counts those whose pixel ((int) x, (int) y) of the undistorted xy is set.  fromTo is
+ * inNum > 50 || inNum >= minInAreaRatio * totalNum.
+ * Only pairs of cameras of two groups are evaluated; allPairs != 0 evaluates every ordered pair (the overlap table of one group).  A pair
+ * that was not evaluated reads nInCam = inNum = -1 and fromTo = 0; nFeat of a camera of no evaluated pair reads -1; info[] behind
+ * nMergeInfo is -1; camDist is filled for every pair of the rig.  The m_lastFrmGroupMerge + 130 hold-off of mergeCamGroups is not built
+ * (nothing merges here), nor is anything behind the gate.
+ * One launch of nCams * (nCams - 1) workgroups with 32 * N bytes of LDS (N <= 5088), no host wait, no read-back; with one group and
+ * allPairs == 0 every workgroup leaves after one word.  d_scratch: cs_merge_check_scratch_bytes() bytes of device memory, ZEROED ONCE by the
+ * caller before its first use (every call leaves it zeroed); one scratch per stream.  nCams: 1..16, N >= 1, no null table or output
+ * (CS_ERR_INVALID otherwise, with cs_last_error() text and no launch). */
+typedef struct {
+    const double* xy;        /* 2N: the hand-back's undistorted pixels, x[N] then y[N] */
+    const int* state;        /* N: the hand-back's state (0 / 1: a feature of this frame) */
+    const int* slot2map;     /* N */
+    const double* K;         /* 9 */
+    const double* R;         /* 9, 3: the key frame's pose */
+    const double* t;
+} cs_merge_cam;
+typedef struct { int frame1, cam1, gid1, frame2, cam2, gid2; } cs_merge_info;   /* MergeInfo::set */
+typedef struct cs_merge_candidates {
+    int frame, groupNum, nMergeInfo, reserved;
+    cs_merge_info info[256];
+    int nFeat[16];            /* features with a non-false map point: camera c's list, and totalNum when c is the target */
+    int nInCam[16][16];       /* [i][j]; -1: pair not evaluated */
+    int inNum[16][16];        /* [i][j]; -1: not evaluated or nInCam < minInNum */
+    unsigned char fromTo[16][16];
+    double camDist[16][16];
+} cs_merge_candidates;
+size_t cs_merge_check_scratch_bytes(int nCams, int N);
+int cs_merge_check_dev(int device, void* hip_stream, int nCams, const cs_merge_cam* cams /* host array */, int N, int nMap,
+                       const int* d_mapCount, const double* d_mapPts, const unsigned char* d_mapFlags, int W, int H,
+                       const cs_camera_groups* d_groups, int frame, int minInNum, double minInAreaRatio, double maxCamDist, int allPairs,
+                       cs_merge_candidates* d_out, void* d_scratch);
+/* the same, synchronous, for a reference-shaped caller (include/shim/app/CoSLAMMergeCheck.h): the tables stay device pointers, the record
+ * comes back in HOST memory (h_out); device record and scratch are the call's own.  One launch, one wait. */
+int cs_merge_check(int device, void* hip_stream, int nCams, const cs_merge_cam* cams /* host array */, int N, int nMap, const int* d_mapCount,
+                   const double* d_mapPts, const unsigned char* d_mapFlags, int W, int H, const cs_camera_groups* d_groups, int frame,
+                   int minInNum, double minInAreaRatio, double maxCamDist, int allPairs, cs_merge_candidates* h_out);
+
 /* ---- live view: CoSLAM::getNumDynamicStaticPoints (src/app/SL_CoSLAM.cpp:1447-1471), CoSLAM::storeDynamicPoints (:1900-1911) and the
  * display's getDynTracks (src/gui/GLScenePane.cpp:19-52) -------------------------------------------------------------------------------------
  * The frame's last step (src/gui/CoSLAMThread.cpp:117-120, behind currentMapPointsRegister); DESIGN.md 3.18.  A map point TAKES PART when

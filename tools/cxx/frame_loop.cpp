@@ -13,7 +13,9 @@
 // whole-run archive behind the pose history, in frames: cs_track_history_set_archive); COSLAM_HIST_STORE (frames of pixels + poses the pose
 // history keeps: 4096, as LoopConfig.hist_store); COSLAM_CAMERA_GROUPING=1 (CoSLAM::cameraGrouping per frame behind the pose update, reported
 // under "camera_grouping": cs_camera_grouping_dev) with COSLAM_GROUP_MIN_OVERLAP_NUM (0), COSLAM_GROUP_MIN_AREA_RATIO (0.0),
-// COSLAM_GROUP_MAX_DIST_RATIO (6.0); COSLAM_LIVE_VIEW=1 (the frame's last step, cs_liveview_frame_dev: the counts, the dynamic points and
+// COSLAM_GROUP_MAX_DIST_RATIO (6.0); COSLAM_MERGE_CHECK=1 (MergeCameraGroup::checkPossibleMergable at every key frame over that frame's group
+// record, reported under "merge_check": cs_merge_check_dev; needs COSLAM_CAMERA_GROUPING=1) with COSLAM_MERGE_MIN_IN_NUM (10),
+// COSLAM_MERGE_MIN_AREA_RATIO (0.5), COSLAM_MERGE_MAX_CAM_DIST (6.0); COSLAM_LIVE_VIEW=1 (the frame's last step, cs_liveview_frame_dev: the counts, the dynamic points and
 // every COSLAM_LIVE_VIEW_EVERY-th (1) frame a snapshot, reported under "live_view") with COSLAM_LIVE_VIEW_DEPTH (8), COSLAM_LIVE_VIEW_TRAIL_DEPTH
 // (150), COSLAM_LIVE_VIEW_CUR_CAP / COSLAM_LIVE_VIEW_DYN_CAP (0: the map's capacity / a quarter of it).
 // Per frame (reference call sites in bench.py's docstring): camera-group redetect (+ prefetch of the next frame's front) on the
@@ -123,6 +125,9 @@ struct Options {
     bool grouping;           // COSLAM_CAMERA_GROUPING=1 (see FrameLoop::camera_grouping)
     int groupMinNum;         // getViewOverlapCosts(viewOverlapCost, 0, 0.0), src/app/SL_CoSLAM.cpp:1635
     double groupMinAreaRatio, groupMaxDistRatio;   // Param::maxDistRatio = 6.0 (src/app/SL_GlobParam.cpp:18)
+    bool mergeCheck;         // COSLAM_MERGE_CHECK=1 (see FrameLoop::merge_check)
+    int mergeMinInNum;       // checkPossibleMergable(10, 0.5, Param::maxDistRatio), src/app/SL_CoSLAM.cpp:1380
+    double mergeMinAreaRatio, mergeMaxCamDist;
     bool liveView;           // COSLAM_LIVE_VIEW=1 (see FrameLoop::live_view)
     int liveEvery, liveDepth, liveTrailDepth, liveCurCap, liveDynCap;
 };
@@ -162,6 +167,16 @@ static Options read_options(int argc, char** argv) {
     o.groupMinAreaRatio = gar && gar[0] ? atof(gar) : 0.0;
     const char* gdr = getenv("COSLAM_GROUP_MAX_DIST_RATIO");
     o.groupMaxDistRatio = gdr && gdr[0] ? atof(gdr) : 6.0;
+    o.mergeCheck = flag("COSLAM_MERGE_CHECK", '1');
+    o.mergeMinInNum = envi("COSLAM_MERGE_MIN_IN_NUM", 10);
+    const char* mar = getenv("COSLAM_MERGE_MIN_AREA_RATIO");
+    o.mergeMinAreaRatio = mar && mar[0] ? atof(mar) : 0.5;
+    const char* mcd = getenv("COSLAM_MERGE_MAX_CAM_DIST");
+    o.mergeMaxCamDist = mcd && mcd[0] ? atof(mcd) : 6.0;
+    if (o.mergeCheck && !o.grouping) {
+        fprintf(stderr, "COSLAM_MERGE_CHECK=1 needs COSLAM_CAMERA_GROUPING=1: the check reads the key frame's record of the groups\n");
+        exit(2);
+    }
     o.liveView = flag("COSLAM_LIVE_VIEW", '1');
     o.liveEvery = std::max(1, envi("COSLAM_LIVE_VIEW_EVERY", 1));
     o.liveDepth = std::max(2, envi("COSLAM_LIVE_VIEW_DEPTH", 8));
@@ -446,6 +461,17 @@ struct FrameLoop {
     bool grpHaveLast = false;
     cs_camera_groups grpLast;
     std::vector<double> grpLastCosts;
+    // MergeCameraGroup::checkPossibleMergable at every key frame (COSLAM_MERGE_CHECK=1), reported only: a device ring of records
+    // (KeyFrame::setCamGroups plus the check's result), read by the host as the grouping's ring is
+    static constexpr int MERGE_RING = 32;
+    cs_merge_candidates* dMrgRing = nullptr;
+    void* dMrgScratch = nullptr;
+    hipEvent_t mrgEv[2];
+    long long mrgCalls = 0, mrgTaken = 0;
+    std::vector<int> mrgFrames;
+    int mrgSplit = 0, mrgWithCandidate = 0, mrgFirstSuch = -1;
+    bool mrgHaveLast = false;
+    cs_merge_candidates mrgLast;
     // the frame's last step (COSLAM_LIVE_VIEW=1): storeDynamicPoints + the display's copy, one launch per frame on the pose stream, no wait
     cs_liveview* live = nullptr;
     int liveFrames = 0, livePublished = 0;
@@ -481,6 +507,10 @@ struct FrameLoop {
     void camera_grouping(int i, int dsti);
     void grouping_take(int n, bool synced);
     std::string grouping_json();
+    void setup_merge_check();
+    void merge_check(int f, const cs_handback_cam* cams, const double* Rk, const double* tk);
+    void merge_take(int n, bool synced);
+    std::string merge_json();
     void live_view(int i, int dsti);
     std::string live_json();
     void run(int n) {
@@ -884,6 +914,86 @@ std::string FrameLoop::grouping_json() {
     return s + "], \"init_cam_translation\": " + buf + "}";
 }
 
+// the device ring of the key frames' merge-check records
+void FrameLoop::setup_merge_check() {
+    dMrgRing = dev_zeros<cs_merge_candidates>(MERGE_RING);
+    dMrgScratch = dev_zeros<unsigned char>(cs_merge_check_scratch_bytes(nCams, N));   // (zeroed once: every call leaves it zeroed)
+    for (int h = 0; h < 2; ++h) HIPCHK(hipEventCreateWithFlags(&mrgEv[h], hipEventDisableTiming));
+}
+
+// checkPossibleMergable of key frame f at its push: the frame's records and poses (as they stand, or a lagged decision's snapshot), the map as
+// it stands, the group record cameraGrouping wrote for frame f (one grouping call per frame: frame f's is call f).  One launch, no wait
+void FrameLoop::merge_check(int f, const cs_handback_cam* cams, const double* Rk, const double* tk) {
+    const int half = MERGE_RING / 2;
+    if (mrgCalls - mrgTaken >= MERGE_RING) merge_take(half, false);
+    if (f < 1 || f > grpCalls || grpCalls - f >= GROUP_RING) {
+        fprintf(stderr, "the group record of key frame %d is no longer in the ring\n", f);
+        exit(1);
+    }
+    const int slot = (int)(mrgCalls % MERGE_RING);
+    cs_merge_cam mc[16];
+    for (int c = 0; c < nCams; ++c) mc[c] = cs_merge_cam{cams[c].xy, cams[c].state, cams[c].slot2map, dK, Rk + 9 * c, tk + 3 * c};
+    CSCHK(cs_merge_check_dev(o.dev, (void*)poseS, nCams, mc, N, nMap, dMapCount, dMap, dMapFlags, W, H, dGrpGroups + (int)((f - 1) % GROUP_RING), f,
+                             o.mergeMinInNum, o.mergeMinAreaRatio, o.mergeMaxCamDist, 0, dMrgRing + slot, dMrgScratch));
+    mrgFrames.push_back(f);
+    if (++mrgCalls % half == 0) HIPCHK(hipEventRecord(mrgEv[(slot / half) & 1], poseS));
+}
+
+// the oldest n records of the ring to the host
+void FrameLoop::merge_take(int n, bool synced) {
+    const int half = MERGE_RING / 2;
+    std::vector<cs_merge_candidates> r;
+    for (int k = 0; k < n;) {
+        const int slot = (int)((mrgTaken + k) % MERGE_RING), seg = std::min(n - k, MERGE_RING - slot);
+        if (!synced && k == 0) HIPCHK(hipEventSynchronize(mrgEv[(slot / half) & 1]));
+        r.resize(seg);
+        HIPCHK(hipMemcpyAsync(r.data(), dMrgRing + slot, sizeof(cs_merge_candidates) * seg, hipMemcpyDeviceToHost, grpCopyS));
+        HIPCHK(hipStreamSynchronize(grpCopyS));
+        for (int q = 0; q < seg; ++q) {
+            mrgSplit += r[q].groupNum > 1;
+            if (r[q].nMergeInfo > 0) {
+                ++mrgWithCandidate;
+                if (mrgFirstSuch < 0) mrgFirstSuch = mrgFrames[k + q];
+            }
+            mrgLast = r[q], mrgHaveLast = true;
+        }
+        k += seg;
+    }
+    mrgFrames.erase(mrgFrames.begin(), mrgFrames.begin() + n);
+    mrgTaken += n;
+}
+
+std::string FrameLoop::merge_json() {
+    if (!o.mergeCheck) return "null";
+    merge_take((int)(mrgCalls - mrgTaken), true);   // (behind the barrier)
+    std::string s = "{\"key_frames_checked\": " + std::to_string(mrgTaken) + ", \"key_frames_with_more_than_one_group\": " + std::to_string(mrgSplit) +
+                    ", \"key_frames_with_a_candidate\": " + std::to_string(mrgWithCandidate) + ", \"first_such_frame\": " +
+                    (mrgFirstSuch < 0 ? std::string("null") : std::to_string(mrgFirstSuch));
+    if (!mrgHaveLast) return s + ", \"last_frame\": null, \"last_group_num\": null, \"last_info\": null}";
+    s += ", \"last_frame\": " + std::to_string(mrgLast.frame) + ", \"last_group_num\": " + std::to_string(mrgLast.groupNum) + ", \"last_info\": [";
+    for (int k = 0; k < mrgLast.nMergeInfo && k < 256; ++k) {
+        const cs_merge_info& m = mrgLast.info[k];
+        s += std::string(k ? ", [" : "[") + std::to_string(m.frame1) + ", " + std::to_string(m.cam1) + ", " + std::to_string(m.gid1) + ", " +
+             std::to_string(m.frame2) + ", " + std::to_string(m.cam2) + ", " + std::to_string(m.gid2) + "]";
+    }
+    s += "], \"last_nFeat\": [";
+    for (int c = 0; c < nCams; ++c) s += (c ? ", " : "") + std::to_string(mrgLast.nFeat[c]);
+    s += "]";
+    auto table = [&](const char* name, auto at) {
+        s += std::string(", \"") + name + "\": [";
+        for (int a = 0; a < nCams; ++a) {
+            s += a ? ", [" : "[";
+            for (int b = 0; b < nCams; ++b) s += (b ? ", " : "") + std::to_string(at(a, b));
+            s += "]";
+        }
+        s += "]";
+    };
+    table("last_nInCam", [&](int a, int b) { return mrgLast.nInCam[a][b]; });
+    table("last_inNum", [&](int a, int b) { return mrgLast.inNum[a][b]; });
+    table("last_fromTo", [&](int a, int b) { return (int)mrgLast.fromTo[a][b]; });
+    return s + "}";
+}
+
 // CoSLAM::storeDynamicPoints + updateDisplayData of frame i where the reference has them (src/gui/CoSLAMThread.cpp:117-120): the tables as
 // the registration left them, the poses just written, the frame's groups when the grouping runs
 void FrameLoop::live_view(int i, int dsti) {
@@ -967,6 +1077,7 @@ void FrameLoop::first_frame() {
         HIPCHK(hipMemcpy(dKfSelfT, dT[0], sizeof(double) * 3 * nCams, hipMemcpyDeviceToDevice));
     }
     if (o.grouping) setup_camera_grouping();
+    if (o.mergeCheck) setup_merge_check();
     if (o.liveView) {
         live = cs_liveview_create(o.dev, nCams, o.liveCurCap ? o.liveCurCap : nMap, o.liveDynCap ? o.liveDynCap : std::max(1, nMap / 4), o.liveDepth,
                                   o.liveTrailDepth, o.liveEvery);
@@ -1170,6 +1281,7 @@ void FrameLoop::key_frame_actions(int f, const cs_handback_cam* cams, const doub
         CSCHK(cs_ba_solve_intercam_async(icWs, icam, (void*)poseS, icCams.data(), W, H, w.nColBlk, w.nRowBlk, dR[dsti], dT[dsti], dMap, dMapFlags,
                                          dNewPt, dPf, 6.0, 3, 40));
     ++nKey;
+    if (o.mergeCheck) merge_check(f, cams, Rk, tk);   // CoSLAM::mergeCamGroups' gate at the key frame (genNewMapPoints, :1339-1342)
     CSCHK(cs_ba_window_push_dev(win, (void*)poseS, cams, dK, 1, Rk, tk, f));
     sched.request(f, placed, dMap, dMapFlags);
 }
@@ -1272,7 +1384,7 @@ void FrameLoop::report(double dt, double dtHost, int applied0, const int rvCnt0[
     int decUnsettled = 0;   // (the decision scratch's last int: sticky "some call's sweeps did not settle")
     HIPCHK(hipMemcpy(&decUnsettled, (char*)dDecScratch + cs_register_decide_scratch_bytes(nCams, N, nMap) - sizeof(int), sizeof(int),
                      hipMemcpyDeviceToHost));
-    const std::string groupingJson = grouping_json(), liveJson = live_json();
+    const std::string groupingJson = grouping_json(), mergeJson = merge_json(), liveJson = live_json();
     const char* transport = o.world == 1 ? "none" : o.hostSegment ? "host segment (test)" : "rccl";
     printf("{\"frames_per_s\": %.3f, \"ms_per_step\": %.5f, \"steps\": %d, \"warmup\": %d, \"host_enqueue_ms_per_step\": %.5f, "
            "\"cams_per_tracker_launch\": %d, \"pose_ok\": %s, \"min_live_features\": %d, \"joint_lm_steps\": %d, \"joint_cost\": %.6f, "
@@ -1282,12 +1394,12 @@ void FrameLoop::report(double dt, double dtHost, int applied0, const int rvCnt0[
            "\"map_capacity\": %d, \"new_map_points_last_run\": %d, \"register_decisions_unsettled\": %s, \"bmerge_frames\": %d, \"current_points_beyond_the_cap\": %d, \"second_visit_rounds\": %d, \"second_visit_features_attached\": %d, "
            "\"second_visit_conflicts\": %d, \"second_visit_conflicts_in_timed_region\": %d, \"second_visit_points_beyond_the_list\": %d, "
            "\"key_frames_placed_by_the_decision\": %s, \"keyframe_lag\": %d, \"frames_run\": %d, \"windows_requested\": %lld, \"windows_applied\": %d, \"windows_not_applied_history_too_short\": %d, "
-           "\"camera_grouping\": %s, %s\"rank\": %d, \"world\": %d, \"cameras_per_rank\": %d, \"transport\": \"%s\", \"digest\": \"%016llx\"}\n",
+           "\"camera_grouping\": %s, \"merge_check\": %s, %s\"rank\": %d, \"world\": %d, \"cameras_per_rank\": %d, \"transport\": \"%s\", \"digest\": \"%016llx\"}\n",
            steps / dt, dt / steps * 1e3, steps, o.warmup, dtHost / steps * 1e3, w.camsPerLaunch, okAll ? "true" : "false", minLive,
            sj.nIterTotal, sj.cost, si.nIterTotal, si.cost, nccRuns, jC, jP, jO, o.baLag, sched.nApplied - applied0,
            cs_ba_output_wait_errors(bout), iS, iP - iS, w.nPts, mapCountNow, nMap, npCounts[0], decUnsettled ? "true" : "false", nMergeFrames, curOverflow,
            RV_ROUNDS, rvCnt[0], rvCnt[2], rvCnt[2] - rvCnt0[2], rvListCnt[1], o.kfDrives ? placedJson.c_str() : "null", o.kfDrives ? o.kfLag : 0, nDone,
-           sched.nRequested, sched.nApplied, sched.nNotApplied, groupingJson.c_str(), liveJson.c_str(), o.rank, o.world, nc, transport, digest);
+           sched.nRequested, sched.nApplied, sched.nNotApplied, groupingJson.c_str(), mergeJson.c_str(), liveJson.c_str(), o.rank, o.world, nc, transport, digest);
     fflush(stdout);
 }
 
