@@ -36,6 +36,7 @@
 // project, getProjectionCovMat, mat22Inv, mahaDist2, dist2, seqTriangulate, formEMat, getFMat, epipolarError are un-vendored
 // LibVisualSLAM (only their calls are in the reference): definitions in DESIGN.md, the same as register.hip / ncc.hip use;
 // seqTriangulate = one Kalman update of (M, cov) from the measurement with noise sigma^2 I.
+#include <atomic>
 #include <cstdlib>
 #include <vector>
 
@@ -1671,7 +1672,10 @@ __device__ __forceinline__ bool cls_solve(const ClsArgs& A, const ClsViews& V, i
     return __builtin_amdgcn_ballot_w64(fail) == 0;
 }
 // isStaticPoint (exclude < 0) / isStaticPointExclude (src/slam/SL_CoSLAMHelper.cpp:117-250)
-__device__ __noinline__ bool cls_is_static(const ClsArgs& A, const ClsFeat& F, int r, const double* Mold, double* M, double* cov, int exclude,
+// (inlined, like cls_is_dynamic: out of line they took the argument block by reference, which made the kernel copy all 1.2 KB of it into
+// every lane's private memory first and read every field back with a generic load -- rounds of the point's chain of dependent loads --
+// and M / cov travelled through private memory as well.  Inlined, the fields are scalar loads from the kernel-argument segment: DESIGN 3.9.2)
+__device__ __forceinline__ bool cls_is_static(const ClsArgs& A, const ClsFeat& F, int r, const double* Mold, double* M, double* cov, int exclude,
                                            int numFrame) {
     ClsViews V;
     V.nv = 0, V.c = 0, V.j = 0, V.s = 0;
@@ -1714,7 +1718,7 @@ __device__ __noinline__ bool cls_is_static(const ClsArgs& A, const ClsFeat& F, i
     return cls_solve(A, V, r, M, cov, true);
 }
 // isDynamicPoint (:251-312)
-__device__ __noinline__ bool cls_is_dynamic(const ClsArgs& A, const ClsFeat& F, int r, double* M, double* cov) {
+__device__ __forceinline__ bool cls_is_dynamic(const ClsArgs& A, const ClsFeat& F, int r, double* M, double* cov) {
     ClsViews V;
     V.nv = 0, V.c = 0, V.j = 0, V.s = 0;
     for (int c = 0; c < A.nCams; ++c) {
@@ -2958,12 +2962,16 @@ extern "C" int cs_feat_ref_advance_refine_dev(cs_track_history* h, void* hip_str
 // frame.  Round r reads the count round r - 1 wrote (round 0's: the decide launch's).  The search is a wave per (point, camera) pair: its answer
 // is the lexicographic minimum on (distance, slot), however the feature list is split; the walks' sweeps reach the same fixed point; the
 // mergability blocks are NT rows' worth instead of 256: every verdict is its own candidate's.  No grid barrier: nothing here can time out.
-// 1024 threads = the walks' rows: a thread per row of a list of up to RV_MAX_ROWS.  This does NOT fit beside the tracker's workgroups (they
-// leave 192 VGPRs per SIMD lane; 16 waves of 128 VGPRs need 512), no more than k_revisit_decide did: the launch starts on a compute unit
-// without tracker waves.  256 threads with several rows a thread in the walks were tried: the phases need 248-256 VGPRs a wave, which does
-// not fit either.
-constexpr int RR_THREADS = 1024;
-static_assert(RR_THREADS >= RV_MAX_ROWS, "k_revisit_rounds: a thread per listed row of the walks");
+// RR_THREADS = 256: four waves, whose registers the compiler may use in full: no spills, no private segment (1024 threads, a thread per
+// row of the longest list, capped a wave at 128 VGPRs where the phases want ~250: 776 B of scratch per lane).  The walks keep a row per
+// thread in registers while the list has at most RR_THREADS rows -- every frame behind the bootstrap -- and loop over rows whose state
+// waits in LDS for a longer one (rv_decide_rows_looped; every launch whose lists' capacity exceeds RR_THREADS carries that LDS, 36 KB
+// for 8 cameras: the loops' default capacity of 1024 does).
+// An empty launch is 4.2 us in the traced loop, with no gap behind the previous kernel -- as the 1024-thread form's was: neither waited
+// for a compute unit with room (the 24 us median once read that way sat between the empty launches and the 115 us ones, half of each;
+// the tracker's main kernel is not resident at the end of a frame's pose work, the BA workers' kernels are).  The gain is in the launches
+// with rows: 115 -> 99 us median.
+constexpr int RR_THREADS = 256;
 struct RrArgs {
     int nRounds, W, H;
     int* lists;                         // [nRounds][rv.cap]
@@ -2977,7 +2985,7 @@ struct RrArgs {
 static_assert(sizeof(RrArgs) <= 4096, "k_revisit_rounds: the arguments must fit the kernel-argument segment");
 template <int MC>
 __global__ __launch_bounds__(RR_THREADS) void k_revisit_rounds(RrArgs A) {
-    extern __shared__ double rr_pose[];   // the mergability's poses [W][12]
+    extern __shared__ double rr_pose[];   // the mergability's poses [W][12]; behind them, for lists longer than the workgroup, the walks' rows
     __shared__ MgMiss missList[RR_THREADS / MG_LPC];
     __shared__ int nMiss;
     __shared__ int sCnt[RR_THREADS / 64][5];
@@ -3018,11 +3026,14 @@ __global__ __launch_bounds__(RR_THREADS) void k_revisit_rounds(RrArgs A) {
             }
         // ---- the walks, the attach, the next round's list
         {
-            RvArgs R = A.rv;
             const bool more = r + 1 < A.nRounds;
-            R.list = list, R.listCount = A.rvCounts + r;
-            R.nextList = more ? A.lists + (size_t)(r + 1) * cap : nullptr, R.nextCount = more ? A.rvCounts + r + 1 : nullptr;
-            rv_decide_rows<MC>(R);
+            const RvRound Rd{list, A.rvCounts + r, more ? A.lists + (size_t)(r + 1) * cap : nullptr, more ? A.rvCounts + r + 1 : nullptr};
+            if (n <= RR_THREADS) {   // (uniform)
+                rv_decide_rows<MC>(A.rv, Rd);
+            } else {
+                int* rowCode = (int*)(rr_pose + 12 * (size_t)A.mg.W);
+                rv_decide_rows_looped<MC, RR_THREADS>(A.rv, Rd, n, rowCode, rowCode + MC * RV_MAX_ROWS);
+            }
         }
         __syncthreads();
         // ---- advance the listed rows' references; the rows that registered again are refined (a wave each) and their marks cleared
@@ -3052,6 +3063,29 @@ __global__ __launch_bounds__(RR_THREADS) void k_revisit_rounds(RrArgs A) {
             if (v) atomicAdd(A.ar.F.counts + tid, v);
         }
     }
+}
+// The dynamic LDS a launch of k_revisit_rounds<MC> may carry on this device: the default 64 KB for 8 cameras, the compute unit's 160 KB
+// for 16 (whose rows' state alone is 68 KB: the attribute is set when the device is first asked about, not per launch), less the kernel's own.
+template <int MC>
+static int rr_dynamic_lds_limit(int device, size_t* out) {
+    static std::atomic<long long> last{-1};   // the device last asked about and its answer (a process drives one device)
+    const long long c = last.load(std::memory_order_acquire);
+    if (c >= 0 && (int)(c >> 32) == device) {
+        *out = (size_t)(c & 0xffffffffll);
+        return CS_OK;
+    }
+    hipFuncAttributes fa;
+    CS_HIP(hipFuncGetAttributes(&fa, (const void*)k_revisit_rounds<MC>));
+    constexpr size_t total = MC == 8 ? 65536 : 163840;
+    if (fa.sharedSizeBytes >= total) {
+        cs_set_error("k_revisit_rounds<%d>: %zu B of static LDS", MC, (size_t)fa.sharedSizeBytes);
+        return CS_ERR_INVALID;
+    }
+    const size_t dyn = total - fa.sharedSizeBytes;
+    if (total > 65536) CS_HIP(hipFuncSetAttribute((const void*)k_revisit_rounds<MC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    if (device >= 0) last.store(((long long)device << 32) | (long long)dyn, std::memory_order_release);
+    *out = dyn;
+    return CS_OK;
 }
 
 extern "C" int cs_register_revisit_rounds_dev(cs_track_history* h, void* hip_stream, const cs_register_cam* regCams, const cs_poseupdate_cam* cams,
@@ -3143,6 +3177,15 @@ extern "C" int cs_register_revisit_rounds_dev(cs_track_history* h, void* hip_str
     for (int c = 0; c < nCams; ++c) R.cam[c] = cams[c];
     CS_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)hip_stream;
+    const int MC = nCams <= 8 ? 8 : RD_MAX_CAMS;
+    const size_t lds = sizeof(double) * 12 * (size_t)A.mg.W + (cap > RR_THREADS ? sizeof(int) * (size_t)(MC + 1) * RV_MAX_ROWS : 0);
+    size_t ldsMax = 0;   // (checked before anything is enqueued: a refused call leaves nothing behind)
+    if (const int rc = MC == 8 ? rr_dynamic_lds_limit<8>(h->device, &ldsMax) : rr_dynamic_lds_limit<RD_MAX_CAMS>(h->device, &ldsMax)) return rc;
+    if (lds > ldsMax) {
+        cs_set_error("cs_register_revisit_rounds_dev: %zu B of LDS (a history window of %d frames, lists of %d rows, %d cameras) where the "
+                     "launch may carry %zu", lds, A.mg.W, cap, nCams, ldsMax);
+        return CS_ERR_INVALID;
+    }
     if (nMap > h->aliveCap) {
         if (h->alive) CS_HIP(hipFree(h->alive));
         h->alive = nullptr, h->aliveCap = 0;
@@ -3152,8 +3195,7 @@ extern "C" int cs_register_revisit_rounds_dev(cs_track_history* h, void* hip_str
     }
     R.F.alive = h->alive;
     hist_centres(h, s);
-    const size_t lds = sizeof(double) * 12 * (size_t)A.mg.W;
-    if (nCams <= 8)
+    if (MC == 8)
         hipLaunchKernelGGL(k_revisit_rounds<8>, dim3(1), dim3(RR_THREADS), lds, s, A);
     else
         hipLaunchKernelGGL(k_revisit_rounds<RD_MAX_CAMS>, dim3(1), dim3(RR_THREADS), lds, s, A);

@@ -675,7 +675,7 @@ __global__ __launch_bounds__(1024) void k_revisit_list(RvListArgs A) {
 template <int MC>
 __global__ __launch_bounds__(1024) void k_revisit_decide(RvArgs A) {
     if (A.listCount && *A.listCount == 0) return;   // (uniform: before any barrier)
-    rv_decide_rows<MC>(A);
+    rv_decide_rows<MC>(A, rv_round_of(A));
 }
 
 }  // namespace

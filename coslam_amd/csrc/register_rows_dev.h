@@ -177,33 +177,31 @@ struct RvArgs {
     int debug;                       // cs_debug_set("merge_print", 1): the launch prints where its time went
 };
 constexpr int RV_MAX_ROWS = 1024;
-// MC: the cameras the row arrays are sized for (8 or MC: 16 cameras' worth of registers per thread spill at 1024 threads)
+// a round's list and the next round's: RvArgs' own fields, or (k_revisit_rounds) the round's slices of the frame's lists
+struct RvRound {
+    const int* list;
+    const int* listCount;
+    int* nextList;
+    int* nextCount;
+};
+__device__ __forceinline__ RvRound rv_round_of(const RvArgs& A) { return RvRound{A.list, A.listCount, A.nextList, A.nextCount}; }
+// owner array k mod 3 (selected, not indexed: a caller's own copy of the arguments then stays in registers)
+__device__ __forceinline__ int* rv_owner(const RvArgs& A, int k) {
+    const int r = k % 3;
+    return r == 0 ? A.owner[0] : (r == 1 ? A.owner[1] : A.owner[2]);
+}
+// ---- a row's pieces: the same code whether a thread keeps its one row in registers (rv_decide_rows) or loops over several rows whose state
+// waits in LDS between the barriers (rv_decide_rows_looped)
+// the row's loads in three rounds (the point's flags, its loop and every camera's entry together; then who owns the candidates; then those
+// owners' state) instead of up to four dependent loads per camera one camera after the other: the launch is a handful of rows' latency.
+// Leaves the row's codes and base (-1: the row does not walk), clears its candidates' owners, counts the conflicts it can see already.
 template <int MC>
-__device__ __forceinline__ void rv_decide_rows(const RvArgs& A) {
-    __shared__ int sChanged, sAttCam[256], sAttSl[256], sAttKey[256], sNAtt;
-    const int j = threadIdx.x, C = A.nCams;
-    const long long tD0 = A.debug ? wall_clock64() : 0;
-    long long tD1 = 0, tD2 = 0, tD3 = 0;
-    const int p = j < A.cap ? A.list[j] : -1;
-    int code[MC], base = -1, kind = -1, nConf = 0;
+__device__ __forceinline__ void rv_row_build(const RvArgs& A, int p, int (&code)[MC], int& base, int& nConf) {
+    const int C = A.nCams;
+    int kind = -1;
+    base = -1;
 #pragma unroll
     for (int i = 0; i < MC; ++i) code[i] = -1;
-    if (j == 0) sNAtt = 0;
-    // the conflict count's scan (at the end) compares every current point's candidates with what this round attached: the candidate rows do
-    // not change in this launch, so a thread asks for its (up to two) current points' rows NOW -- the loads travel while the walks are built
-    // and swept -- and the scan is register compares (it was 13 us of three dependent rounds of loads behind the attach, as much as the walks)
-    const int nCurPre = *A.curCount < A.curCap ? *A.curCount : A.curCap;
-    int preQ[2], preS[2][MC];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int e = j + u * (int)blockDim.x;
-        preQ[u] = e < nCurPre ? A.curList[e] : -1;
-        if (preQ[u] >= A.P) preQ[u] = -1;
-#pragma unroll
-        for (int i = 0; i < MC; ++i) preS[u][i] = preQ[u] >= 0 ? A.slot[(size_t)preQ[u] * C + (i < C ? i : 0)] : -1;
-    }
-    // the row's loads in three rounds (the point's flags, its loop and every camera's entry together; then who owns the candidates; then those
-    // owners' state) instead of up to four dependent loads per camera one camera after the other: the launch is a handful of rows' latency
     int pfv[MC], slv[MC], flv[MC], own[MC];
     unsigned char mgv[MC];
     {
@@ -253,6 +251,147 @@ __device__ __forceinline__ void rv_decide_rows(const RvArgs& A) {
         for (int i = 0; i < MC; ++i)
             if (code[i] >= 0) rd_st(A.owner[0] + (code[i] & RD_FEAT), RD_INF), rd_st(A.owner[1] + (code[i] & RD_FEAT), RD_INF), rd_st(A.owner[2] + (code[i] & RD_FEAT), RD_INF);
     }
+}
+// the three steps of a Jacobi sweep (k_decide_settle's recursion), a barrier between them
+template <int MC>
+__device__ __forceinline__ void rv_row_clear(const int (&code)[MC], int base, int* clear) {
+    if (base < 0) return;
+#pragma unroll
+    for (int i = 0; i < MC; ++i)
+        if (code[i] >= 0) rd_st(clear + (code[i] & RD_FEAT), RD_INF);
+}
+template <int MC>
+__device__ __forceinline__ void rv_row_claim(const int (&code)[MC], int base, const int* prev, int* next) {
+    if (base < 0) return;
+    bool go = true;
+#pragma unroll
+    for (int i = 0; i < MC; ++i) {
+        if (go && code[i] >= 0) {
+            const int ord = base + i, f = code[i] & RD_FEAT;
+            if ((code[i] & RD_INIT_MAPPED) || rd_ld(prev + f) < ord) go = false;
+            else if (code[i] & RD_CAN_MERGE) atomicMin(&next[f], ord);
+        }
+    }
+}
+template <int MC>
+__device__ __forceinline__ int rv_row_changed(const int (&code)[MC], int base, const int* prev, const int* next) {
+    int ch = 0;
+    if (base < 0) return ch;
+#pragma unroll
+    for (int i = 0; i < MC; ++i)
+        if (code[i] >= 0) ch |= rd_ld(next + (code[i] & RD_FEAT)) != rd_ld(prev + (code[i] & RD_FEAT));
+    return ch;
+}
+// what the round attached, for the conflict count's scan (the first 256)
+struct RvAttached {
+    int cam[256], sl[256], key[256], n;
+};
+// attach (the owners in `fin` are final); a row that registered marks itself and joins the next round's list
+template <int MC>
+__device__ __forceinline__ void rv_row_attach(const RvArgs& A, const RvRound& Rd, int p, const int (&code)[MC], int base, const int* fin, RvAttached& S, int& nAtt,
+                                              int& nReg) {
+    if (base < 0) return;
+    const int C = A.nCams;
+    bool go = true, reg = false;
+#pragma unroll
+    for (int i = 0; i < MC; ++i) {
+        if (go && code[i] >= 0) {
+            const int ord = base + i, f = code[i] & RD_FEAT, own = rd_ld(fin + f);
+            if ((code[i] & RD_INIT_MAPPED) || own < ord) {
+                go = false;
+            } else if ((code[i] & RD_CAN_MERGE) && own == ord) {
+                const int s2 = f - i * A.N;
+                A.slot2map[i][s2] = A.mapBase + p;
+                A.pointFeat[(size_t)p * C + i] = s2;
+                A.attached[(size_t)p * C + i] = 1;
+                reg = true, ++nAtt;
+                const int q = atomicAdd(&S.n, 1);
+                if (q < 256) S.cam[q] = i, S.sl[q] = s2, S.key[q] = ord;
+            }
+        }
+    }
+    if (reg) {
+        ++nReg;
+        const int last = A.nextLoop[p];
+        A.regOut[p] = 1, A.visitLoop[p] = last;
+        if (Rd.nextList) {
+            int b = -1;
+            for (int c = C - 1; c > last; --c)
+                if (A.pointFeat[(size_t)p * C + c] >= 0) b = c;
+            if (b >= 0) {
+                const int q = atomicAdd(Rd.nextCount, 1);
+                if (q < A.cap) Rd.nextList[q] = p, A.nextLoopW[p] = b;
+                else if (A.overflow) atomicAdd(A.overflow, 1);
+            }
+        }
+    }
+}
+// a feature attached here was unmapped until now: a LATER-ordered visit of this frame that had it as its candidate walked past it (it
+// could not take it) and went on to other cameras -- in the reference's order that walk ends at it.  Counted where that walk attached
+// something behind it (what it did there would not have happened).  q: a current point, qs: its candidates' slots.
+template <int MC>
+__device__ __forceinline__ void rv_conflicts_of(const RvArgs& A, int q, const int (&qs)[MC], const RvAttached& S, int nA, int& nConf) {
+    const int C = A.nCams;
+    // does ANY of the round's attachments name one of q's candidates?  (almost never: only then is q's row of features looked at)
+    bool any = false;
+    for (int a = 0; a < nA && !any; ++a) {
+        const int i = S.cam[a], sl = S.sl[a];
+#pragma unroll
+        for (int t = 0; t < MC; ++t) any |= t == i && qs[t] == sl;
+    }
+    if (!any) return;
+    int qp[MC];
+    unsigned qatt = 0;
+#pragma unroll
+    for (int i = 0; i < MC; ++i) {
+        const size_t kq = (size_t)q * C + (i < C ? i : 0);
+        qp[i] = A.pointFeat[kq];
+        if (i < C && A.attached[kq]) qatt |= 1u << i;
+    }
+    int lq = -1;   // the loop of q's (first) visit in this frame
+#pragma unroll
+    for (int i = MC - 1; i >= 0; --i)
+        if (i < C && qp[i] >= 0 && !((qatt >> i) & 1u)) lq = i;
+    if (lq < 0) return;
+    for (int a = 0; a < nA; ++a) {
+        const int i = S.cam[a], sl = S.sl[a];
+        int qsi = -1, qpi = 0;
+#pragma unroll
+        for (int t = 0; t < MC; ++t)
+            if (t == i) qsi = qs[t], qpi = qp[t];
+        if (qsi != sl || qpi >= 0) continue;
+        if ((lq * A.P + q) * C + i <= S.key[a]) continue;
+        if ((qatt >> (i + 1)) != 0u) ++nConf;   // it attached something in a camera behind the one it walked past
+    }
+}
+// MC: the cameras the row arrays are sized for (8 or RD_MAX_CAMS).  A thread per listed row.  Preconditions, the caller's: the workgroup
+// has at least as many threads as the list has LISTED rows, and the entries of the list behind the listed ones, up to A.cap, are -1 (the
+// kernels that build a list fill it so): thread j reads list[j] for every j < A.cap and takes a negative entry for "no row".  (The looped
+// form below is handed the listed count and reads no entry behind it.)
+template <int MC>
+__device__ __forceinline__ void rv_decide_rows(const RvArgs& A, const RvRound& Rd) {
+    __shared__ int sChanged;
+    __shared__ RvAttached sAtt;
+    const int j = threadIdx.x, C = A.nCams;
+    const long long tD0 = A.debug ? wall_clock64() : 0;
+    long long tD1 = 0, tD2 = 0, tD3 = 0;
+    const int p = j < A.cap ? Rd.list[j] : -1;
+    int code[MC], base = -1, nConf = 0;
+    if (j == 0) sAtt.n = 0;
+    // the conflict count's scan (at the end) compares every current point's candidates with what this round attached: the candidate rows do
+    // not change in this launch, so a thread asks for its (up to two) current points' rows NOW -- the loads travel while the walks are built
+    // and swept -- and the scan is register compares (it was 13 us of three dependent rounds of loads behind the attach, as much as the walks)
+    const int nCurPre = *A.curCount < A.curCap ? *A.curCount : A.curCap;
+    int preQ[2], preS[2][MC];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int e = j + u * (int)blockDim.x;
+        preQ[u] = e < nCurPre ? A.curList[e] : -1;
+        if (preQ[u] >= A.P) preQ[u] = -1;
+#pragma unroll
+        for (int i = 0; i < MC; ++i) preS[u][i] = preQ[u] >= 0 ? A.slot[(size_t)preQ[u] * C + (i < C ? i : 0)] : -1;
+    }
+    rv_row_build<MC>(A, p, code, base, nConf);
     __syncthreads();   // (ONE workgroup: its barrier orders the agent-scope accesses above -- an agent-scope fence here writes the XCD's L2 back, tracker's lines and all: 30-70 us a launch)
     if (A.debug) tD1 = wall_clock64();
     // Jacobi sweeps among the round's visits (k_decide_settle's recursion, one workgroup)
@@ -260,35 +399,15 @@ __device__ __forceinline__ void rv_decide_rows(const RvArgs& A) {
     const int* fin = A.owner[0];
     bool settled = false;
     for (; k < 32; ++k) {
-        const int* prev = A.owner[k % 3];
-        int* next = A.owner[(k + 1) % 3];
-        int* clear = A.owner[(k + 2) % 3];
+        const int* prev = rv_owner(A, k);
+        int* next = rv_owner(A, k + 1);
+        int* clear = rv_owner(A, k + 2);
         if (j == 0) sChanged = 0;
-        if (base >= 0) {
-#pragma unroll
-            for (int i = 0; i < MC; ++i)
-                if (code[i] >= 0) rd_st(clear + (code[i] & RD_FEAT), RD_INF);
-        }
+        rv_row_clear<MC>(code, base, clear);
         __syncthreads();
-        if (base >= 0) {
-            bool go = true;
-#pragma unroll
-            for (int i = 0; i < MC; ++i) {
-                if (go && code[i] >= 0) {
-                    const int ord = base + i, f = code[i] & RD_FEAT;
-                    if ((code[i] & RD_INIT_MAPPED) || rd_ld(prev + f) < ord) go = false;
-                    else if (code[i] & RD_CAN_MERGE) atomicMin(&next[f], ord);
-                }
-            }
-        }
+        rv_row_claim<MC>(code, base, prev, next);
         __syncthreads();
-        if (base >= 0) {
-            int ch = 0;
-#pragma unroll
-            for (int i = 0; i < MC; ++i)
-                if (code[i] >= 0) ch |= rd_ld(next + (code[i] & RD_FEAT)) != rd_ld(prev + (code[i] & RD_FEAT));
-            if (ch) sChanged = 1;
-        }
+        if (rv_row_changed<MC>(code, base, prev, next)) sChanged = 1;
         __syncthreads();
         fin = next;
         const int chg = sChanged;
@@ -299,98 +418,111 @@ __device__ __forceinline__ void rv_decide_rows(const RvArgs& A) {
         }
     }
     if (A.debug) tD2 = wall_clock64();
-    // attach (the owners in `fin` are final)
-    bool reg = false;
-    int nAtt = 0;
-    if (base >= 0) {
-        bool go = true;
-#pragma unroll
-        for (int i = 0; i < MC; ++i) {
-            if (go && code[i] >= 0) {
-                const int ord = base + i, f = code[i] & RD_FEAT, own = rd_ld(fin + f);
-                if ((code[i] & RD_INIT_MAPPED) || own < ord) {
-                    go = false;
-                } else if ((code[i] & RD_CAN_MERGE) && own == ord) {
-                    const int s2 = f - i * A.N;
-                    A.slot2map[i][s2] = A.mapBase + p;
-                    A.pointFeat[(size_t)p * C + i] = s2;
-                    A.attached[(size_t)p * C + i] = 1;
-                    reg = true, ++nAtt;
-                    const int q = atomicAdd(&sNAtt, 1);
-                    if (q < 256) sAttCam[q] = i, sAttSl[q] = s2, sAttKey[q] = ord;
-                }
-            }
-        }
-        if (reg) {
-            const int last = A.nextLoop[p];
-            A.regOut[p] = 1, A.visitLoop[p] = last;
-            if (A.nextList) {
-                int b = -1;
-                for (int c = C - 1; c > last; --c)
-                    if (A.pointFeat[(size_t)p * C + c] >= 0) b = c;
-                if (b >= 0) {
-                    const int q = atomicAdd(A.nextCount, 1);
-                    if (q < A.cap) A.nextList[q] = p, A.nextLoopW[p] = b;
-                    else if (A.overflow) atomicAdd(A.overflow, 1);
-                }
-            }
-        }
-    }
+    int nAtt = 0, nReg = 0;
+    rv_row_attach<MC>(A, Rd, p, code, base, fin, sAtt, nAtt, nReg);
     __syncthreads();
-    // a feature attached here was unmapped until now: a LATER-ordered visit of this frame that had it as its candidate walked past it (it
-    // could not take it) and went on to other cameras -- in the reference's order that walk ends at it.  Counted where that walk attached
-    // something behind it (what it did there would not have happened).
     if (A.debug) tD3 = wall_clock64();
-    const int nA = sNAtt < 256 ? sNAtt : 256;
+    const int nA = sAtt.n < 256 ? sAtt.n : 256;
     if (nA > 0) {
         const int nCur = nCurPre;
         for (int e = j, u = 0; e < nCur; e += (int)blockDim.x, ++u) {
-            const int q = u < 2 ? preQ[u < 2 ? u : 0] : A.curList[e];
+            const int q = u == 0 ? preQ[0] : (u == 1 ? preQ[1] : A.curList[e]);
             if (q < 0 || q >= A.P) continue;
             int qs[MC];
 #pragma unroll
             for (int i = 0; i < MC; ++i) qs[i] = u == 0 ? preS[0][i] : (u == 1 ? preS[1][i] : A.slot[(size_t)q * C + (i < C ? i : 0)]);
-            // does ANY of the round's attachments name one of q's candidates?  (almost never: only then is q's row of features looked at)
-            bool any = false;
-            for (int a = 0; a < nA && !any; ++a) {
-                const int i = sAttCam[a], sl = sAttSl[a];
-#pragma unroll
-                for (int t = 0; t < MC; ++t) any |= t == i && qs[t] == sl;
-            }
-            if (!any) continue;
-            int qp[MC];
-            unsigned qatt = 0;
-#pragma unroll
-            for (int i = 0; i < MC; ++i) {
-                const size_t kq = (size_t)q * C + (i < C ? i : 0);
-                qp[i] = A.pointFeat[kq];
-                if (i < C && A.attached[kq]) qatt |= 1u << i;
-            }
-            int lq = -1;   // the loop of q's (first) visit in this frame
-#pragma unroll
-            for (int i = MC - 1; i >= 0; --i)
-                if (i < C && qp[i] >= 0 && !((qatt >> i) & 1u)) lq = i;
-            if (lq < 0) continue;
-            for (int a = 0; a < nA; ++a) {
-                const int i = sAttCam[a], sl = sAttSl[a];
-                int qsi = -1, qpi = 0;
-#pragma unroll
-                for (int t = 0; t < MC; ++t)
-                    if (t == i) qsi = qs[t], qpi = qp[t];
-                if (qsi != sl || qpi >= 0) continue;
-                if ((lq * A.P + q) * C + i <= sAttKey[a]) continue;
-                if ((qatt >> (i + 1)) != 0u) ++nConf;   // it attached something in a camera behind the one it walked past
-            }
+            rv_conflicts_of<MC>(A, q, qs, sAtt, nA, nConf);
         }
     }
     if (A.debug && j == 0)
-        printf("k_revisit_decide: rows %d; build %lld us, %d sweeps %lld us, attach %lld us (%d attached), scan %lld us\n", A.listCount ? *A.listCount : -1,
+        printf("k_revisit_decide: rows %d; build %lld us, %d sweeps %lld us, attach %lld us (%d attached), scan %lld us\n", Rd.listCount ? *Rd.listCount : -1,
                (tD1 - tD0) / 100, k + 1, (tD2 - tD1) / 100, (tD3 - tD2) / 100, nA, (wall_clock64() - tD3) / 100);
     if (A.counts) {
         if (nAtt) atomicAdd(A.counts, nAtt);
-        if (reg) atomicAdd(A.counts + 1, 1);
+        if (nReg) atomicAdd(A.counts + 1, nReg);
         if (nConf) atomicAdd(A.counts + 2, nConf);
         if (j == 0 && !settled) atomicAdd(A.counts + 3, 1);
+    }
+}
+// The same round for a list LONGER than the workgroup (NT threads, n rows, n > NT: the bootstrap frames).  A thread loops over rows
+// tid, tid + NT, ... inside every phase, between the same barriers; a row's codes and base wait in LDS (rowCode [MC][RV_MAX_ROWS],
+// rowBase [RV_MAX_ROWS]: camera-major, so a wave's rows are neighbouring words).  The sweeps reach the same fixed point however rows map to
+// threads, the counters are sums, the next list is a set.  The current points' candidates are read when the scan needs them.
+template <int MC, int NT>
+__device__ __forceinline__ void rv_decide_rows_looped(const RvArgs& A, const RvRound& Rd, int n, int* rowCode, int* rowBase) {
+    __shared__ int sChanged;
+    __shared__ RvAttached sAtt;
+    const int tid = threadIdx.x, C = A.nCams;
+    int code[MC], base, nConf = 0;
+    if (tid == 0) sAtt.n = 0;
+    for (int j = tid; j < n; j += NT) {
+        rv_row_build<MC>(A, Rd.list[j], code, base, nConf);
+        rowBase[j] = base;
+#pragma unroll
+        for (int i = 0; i < MC; ++i) rowCode[i * RV_MAX_ROWS + j] = code[i];
+    }
+    __syncthreads();
+    int k = 0;
+    const int* fin = A.owner[0];
+    bool settled = false;
+    for (; k < 32; ++k) {
+        const int* prev = rv_owner(A, k);
+        int* next = rv_owner(A, k + 1);
+        int* clear = rv_owner(A, k + 2);
+        if (tid == 0) sChanged = 0;
+        for (int j = tid; j < n; j += NT) {
+#pragma unroll
+            for (int i = 0; i < MC; ++i) code[i] = rowCode[i * RV_MAX_ROWS + j];
+            rv_row_clear<MC>(code, rowBase[j], clear);
+        }
+        __syncthreads();
+        for (int j = tid; j < n; j += NT) {
+#pragma unroll
+            for (int i = 0; i < MC; ++i) code[i] = rowCode[i * RV_MAX_ROWS + j];
+            rv_row_claim<MC>(code, rowBase[j], prev, next);
+        }
+        __syncthreads();
+        int ch = 0;
+        for (int j = tid; j < n; j += NT) {
+#pragma unroll
+            for (int i = 0; i < MC; ++i) code[i] = rowCode[i * RV_MAX_ROWS + j];
+            ch |= rv_row_changed<MC>(code, rowBase[j], prev, next);
+        }
+        if (ch) sChanged = 1;
+        __syncthreads();
+        fin = next;
+        const int chg = sChanged;
+        __syncthreads();
+        if (!chg) {
+            settled = true;
+            break;
+        }
+    }
+    int nAtt = 0, nReg = 0;
+    for (int j = tid; j < n; j += NT) {
+#pragma unroll
+        for (int i = 0; i < MC; ++i) code[i] = rowCode[i * RV_MAX_ROWS + j];
+        rv_row_attach<MC>(A, Rd, Rd.list[j], code, rowBase[j], fin, sAtt, nAtt, nReg);
+    }
+    __syncthreads();
+    const int nA = sAtt.n < 256 ? sAtt.n : 256;
+    if (nA > 0) {
+        const int nCur = *A.curCount < A.curCap ? *A.curCount : A.curCap;
+        for (int e = tid; e < nCur; e += NT) {
+            const int q = A.curList[e];
+            if (q < 0 || q >= A.P) continue;
+            int qs[MC];
+#pragma unroll
+            for (int i = 0; i < MC; ++i) qs[i] = A.slot[(size_t)q * C + (i < C ? i : 0)];
+            rv_conflicts_of<MC>(A, q, qs, sAtt, nA, nConf);
+        }
+    }
+    if (A.debug && tid == 0) printf("k_revisit_rounds: rows %d in turns of %d; %d sweeps, %d attached\n", n, NT, k + 1, nA);
+    if (A.counts) {
+        if (nAtt) atomicAdd(A.counts, nAtt);
+        if (nReg) atomicAdd(A.counts + 1, nReg);
+        if (nConf) atomicAdd(A.counts + 2, nConf);
+        if (tid == 0 && !settled) atomicAdd(A.counts + 3, 1);
     }
 }
 
