@@ -26,6 +26,7 @@ HIP_SOURCES = [
     "keyframe.hip",
     "grouping.hip",
     "merge.hip",
+    "merge_graph.cpp",
     "liveview.hip",
     "poseupdate.hip",
     "ncc.hip",

@@ -1,0 +1,129 @@
+// merge_graph.cpp -- the key-frame pose graph of a camera-group merge as a host plan (no device work), DESIGN 3.20.
+//
+// Replaces MergeCameraGroup::searchFirstKeyFrameForMerge (src/app/SL_MergeCameraGroup.cpp:884-906) and the topology of
+// _constructGraphForKeyFrms (:907-1035) over host copies of the key frames' records: which key frame is held fixed, the
+// node table (key frame, camera) frame-major over the cameras of both groups, and the edges in the reference's order --
+// what cs_posegraph_create_scaled takes.  The edges' transforms are data movement around it: cs_posegraph_edges_dev for the
+// plain ones, MergeInfo::R / t for the constraint edges.
+//
+// The search loop is restated as written (:888-901):
+//   for (kf = current; kf && n <= nMaxKeyFrms && !found; kf = kf->prev) {
+//       if (kf->f >= firstConstrain->f) continue;          // skipped WITHOUT counting
+//       found = some group of kf holds both camId1 and camId2;
+//       fixed = kf; n++;                                    // the frame that ends the search BECOMES the fixed frame
+//   }
+// so up to nMaxKeyFrms + 1 older frames are visited, and with no older frame at all the reference asserts (here: an error).
+#include <cstring>
+#include <vector>
+
+#include "cs_common.h"
+
+extern "C" int cs_merge_keygraph_plan(int nKeyFrames, const int* frames, const cs_camera_groups* groups, int nCamIds, const int* camIds,
+                                      int firstConstrain, int camId1, int camId2, int nInfos, const int* infos, int nMaxKeyFrame,
+                                      int* fixedKeyFrame, int nodeCap, int* nNodes, int* nodeKf, int* nodeCam, unsigned char* fixed,
+                                      int edgeCap, int* nEdges, int* id1, int* id2, int* scaleId, int* nConstraintEdge) {
+    if (fixedKeyFrame) *fixedKeyFrame = -1;
+    if (nNodes) *nNodes = 0;
+    if (nEdges) *nEdges = 0;
+    if (nConstraintEdge) *nConstraintEdge = 0;
+    if (nKeyFrames <= 0 || !frames || !groups || nCamIds <= 0 || nCamIds > 16 || !camIds || firstConstrain < 0 ||
+        firstConstrain >= nKeyFrames || nInfos < 0 || (nInfos > 0 && !infos) || !fixedKeyFrame || !nNodes || !nEdges) {
+        cs_set_error("cs_merge_keygraph_plan: bad argument");
+        return CS_ERR_INVALID;
+    }
+    for (int k = 1; k < nKeyFrames; ++k)
+        if (frames[k] <= frames[k - 1]) {
+            cs_set_error("cs_merge_keygraph_plan: key frames must be given oldest first (frame %d behind %d)", frames[k], frames[k - 1]);
+            return CS_ERR_INVALID;
+        }
+    bool inIds[16] = {};
+    for (int i = 0; i < nCamIds; ++i) {
+        if (camIds[i] < 0 || camIds[i] >= 16 || (i > 0 && camIds[i] <= camIds[i - 1])) {
+            cs_set_error("cs_merge_keygraph_plan: camIds must be ascending camera ids below 16");
+            return CS_ERR_INVALID;
+        }
+        inIds[camIds[i]] = true;
+    }
+    auto inGroup = [](const cs_camera_groups& r, int g, int cam) {
+        for (int i = 0; i < r.num[g]; ++i)
+            if (r.camIds[g][i] == cam) return true;
+        return false;
+    };
+    // searchFirstKeyFrameForMerge
+    const int firstF = frames[firstConstrain];
+    int fx = -1, n = 0;
+    bool found = false;
+    for (int k = nKeyFrames - 1; k >= 0 && n <= nMaxKeyFrame && !found; --k) {
+        if (frames[k] >= firstF) continue;
+        for (int g = 0; g < groups[k].groupNum; ++g)
+            if (inGroup(groups[k], g, camId1) && inGroup(groups[k], g, camId2)) {
+                found = true;
+                break;
+            }
+        fx = k;
+        n++;
+    }
+    if (fx < 0) {
+        cs_set_error("cs_merge_keygraph_plan: no key frame is older than the first-constrained one (frame %d): nothing to hold fixed", firstF);
+        return CS_ERR_INVALID;
+    }
+    *fixedKeyFrame = fx;
+    // _constructGraphForKeyFrms: nodes
+    const int nK = nKeyFrames - fx, nN = nK * nCamIds;
+    int camPos[16];
+    for (int c = 0; c < 16; ++c) camPos[c] = -1;
+    for (int i = 0; i < nCamIds; ++i) camPos[camIds[i]] = i;
+    std::vector<int> e1, e2, es;
+    for (int k = fx; k < nKeyFrames; ++k) {
+        const int base = (k - fx) * nCamIds;
+        const cs_camera_groups& r = groups[k];
+        for (int g = 0; g < r.groupNum; ++g) {
+            int cams[16], m = 0;
+            for (int i = 0; i < r.num[g] && i < 16; ++i)
+                if (r.camIds[g][i] >= 0 && r.camIds[g][i] < 16 && inIds[r.camIds[g][i]]) cams[m++] = r.camIds[g][i];
+            if (m > 1 && frames[k] <= firstF) {
+                for (int i = 1; i < m; ++i) e1.push_back(base + camPos[cams[i - 1]]), e2.push_back(base + camPos[cams[i]]), es.push_back(-1);
+                if (m > 2) e1.push_back(base + camPos[cams[m - 1]]), e2.push_back(base + camPos[cams[0]]), es.push_back(-1);
+            }
+        }
+        if (k != fx)
+            for (int i = 0; i < nCamIds; ++i) e1.push_back(base - nCamIds + i), e2.push_back(base + i), es.push_back(-1);
+    }
+    auto nodeOf = [&](int frame, int cam) {
+        if (cam < 0 || cam >= 16 || camPos[cam] < 0) return -1;
+        for (int k = fx; k < nKeyFrames; ++k)
+            if (frames[k] == frame) return (k - fx) * nCamIds + camPos[cam];
+        return -1;
+    };
+    for (int i = 0; i < nInfos; ++i) {
+        const int a = nodeOf(infos[4 * i], infos[4 * i + 1]), b = nodeOf(infos[4 * i + 2], infos[4 * i + 3]);
+        if (a < 0 || b < 0 || a == b) {
+            cs_set_error("cs_merge_keygraph_plan: merge info %d (frame %d cam %d -> frame %d cam %d) does not name two nodes of the graph", i,
+                         infos[4 * i], infos[4 * i + 1], infos[4 * i + 2], infos[4 * i + 3]);
+            return CS_ERR_INVALID;
+        }
+        e1.push_back(a), e2.push_back(b), es.push_back(0);
+    }
+    *nNodes = nN;
+    *nEdges = (int)e1.size();
+    if (nConstraintEdge) *nConstraintEdge = nInfos;
+    if (nN > nodeCap || (int)e1.size() > edgeCap) {
+        cs_set_error("cs_merge_keygraph_plan: %d nodes / %d edges do not fit the capacities %d / %d", nN, (int)e1.size(), nodeCap, edgeCap);
+        return CS_ERR_INVALID;
+    }
+    if ((nN > 0 && (!nodeKf || !nodeCam || !fixed)) || (!e1.empty() && (!id1 || !id2 || !scaleId))) {
+        cs_set_error("cs_merge_keygraph_plan: null output array");
+        return CS_ERR_INVALID;
+    }
+    for (int i = 0; i < nN; ++i) {
+        nodeKf[i] = fx + i / nCamIds;
+        nodeCam[i] = camIds[i % nCamIds];
+        fixed[i] = i < nCamIds ? 1 : 0;
+    }
+    if (!e1.empty()) {
+        memcpy(id1, e1.data(), sizeof(int) * e1.size());
+        memcpy(id2, e2.data(), sizeof(int) * e2.size());
+        memcpy(scaleId, es.data(), sizeof(int) * es.size());
+    }
+    return CS_OK;
+}

@@ -27,8 +27,16 @@
 // out of an HBM workspace.  The least-squares solution is unique (full column rank), so QR on A and L D L^T of A^T A
 // agree to rounding: cond(A^T A) ~ (chain length)^2, far from 1e16.  Tolerance stated in tests/test_posegraph_gpu.py.
 //
-// Not built: edges with uncertainScale (extra scale unknowns; only src/app/SL_MergeCameraGroup.cpp:972-1025 creates them,
-// out of SURVEY 8's scope) -- the C++ shim refuses a graph that has one.
+//
+// Edges with uncertainScale (src/app/SL_MergeCameraGroup.cpp:1025-1028 creates them; computeNewCameraTranslations4, :361-525,
+// solves them) are the second half of this file (k_posegraph_relax_scaled): the translation system gains one
+// column per scale id, [N B; B^T C] with the SAME node matrix N.  N is factored once with 4 + nS right-hand sides (3
+// rotation columns, the translation, B's columns), the nS x nS Schur system is solved in one lane and the translation
+// corrected.  The plan merges the components a scale ties together and moves the ends of the scaled edges ("border
+// nodes") behind the interior, so that the interior keeps its narrow band and only the border block is dense; such a
+// component runs on one whole workgroup, no atomics, fixed summation order.  Handles without a scaled edge, and the plain
+// components of a scaled handle, run k_posegraph_relax exactly as before.
+// Not built: a one-wave natural-order path for scaled components, and the workgroup path for plain components that are wide.
 #include "cs_common.h"
 
 #include <algorithm>
@@ -315,7 +323,7 @@ __global__ void k_posegraph_edges(int nEdges, const int* __restrict__ ge1, const
                                   const double* __restrict__ nodeR, const double* __restrict__ nodeT,
                                   double* __restrict__ edgeR, double* __restrict__ edgeT) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nEdges) return;
+    if (e >= nEdges || ge1[e] < 0) return;  // < 0: an uncertain-scale edge, its transform is given
     const size_t i = (size_t)ge1[e], j = (size_t)ge2[e];
     double R1[9], R2[9], R[9];
 #pragma unroll
@@ -343,6 +351,344 @@ __global__ void k_posegraph_set_poses(int n, const int* __restrict__ nodeIdx, co
     for (int q = 0; q < 3; ++q) nodeT[3 * (size_t)node + q] = t[3 * (size_t)i + q];
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// components with uncertain-scale edges (computeNewCameraTranslations4): one workgroup per component
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int PGS_THREADS = 256;   // 4 waves
+constexpr int PGS_WAVES = PGS_THREADS / 64;
+constexpr int PGS_MAX_SCALES = 4;  // scale unknowns per component (the reference only ever uses id 0)
+constexpr int PGS_MAX_RHS = 4 + PGS_MAX_SCALES;
+// the scale solve's small LDS block: Schur matrix | right-hand side | C's diagonal | the scales | failed
+constexpr int PGS_SH_S = 0, PGS_SH_H = PGS_SH_S + PGS_MAX_SCALES * PGS_MAX_SCALES, PGS_SH_C = PGS_SH_H + PGS_MAX_SCALES,
+              PGS_SH_X = PGS_SH_C + PGS_MAX_SCALES, PGS_SH_FAIL = PGS_SH_X + PGS_MAX_SCALES, PGS_SH_DOUBLES = PGS_SH_FAIL + 1;
+
+struct PgsPlan {
+    int nComp;
+    const int* compPtr;        // nComp + 1, into compNode
+    const int* compNode;       // global node index: the component's interior nodes ascending, then its border nodes ascending
+    const int4* compDim;       // {interior nodes, border nodes, scalar half-bandwidth of the interior, scales}
+    const long long* compOff;  // < 0: LDS; else offset (doubles) of the component's workspace in `scratch`
+    const int* adjPtr;         // per node slot, into adjEnt
+    const int4* adjEnt;        // {edge, role, other end (position or -1 - global node), scale of the edge in the component or -1}
+    const int* sePtr;          // nComp + 1, into seEnt
+    const int4* seEnt;         // the scaled edges in edge order: {edge, id1's position or -1 - global, id2's, scale}
+    double* scratch;
+    int* status;               // per component: as PgPlan::status, 3 = a scale unknown is not determined
+};
+
+// Workspace W of a component (n_I = 3 * interior, n_B = 3 * border, nr = 4 + scales, nT = n_B + nr "trailing rows"):
+//   Bnd[c * ld + a]   = N[c + a][c]                     the interior's lower band, column by column (ld = w + 1)
+//   Tr[c * nT + r]    = N[n_I + r][c]        r <  n_B   the border rows over the interior columns (dense: they fill in)
+//                     = right-hand side r - n_B, row c   r >= n_B   (a right-hand side is eliminated like a matrix row)
+//   Dd[r * nT + c]    = N[n_I + r][n_I + c]  c <= r < n_B  the border block, lower triangle
+//                     = right-hand side r - n_B, row n_I + c        r >= n_B
+//   invd[c]           = 1 / pivot
+// After the solve the right-hand-side slots hold the solution.
+__device__ __forceinline__ void pgs_component(const PgsPlan& p, int k, int tid, double* W, double* sh, const double* __restrict__ nodeR,
+                                              const double* __restrict__ nodeT, const double* __restrict__ edgeR,
+                                              const double* __restrict__ edgeT, double* __restrict__ newR,
+                                              double* __restrict__ newT, double* __restrict__ edgeS) {
+    const int4 dim = p.compDim[k];
+    const int s0 = p.compPtr[k], ni = dim.x, nb = dim.y, w = dim.z, nS = dim.w;
+    const int cnt = ni + nb, nI = 3 * ni, nB = 3 * nb, nr = 4 + nS, nT = nB + nr, ld = w + 1, n = nI + nB;
+    const int wave = tid >> 6, lane = tid & 63;
+    double* Bnd = W;
+    double* Tr = Bnd + (size_t)nI * ld;
+    double* Dd = Tr + (size_t)nI * nT;
+    double* invd = Dd + (size_t)nT * nT;
+    const size_t tot = (size_t)nI * (ld + nT) + (size_t)nT * nT + n;
+    for (size_t i = tid; i < tot; i += PGS_THREADS) W[i] = 0.0;
+    __syncthreads();
+
+    // ---- normal equations, one lane per free node, its edges in edge order.  Row of an edge (i -> j, R, t):
+    //      x_j - R x_i = b, b = 0 for the rotation columns, t for the translation of a plain edge, 0 for the translation of
+    //      a scaled edge (:450-456: its t goes into the scale's column as -t), plus what a fixed end gives (:476-478, :495)
+    for (int q = tid; q < cnt; q += PGS_THREADS) {
+        const int slot = s0 + q;
+        double D[9], g[3 * PGS_MAX_RHS];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) D[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3 * PGS_MAX_RHS; ++i) g[i] = 0.0;
+        for (int e = p.adjPtr[slot]; e < p.adjPtr[slot + 1]; ++e) {
+            const int4 ent = p.adjEnt[e];
+            double Re[9], b[3 * PGS_MAX_RHS];  // b[i * PGS_MAX_RHS + rhs]
+#pragma unroll
+            for (int i = 0; i < 9; ++i) Re[i] = edgeR[9 * (size_t)ent.x + i];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const double te = edgeT[3 * (size_t)ent.x + i];
+#pragma unroll
+                for (int r = 0; r < PGS_MAX_RHS; ++r) b[PGS_MAX_RHS * i + r] = 0.0;
+                if (ent.w < 0) b[PGS_MAX_RHS * i + 3] = te;
+#pragma unroll
+                for (int r = 0; r < PGS_MAX_SCALES; ++r)
+                    if (ent.w == r) b[PGS_MAX_RHS * i + 4 + r] = -te;
+            }
+            const int z = ent.z;
+            if (ent.y == 0) {  // this node is the edge's id2
+                if (z < 0) {   // id1 fixed: + R X_1
+                    const size_t f = (size_t)(-1 - z);
+                    double X1[12];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        X1[4 * i] = nodeR[9 * f + 3 * i], X1[4 * i + 1] = nodeR[9 * f + 3 * i + 1];
+                        X1[4 * i + 2] = nodeR[9 * f + 3 * i + 2], X1[4 * i + 3] = nodeT[3 * f + i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            b[PGS_MAX_RHS * i + r] += (Re[3 * i] * X1[r] + Re[3 * i + 1] * X1[4 + r]) + Re[3 * i + 2] * X1[8 + r];
+                }
+                D[0] += 1.0, D[4] += 1.0, D[8] += 1.0;
+#pragma unroll
+                for (int i = 0; i < 3 * PGS_MAX_RHS; ++i) g[i] += b[i];
+            } else {  // this node is the edge's id1
+                if (z < 0) {  // id2 fixed: - X_2
+                    const size_t f = (size_t)(-1 - z);
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        b[PGS_MAX_RHS * i] -= nodeR[9 * f + 3 * i], b[PGS_MAX_RHS * i + 1] -= nodeR[9 * f + 3 * i + 1];
+                        b[PGS_MAX_RHS * i + 2] -= nodeR[9 * f + 3 * i + 2], b[PGS_MAX_RHS * i + 3] -= nodeT[3 * f + i];
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) D[3 * r + c] += (Re[r] * Re[c] + Re[3 + r] * Re[3 + c]) + Re[6 + r] * Re[6 + c];
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int r = 0; r < PGS_MAX_RHS; ++r)
+                        g[PGS_MAX_RHS * i + r] -= (Re[i] * b[r] + Re[3 + i] * b[PGS_MAX_RHS + r]) + Re[6 + i] * b[2 * PGS_MAX_RHS + r];
+            }
+            if (z >= 0 && z < q) {  // block (rows q, columns z): -R when this node is id2, -R^T when it is id1
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const double v = ent.y == 0 ? Re[3 * r + c] : Re[3 * c + r];
+                        if (q < ni)
+                            Bnd[(size_t)(3 * z + c) * ld + (3 * (q - z) + r - c)] -= v;
+                        else if (z < ni)
+                            Tr[(size_t)(3 * z + c) * nT + (3 * (q - ni) + r)] -= v;
+                        else
+                            Dd[(size_t)(3 * (q - ni) + r) * nT + (3 * (z - ni) + c)] -= v;
+                    }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int r = c; r < 3; ++r) {
+                if (q < ni)
+                    Bnd[(size_t)(3 * q + c) * ld + (r - c)] += D[3 * r + c];
+                else
+                    Dd[(size_t)(3 * (q - ni) + r) * nT + (3 * (q - ni) + c)] += D[3 * r + c];
+            }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int r = 0; r < PGS_MAX_RHS; ++r) {  // (unrolled: g stays in registers)
+                if (r >= nr) continue;
+                if (q < ni)
+                    Tr[(size_t)(3 * q + i) * nT + nB + r] = g[PGS_MAX_RHS * i + r];
+                else
+                    Dd[(size_t)(nB + r) * nT + (3 * (q - ni) + i)] = g[PGS_MAX_RHS * i + r];
+            }
+    }
+    __syncthreads();
+
+    // ---- L D L^T, columns unscaled (L = column / pivot).  An interior column updates its band window, the trailing rows
+    //      over the window, and the trailing block; every item reads column j only and writes elsewhere: one barrier per
+    //      unknown.  Items are dealt to the waves by row, to the lanes along the row: each sum has one owner and one order.
+    bool bad = false;
+    for (int j = 0; j < nI; ++j) {
+        const int len = min(w, nI - 1 - j);
+        double* col = Bnd + (size_t)j * ld;
+        const double* trj = Tr + (size_t)j * nT;
+        const double d = col[0];
+        if (!(d > 0.0)) bad = true;
+        const double inv = pg_rcp(d > 0.0 ? d : 1.0);
+        if (tid == 0) invd[j] = inv;
+        for (int b = 1 + wave; b <= len; b += PGS_WAVES) {
+            const double cb = col[b] * inv;
+            for (int a = b + lane; a <= len; a += 64) col[(size_t)b * ld + (a - b)] -= col[a] * cb;
+        }
+        for (int a = 1 + wave; a <= len; a += PGS_WAVES) {
+            const double ca = col[a] * inv;
+            for (int r = lane; r < nT; r += 64) {
+                const double v = trj[r];
+                if (v != 0.0) Tr[(size_t)(j + a) * nT + r] -= v * ca;
+            }
+        }
+        for (int r = wave; r < nT; r += PGS_WAVES) {
+            const double v = trj[r] * inv;
+            if (v == 0.0) continue;
+            const int cmax = min(r, nB - 1);
+            for (int c = lane; c <= cmax; c += 64) Dd[(size_t)r * nT + c] -= v * trj[c];
+        }
+        __syncthreads();
+    }
+    for (int j = 0; j < nB; ++j) {  // the border block, dense
+        const double d = Dd[(size_t)j * nT + j];
+        if (!(d > 0.0)) bad = true;
+        const double inv = pg_rcp(d > 0.0 ? d : 1.0);
+        if (tid == 0) invd[nI + j] = inv;
+        for (int r = j + 1 + wave; r < nT; r += PGS_WAVES) {
+            const double v = Dd[(size_t)r * nT + j] * inv;
+            if (v == 0.0) continue;
+            const int cmax = min(r, nB - 1);
+            for (int c = j + 1 + lane; c <= cmax; c += 64) Dd[(size_t)r * nT + c] -= v * Dd[(size_t)c * nT + j];
+        }
+        __syncthreads();
+    }
+    // ---- back substitution.  Border: one lane per right-hand side (it reads and writes its own row only) ----
+    if (tid < nr) {
+        double* x = Dd + (size_t)(nB + tid) * nT;
+        for (int c = nB - 1; c >= 0; --c) {
+            double sum = 0.0;
+            for (int c2 = c + 1; c2 < nB; ++c2) sum += Dd[(size_t)c2 * nT + c] * x[c2];
+            x[c] = (x[c] - sum) * invd[nI + c];
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < nI * nr; t += PGS_THREADS) {  // the border's part of every interior row
+        const int j = t / nr, r = t - j * nr;
+        const double* trj = Tr + (size_t)j * nT;
+        const double* x = Dd + (size_t)(nB + r) * nT;
+        double sum = 0.0;
+        for (int c = 0; c < nB; ++c) sum += trj[c] * x[c];
+        Tr[(size_t)j * nT + nB + r] -= sum;
+    }
+    __syncthreads();
+    {  // interior: lane = 4 * rhs + stripe of the band, the 4 stripes of a quad folded on the DPP path
+        const int r = tid >> 2, u = tid & 3;
+        const bool act = r < nr;
+        for (int j = nI - 1; j >= 0; --j) {
+            const int len = min(w, nI - 1 - j);
+            const double* col = Bnd + (size_t)j * ld;
+            double* gj = Tr + (size_t)j * nT + nB + (act ? r : 0);
+            double sum = 0.0;
+            if (act)
+                for (int a = 1 + u; a <= len; a += 4) sum += col[a] * gj[(size_t)a * nT];
+            sum += cs_dpp_d<0xB1, 0xf>(sum);  // quad_perm [1,0,3,2]
+            sum += cs_dpp_d<0x4E, 0xf>(sum);  // quad_perm [2,3,0,1]
+            if (act && u == 0) gj[0] = (gj[0] - sum) * invd[j];
+            __syncthreads();
+        }
+    }
+    auto sol = [&](int pos, int i, int r) -> double {
+        return pos < ni ? Tr[(size_t)(3 * pos + i) * nT + nB + r] : Dd[(size_t)(nB + r) * nT + (3 * (pos - ni) + i)];
+    };
+    // ---- the scales: with x0 = N^-1 g_t and Y = N^-1 B in hand, (C - B^T Y) s = h - B^T x0, written over the scaled edges'
+    //      rows (B^T v = sum over the scale's edges of -t . (v_j - R v_i)); one lane, edge order ----
+    if (tid == 0) {
+        // (in LDS: the edges index them by their scale, registers would go to scratch)
+        double *S = sh + PGS_SH_S, *h = sh + PGS_SH_H, *C = sh + PGS_SH_C, *sc = sh + PGS_SH_X;
+        for (int a = 0; a < PGS_MAX_SCALES; ++a) {
+            h[a] = C[a] = sc[a] = 0.0;
+            for (int b = 0; b < PGS_MAX_SCALES; ++b) S[a * PGS_MAX_SCALES + b] = 0.0;
+        }
+        for (int e = p.sePtr[k]; e < p.sePtr[k + 1]; ++e) {
+            const int4 ent = p.seEnt[e];
+            if (ent.y < 0 && ent.z < 0) continue;  // fixed-fixed: no row (:368)
+            double Re[9], te[3], rr[3];
+            for (int i = 0; i < 9; ++i) Re[i] = edgeR[9 * (size_t)ent.x + i];
+            for (int i = 0; i < 3; ++i) te[i] = edgeT[3 * (size_t)ent.x + i], rr[i] = 0.0;
+            if (ent.y < 0) {
+                const size_t f = (size_t)(-1 - ent.y);
+                for (int i = 0; i < 3; ++i) rr[i] += (Re[3 * i] * nodeT[3 * f] + Re[3 * i + 1] * nodeT[3 * f + 1]) + Re[3 * i + 2] * nodeT[3 * f + 2];
+            }
+            if (ent.z < 0) {
+                const size_t f = (size_t)(-1 - ent.z);
+                for (int i = 0; i < 3; ++i) rr[i] -= nodeT[3 * f + i];
+            }
+            double tt = (te[0] * te[0] + te[1] * te[1]) + te[2] * te[2];
+            C[ent.w] += tt;
+            S[ent.w * PGS_MAX_SCALES + ent.w] += tt;
+            for (int r = 3; r < nr; ++r) {  // (A v)_e for v = x0 and every Y column
+                double v1[3] = {0, 0, 0}, av[3];
+                if (ent.y >= 0)
+                    for (int i = 0; i < 3; ++i) v1[i] = sol(ent.y, i, r);
+                for (int i = 0; i < 3; ++i) {
+                    av[i] = -((Re[3 * i] * v1[0] + Re[3 * i + 1] * v1[1]) + Re[3 * i + 2] * v1[2]);
+                    if (ent.z >= 0) av[i] += sol(ent.z, i, r);
+                }
+                if (r == 3)
+                    h[ent.w] -= (te[0] * (rr[0] - av[0]) + te[1] * (rr[1] - av[1])) + te[2] * (rr[2] - av[2]);
+                else
+                    S[ent.w * PGS_MAX_SCALES + (r - 4)] += (te[0] * av[0] + te[1] * av[1]) + te[2] * av[2];
+            }
+        }
+        bool ok = true;  // Gaussian elimination of the small symmetric positive definite system, no pivoting
+        for (int a = 0; a < nS; ++a) {
+            const double piv = S[a * PGS_MAX_SCALES + a];
+            if (!(piv > 1e-12 * C[a])) {
+                ok = false;
+                break;
+            }
+            for (int b = a + 1; b < nS; ++b) {
+                const double f = S[b * PGS_MAX_SCALES + a] / piv;
+                for (int c = a; c < nS; ++c) S[b * PGS_MAX_SCALES + c] -= f * S[a * PGS_MAX_SCALES + c];
+                h[b] -= f * h[a];
+            }
+        }
+        if (ok)
+            for (int a = nS - 1; a >= 0; --a) {
+                double v = h[a];
+                for (int b = a + 1; b < nS; ++b) v -= S[a * PGS_MAX_SCALES + b] * sc[b];
+                sc[a] = v / S[a * PGS_MAX_SCALES + a];
+            }
+        for (int a = 0; a < PGS_MAX_SCALES; ++a) sc[a] = ok ? sc[a] : 0.0;
+        sh[PGS_SH_FAIL] = ok ? 0.0 : 1.0;
+        for (int e = p.sePtr[k]; e < p.sePtr[k + 1]; ++e) {  // CamPoseEdge::s (:515-522), fixed-fixed edges included
+            const int4 ent = p.seEnt[e];
+            edgeS[ent.x] = ok ? sc[ent.w] : 0.0;
+        }
+    }
+    __syncthreads();
+    // ---- results: rotations as in k_posegraph_relax, translation x0 - Y s ----
+    bool singular = false;
+    for (int q = tid; q < cnt; q += PGS_THREADS) {
+        const size_t node = (size_t)p.compNode[s0 + q];
+        double M[9], Q[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int a = 0; a < 3; ++a) M[3 * i + a] = sol(q, i, a);
+        if (!polar_rotation(M, Q)) singular = true;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) newR[9 * node + i] = Q[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double v = sol(q, i, 3);
+            for (int a = 0; a < nS; ++a) v -= sol(q, i, 4 + a) * sh[PGS_SH_X + a];
+            newT[3 * node + i] = v;
+        }
+    }
+    const int anySing = __syncthreads_or(singular ? 1 : 0);
+    const int st = bad ? 1 : (sh[PGS_SH_FAIL] != 0.0 ? 3 : (anySing ? 2 : 0));
+    if (tid == 0) p.status[k] = st;
+}
+
+__global__ __launch_bounds__(PGS_THREADS) void k_posegraph_relax_scaled(PgsPlan p, const double* __restrict__ nodeR,
+                                                                        const double* __restrict__ nodeT,
+                                                                        const double* __restrict__ edgeR,
+                                                                        const double* __restrict__ edgeT, double* __restrict__ newR,
+                                                                        double* __restrict__ newT, double* __restrict__ edgeS) {
+    extern __shared__ double pgs_lds[];
+    __shared__ double sh[PGS_SH_DOUBLES];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    if (k >= p.nComp) return;
+    if (p.compOff[k] < 0)
+        pgs_component(p, k, tid, pgs_lds, sh, nodeR, nodeT, edgeR, edgeT, newR, newT, edgeS);
+    else
+        pgs_component(p, k, tid, p.scratch + p.compOff[k], sh, nodeR, nodeT, edgeR, edgeT, newR, newT, edgeS);
+}
+
 int find_root(std::vector<int>& parent, int i) {
     while (parent[i] != i) {
         parent[i] = parent[parent[i]];
@@ -357,37 +703,36 @@ struct cs_posegraph {
     int device = 0;
     int nGraphs = 0, nNodes = 0, nEdges = 0, nComp = 0;
     size_t ldsBytes = 0;
+    // components with uncertain-scale edges (cs_posegraph_create_scaled); status and compGraph hold them behind the plain ones
+    int nSComp = 0, nScales = 0, nBorder = 0, maxInteriorW = 0;
+    size_t sLdsBytes = 0;
+    PgsPlan splan{};
     char* dev = nullptr;  // one allocation: plan arrays | status | workspace
     PgPlan plan{};
     std::vector<int> compGraph;  // component -> graph (error messages)
     double* dIn = nullptr;  // staging of the host form (inside `dev`)
 };
 
-extern "C" int cs_posegraph_create(int device, int nGraphs, const int* nodePtr, const int* edgePtr, const unsigned char* fixed,
-                                   const int* id1, const int* id2, cs_posegraph** out) {
+static int pg_create(const char* fn, int device, int nGraphs, const int* nodePtr, const int* edgePtr, const unsigned char* fixed,
+                     const int* id1, const int* id2, const int* scaleId, cs_posegraph** out) {
     if (!out) {
-        cs_set_error("cs_posegraph_create: null out pointer");
+        cs_set_error("%s: null out pointer", fn);
         return CS_ERR_INVALID;
     }
     *out = nullptr;
     if (nGraphs < 0 || !nodePtr || !edgePtr || nodePtr[0] != 0 || edgePtr[0] != 0) {
-        cs_set_error("cs_posegraph_create: bad graph table");
+        cs_set_error("%s: bad graph table", fn);
         return CS_ERR_INVALID;
     }
     for (int g = 0; g < nGraphs; ++g)
         if (nodePtr[g + 1] < nodePtr[g] || edgePtr[g + 1] < edgePtr[g]) {
-            cs_set_error("cs_posegraph_create: nodePtr / edgePtr must be non-decreasing (graph %d)", g);
+            cs_set_error("%s: nodePtr / edgePtr must be non-decreasing (graph %d)", fn, g);
             return CS_ERR_INVALID;
         }
     const int N = nGraphs ? nodePtr[nGraphs] : 0, E = nGraphs ? edgePtr[nGraphs] : 0;
     if ((N > 0 && !fixed) || (E > 0 && (!id1 || !id2))) {
-        cs_set_error("cs_posegraph_create: null pointer");
+        cs_set_error("%s: null pointer", fn);
         return CS_ERR_INVALID;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        cs_set_error("cs_posegraph_create: no usable HIP device %d (there is no CPU fallback)", device);
-        return CS_ERR_NO_DEVICE;
     }
     // global ends of the edges, connected components of the free nodes (fixed nodes cut the graph)
     std::vector<int> ge1(E), ge2(E), parent(N);
@@ -396,8 +741,8 @@ extern "C" int cs_posegraph_create(int device, int nGraphs, const int* nodePtr, 
         const int nb = nodePtr[g], nn = nodePtr[g + 1] - nb;
         for (int e = edgePtr[g]; e < edgePtr[g + 1]; ++e) {
             if (id1[e] < 0 || id1[e] >= nn || id2[e] < 0 || id2[e] >= nn || id1[e] == id2[e]) {
-                cs_set_error("cs_posegraph_create: edge %d of graph %d joins nodes %d -> %d (graph has %d nodes)", e - edgePtr[g], g,
-                             id1[e], id2[e], nn);
+                cs_set_error("%s: edge %d of graph %d joins nodes %d -> %d (graph has %d nodes)", fn, e - edgePtr[g], g, id1[e],
+                             id2[e], nn);
                 return CS_ERR_INVALID;
             }
             ge1[e] = nb + id1[e];
@@ -408,15 +753,56 @@ extern "C" int cs_posegraph_create(int device, int nGraphs, const int* nodePtr, 
             }
         }
     }
+    // uncertain-scale edges: a scale ties the components of its edges' free ends together; those components leave the plain plan
+    std::vector<unsigned char> inScaled(N, 0);
+    std::vector<int> scaleAnchor(E, -1);  // per edge slot edgePtr[g] + id: a free node of scale id of graph g
+    bool anyScaled = false;
+    if (scaleId) {
+        for (int g = 0; g < nGraphs; ++g) {
+            const int eb = edgePtr[g], ne = edgePtr[g + 1] - eb;
+            for (int e = eb; e < eb + ne; ++e) {
+                const int sid = scaleId[e];
+                if (sid < 0) continue;
+                if (sid >= ne) {
+                    cs_set_error("%s: edge %d of graph %d has scale id %d, the graph has %d edges (ids must be below the edge count)", fn,
+                                 e - eb, g, sid, ne);
+                    return CS_ERR_INVALID;
+                }
+                anyScaled = true;
+                for (int end = 0; end < 2; ++end) {
+                    const int nd = end ? ge2[e] : ge1[e];
+                    if (fixed[nd]) continue;
+                    if (scaleAnchor[eb + sid] < 0) scaleAnchor[eb + sid] = nd;
+                    const int a = find_root(parent, scaleAnchor[eb + sid]), b = find_root(parent, nd);
+                    if (a != b) parent[std::max(a, b)] = std::min(a, b);
+                }
+            }
+            for (int e = eb; e < eb + ne; ++e)
+                if (scaleId[e] >= 0 && scaleAnchor[eb + scaleId[e]] < 0) {
+                    cs_set_error("%s: scale id %d of graph %d is used by edges between fixed nodes only (a zero column)", fn, scaleId[e], g);
+                    return CS_ERR_INVALID;
+                }
+        }
+        if (anyScaled) {
+            std::vector<unsigned char> rootScaled(N, 0);
+            for (int e = 0; e < E; ++e)
+                if (scaleId[e] >= 0) {
+                    if (!fixed[ge1[e]]) rootScaled[find_root(parent, ge1[e])] = 1;
+                    if (!fixed[ge2[e]]) rootScaled[find_root(parent, ge2[e])] = 1;
+                }
+            for (int i = 0; i < N; ++i)
+                if (!fixed[i] && rootScaled[find_root(parent, i)]) inScaled[i] = 1;
+        }
+    }
     std::vector<int> compOfRoot(N, -1), nodeSlot(N, -1), nodePos(N, -1), compPtr(1, 0), compNode, compGraph;
     int nComp = 0;
+    std::vector<int> graphOf(N);
+    for (int g = 0; g < nGraphs; ++g)
+        for (int i = nodePtr[g]; i < nodePtr[g + 1]; ++i) graphOf[i] = g;
     {
-        std::vector<int> graphOf(N);
-        for (int g = 0; g < nGraphs; ++g)
-            for (int i = nodePtr[g]; i < nodePtr[g + 1]; ++i) graphOf[i] = g;
         std::vector<int> compCount;
         for (int i = 0; i < N; ++i) {
-            if (fixed[i]) continue;
+            if (fixed[i] || inScaled[i]) continue;
             const int r = find_root(parent, i);
             if (compOfRoot[r] < 0) {
                 compOfRoot[r] = nComp++;
@@ -429,7 +815,7 @@ extern "C" int cs_posegraph_create(int device, int nGraphs, const int* nodePtr, 
         compNode.resize(compPtr.back());
         std::vector<int> fill(compPtr.begin(), compPtr.end() - 1);
         for (int i = 0; i < N; ++i) {
-            if (fixed[i]) continue;
+            if (fixed[i] || inScaled[i]) continue;
             const int c = compOfRoot[find_root(parent, i)];
             nodePos[i] = fill[c] - compPtr[c];
             nodeSlot[i] = fill[c];
@@ -473,23 +859,116 @@ extern "C" int cs_posegraph_create(int device, int nGraphs, const int* nodePtr, 
             scratchDoubles += need;
         }
     }
+    // ---- the components with scaled edges: interior nodes in node order (frame-major for a merge graph: the band stays
+    //      narrow), the ends of the scaled edges behind them as the dense border ----
+    int nSComp = 0, nScalesTotal = 0, nBorderTotal = 0, maxInteriorW = 0;
+    std::vector<int> sCompPtr(1, 0), sCompNode, sAdjPtr(1, 0), sePtr(1, 0), sCompGraph;
+    std::vector<int4> sCompDim, sAdjEnt, seEnt;
+    std::vector<long long> sCompOff;
+    size_t sLdsDoubles = 0;
+    if (anyScaled) {
+        std::vector<int> sCompOf(N, -1), sPos(N, -1);
+        std::vector<unsigned char> border(N, 0);
+        for (int e = 0; e < E; ++e)
+            if (scaleId[e] >= 0) border[ge1[e]] = border[ge2[e]] = 1;
+        std::vector<std::vector<int>> members;
+        for (int i = 0; i < N; ++i) {
+            if (!inScaled[i]) continue;
+            const int r = find_root(parent, i);
+            if (sCompOf[r] < 0) {
+                sCompOf[r] = nSComp++;
+                members.emplace_back();
+                sCompGraph.push_back(graphOf[i]);
+            }
+            members[sCompOf[r]].push_back(i);
+        }
+        auto compOfNode = [&](int nd) { return sCompOf[find_root(parent, nd)]; };
+        std::vector<std::vector<int>> compScales(nSComp), compEdges(nSComp);
+        for (int g = 0; g < nGraphs; ++g)
+            for (int e = edgePtr[g]; e < edgePtr[g + 1]; ++e) {
+                const int f1 = !fixed[ge1[e]] && inScaled[ge1[e]], f2 = !fixed[ge2[e]] && inScaled[ge2[e]];
+                int c = f1 ? compOfNode(ge1[e]) : (f2 ? compOfNode(ge2[e]) : -1);
+                if (scaleId[e] >= 0) {
+                    c = compOfNode(scaleAnchor[edgePtr[g] + scaleId[e]]);
+                    compScales[c].push_back(scaleId[e]);
+                }
+                if (c >= 0) compEdges[c].push_back(e);
+            }
+        for (int c = 0; c < nSComp; ++c) {
+            std::vector<int>& sc = compScales[c];
+            std::sort(sc.begin(), sc.end());
+            sc.erase(std::unique(sc.begin(), sc.end()), sc.end());  // ascending by id: the reference's column order (:397-403)
+            if ((int)sc.size() > PGS_MAX_SCALES) {
+                cs_set_error("%s: a component of graph %d has %d scale unknowns, at most %d are supported", fn, sCompGraph[c], (int)sc.size(),
+                             PGS_MAX_SCALES);
+                return CS_ERR_INVALID;
+            }
+            int ni = 0, nb = 0;
+            for (int nd : members[c])
+                if (!border[nd]) sPos[nd] = ni++, sCompNode.push_back(nd);
+            for (int nd : members[c])
+                if (border[nd]) sPos[nd] = ni + nb++, sCompNode.push_back(nd);
+            sCompPtr.push_back((int)sCompNode.size());
+            int bw = 0;
+            std::vector<std::vector<int4>> adj(ni + nb);
+            for (int e : compEdges[c]) {
+                const int a = ge1[e], b = ge2[e], pa = fixed[a] ? -1 - a : sPos[a], pb = fixed[b] ? -1 - b : sPos[b];
+                const int ls = scaleId[e] < 0 ? -1 : (int)(std::lower_bound(sc.begin(), sc.end(), scaleId[e]) - sc.begin());
+                if (pa >= 0 && pb >= 0 && pa < ni && pb < ni) bw = std::max(bw, std::abs(pa - pb));
+                if (pb >= 0) adj[pb].push_back(make_int4(e, 0, pa, ls));
+                if (pa >= 0) adj[pa].push_back(make_int4(e, 1, pb, ls));
+                if (ls >= 0) seEnt.push_back(make_int4(e, pa, pb, ls));
+            }
+            sePtr.push_back((int)seEnt.size());
+            for (auto& v : adj) {
+                sAdjEnt.insert(sAdjEnt.end(), v.begin(), v.end());
+                sAdjPtr.push_back((int)sAdjEnt.size());
+            }
+            const int nI = 3 * ni, nB = 3 * nb, nS = (int)sc.size(), nT = nB + 4 + nS, w = ni ? std::min(3 * bw + 2, nI - 1) : 0;
+            sCompDim.push_back(make_int4(ni, nb, w, nS));
+            const size_t need = (size_t)nI * (w + 1 + nT) + (size_t)nT * nT + nI + nB;
+            if (need <= (size_t)PG_LDS_DOUBLES) {
+                sCompOff.push_back(-1);
+                sLdsDoubles = std::max(sLdsDoubles, need);
+            } else {
+                sCompOff.push_back((long long)scratchDoubles);
+                scratchDoubles += need;
+            }
+            nScalesTotal += nS, nBorderTotal += nb, maxInteriorW = std::max(maxInteriorW, w);
+        }
+        for (int i = 0; i < N; ++i)
+            if (inScaled[i]) nodeSlot[i] = 0;  // the kernel's tail only asks "fixed?" of this array
+        compGraph.insert(compGraph.end(), sCompGraph.begin(), sCompGraph.end());
+    }
+    // (the device is asked for only here: a graph that is refused is refused with or without one)
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+        cs_set_error("%s: no usable HIP device %d (there is no CPU fallback)", fn, device);
+        return CS_ERR_NO_DEVICE;
+    }
     cs_posegraph* G = new (std::nothrow) cs_posegraph();
     if (!G) {
-        cs_set_error("cs_posegraph_create: out of memory");
+        cs_set_error("%s: out of memory", fn);
         return CS_ERR_ALLOC;
     }
     G->device = device;
     G->nGraphs = nGraphs, G->nNodes = N, G->nEdges = E, G->nComp = nComp;
     G->ldsBytes = ldsDoubles * sizeof(double);
     G->compGraph = compGraph;
+    G->nSComp = nSComp, G->nScales = nScalesTotal, G->nBorder = nBorderTotal, G->maxInteriorW = maxInteriorW;
+    G->sLdsBytes = sLdsDoubles * sizeof(double);
     // one device block
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t oCompPtr = 0, oCompNode = oCompPtr + pad(4 * (size_t)(nComp + 1)), oCompW = oCompNode + pad(4 * (size_t)nFree),
                  oCompOff = oCompW + pad(4 * (size_t)nComp), oAdjPtr = oCompOff + pad(8 * (size_t)nComp),
                  oAdjEnt = oAdjPtr + pad(4 * (size_t)(nFree + 1)), oNodeSlot = oAdjEnt + pad(16 * adjEnt.size()),
-                 oGe1 = oNodeSlot + pad(4 * (size_t)N), oGe2 = oGe1 + pad(4 * (size_t)E), oStatus = oGe2 + pad(4 * (size_t)E),
-                 oScratch = oStatus + pad(4 * (size_t)std::max(nComp, 1)), planBytes = oScratch,
-                 oStage = oScratch + pad(8 * scratchDoubles), total = oStage + pad(8 * (24 * (size_t)N + 12 * (size_t)E));
+                 oGe1 = oNodeSlot + pad(4 * (size_t)N), oGe2 = oGe1 + pad(4 * (size_t)E), oSCompPtr = oGe2 + pad(4 * (size_t)E),
+                 oSCompNode = oSCompPtr + pad(4 * sCompPtr.size()), oSCompDim = oSCompNode + pad(4 * sCompNode.size()),
+                 oSCompOff = oSCompDim + pad(16 * sCompDim.size()), oSAdjPtr = oSCompOff + pad(8 * sCompOff.size()),
+                 oSAdjEnt = oSAdjPtr + pad(4 * sAdjPtr.size()), oSePtr = oSAdjEnt + pad(16 * sAdjEnt.size()),
+                 oSeEnt = oSePtr + pad(4 * sePtr.size()), oStatus = oSeEnt + pad(16 * seEnt.size()),
+                 oScratch = oStatus + pad(4 * (size_t)std::max(nComp + nSComp, 1)), planBytes = oScratch,
+                 oStage = oScratch + pad(8 * scratchDoubles), total = oStage + pad(8 * (24 * (size_t)N + 13 * (size_t)E));
     std::vector<char> h(planBytes, 0);
     auto put = [&](size_t off, const void* src, size_t bytes) {
         if (bytes) memcpy(h.data() + off, src, bytes);
@@ -501,13 +980,24 @@ extern "C" int cs_posegraph_create(int device, int nGraphs, const int* nodePtr, 
     put(oAdjPtr, adjPtr.data(), 4 * (size_t)(nFree + 1));
     put(oAdjEnt, adjEnt.data(), 16 * adjEnt.size());
     put(oNodeSlot, nodeSlot.data(), 4 * (size_t)N);
+    if (anyScaled)  // the scaled edges' rows of edgeR / edgeT are the caller's (MergeInfo::R, t): cs_posegraph_edges_dev skips them
+        for (int e = 0; e < E; ++e)
+            if (scaleId[e] >= 0) ge1[e] = -1;
     put(oGe1, ge1.data(), 4 * (size_t)E);
     put(oGe2, ge2.data(), 4 * (size_t)E);
+    put(oSCompPtr, sCompPtr.data(), 4 * sCompPtr.size());
+    put(oSCompNode, sCompNode.data(), 4 * sCompNode.size());
+    put(oSCompDim, sCompDim.data(), 16 * sCompDim.size());
+    put(oSCompOff, sCompOff.data(), 8 * sCompOff.size());
+    put(oSAdjPtr, sAdjPtr.data(), 4 * sAdjPtr.size());
+    put(oSAdjEnt, sAdjEnt.data(), 16 * sAdjEnt.size());
+    put(oSePtr, sePtr.data(), 4 * sePtr.size());
+    put(oSeEnt, seEnt.data(), 16 * seEnt.size());
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipMalloc((void**)&G->dev, total);
     if (e == hipSuccess) e = hipMemcpy(G->dev, h.data(), planBytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        cs_set_error("cs_posegraph_create: %s", hipGetErrorString(e));
+        cs_set_error("%s: %s", fn, hipGetErrorString(e));
         if (G->dev) (void)hipFree(G->dev);
         delete G;
         return CS_ERR_HIP;
@@ -525,8 +1015,42 @@ extern "C" int cs_posegraph_create(int device, int nGraphs, const int* nodePtr, 
     p.ge2 = (const int*)(G->dev + oGe2);
     p.status = (int*)(G->dev + oStatus);
     p.scratch = (double*)(G->dev + oScratch);
-    G->dIn = (double*)(G->dev + oStage);  // staging of the host form: nodeR | nodeT | edgeR | edgeT | newR | newT
+    G->dIn = (double*)(G->dev + oStage);  // staging of the host form: nodeR | nodeT | edgeR | edgeT | newR | newT | edgeS
+    PgsPlan& sp = G->splan;
+    sp.nComp = nSComp;
+    sp.compPtr = (const int*)(G->dev + oSCompPtr);
+    sp.compNode = (const int*)(G->dev + oSCompNode);
+    sp.compDim = (const int4*)(G->dev + oSCompDim);
+    sp.compOff = (const long long*)(G->dev + oSCompOff);
+    sp.adjPtr = (const int*)(G->dev + oSAdjPtr);
+    sp.adjEnt = (const int4*)(G->dev + oSAdjEnt);
+    sp.sePtr = (const int*)(G->dev + oSePtr);
+    sp.seEnt = (const int4*)(G->dev + oSeEnt);
+    sp.scratch = p.scratch;
+    sp.status = p.status + nComp;
     *out = G;
+    return CS_OK;
+}
+
+extern "C" int cs_posegraph_create(int device, int nGraphs, const int* nodePtr, const int* edgePtr, const unsigned char* fixed,
+                                   const int* id1, const int* id2, cs_posegraph** out) {
+    return pg_create("cs_posegraph_create", device, nGraphs, nodePtr, edgePtr, fixed, id1, id2, nullptr, out);
+}
+
+extern "C" int cs_posegraph_create_scaled(int device, int nGraphs, const int* nodePtr, const int* edgePtr, const unsigned char* fixed,
+                                          const int* id1, const int* id2, const int* scaleId, cs_posegraph** out) {
+    return pg_create(scaleId ? "cs_posegraph_create_scaled" : "cs_posegraph_create", device, nGraphs, nodePtr, edgePtr, fixed, id1, id2,
+                     scaleId, out);
+}
+
+extern "C" int cs_posegraph_scaled_counts(const cs_posegraph* g, int* nScales, int* nBorderNodes, int* maxInteriorHalfBandwidth) {
+    if (!g) {
+        cs_set_error("cs_posegraph_scaled_counts: null handle");
+        return CS_ERR_INVALID;
+    }
+    if (nScales) *nScales = g->nScales;
+    if (nBorderNodes) *nBorderNodes = g->nBorder;
+    if (maxInteriorHalfBandwidth) *maxInteriorHalfBandwidth = g->maxInteriorW;
     return CS_OK;
 }
 
@@ -544,14 +1068,14 @@ extern "C" int cs_posegraph_counts(const cs_posegraph* g, int* nNodes, int* nEdg
     }
     if (nNodes) *nNodes = g->nNodes;
     if (nEdges) *nEdges = g->nEdges;
-    if (nComponents) *nComponents = g->nComp;
+    if (nComponents) *nComponents = g->nComp + g->nSComp;
     if (maxHalfBandwidth) {
         std::vector<int> w(g->nComp);
         if (g->nComp) {
             CS_HIP(hipSetDevice(g->device));
             CS_HIP(hipMemcpy(w.data(), g->plan.compW, 4 * (size_t)g->nComp, hipMemcpyDeviceToHost));
         }
-        *maxHalfBandwidth = g->nComp ? *std::max_element(w.begin(), w.end()) : 0;
+        *maxHalfBandwidth = std::max(g->nComp ? *std::max_element(w.begin(), w.end()) : 0, g->maxInteriorW);
     }
     return CS_OK;
 }
@@ -594,12 +1118,43 @@ extern "C" int cs_posegraph_relax_dev(cs_posegraph* g, void* hip_stream, const d
         cs_set_error("cs_posegraph_relax_dev: the new poses must not alias the node poses (free nodes read their fixed neighbours)");
         return CS_ERR_INVALID;
     }
+    if (g->nSComp) {
+        cs_set_error("cs_posegraph_relax_dev: the handle has uncertain-scale edges, use cs_posegraph_relax_scaled_dev");
+        return CS_ERR_INVALID;
+    }
     if (g->nNodes == 0) return CS_OK;
     CS_HIP(hipSetDevice(g->device));
     const int grid = g->nComp + (g->nNodes + 63) / 64;
     hipLaunchKernelGGL(k_posegraph_relax, dim3(grid), dim3(64), g->ldsBytes, (hipStream_t)hip_stream, g->plan, d_nodeR, d_nodeT, d_edgeR,
                        d_edgeT, d_newR, d_newT);
     CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+extern "C" int cs_posegraph_relax_scaled_dev(cs_posegraph* g, void* hip_stream, const double* d_nodeR, const double* d_nodeT,
+                                             const double* d_edgeR, const double* d_edgeT, double* d_newR, double* d_newT,
+                                             double* d_edgeS) {
+    if (!g || (g->nNodes > 0 && (!d_nodeR || !d_nodeT || !d_newR || !d_newT)) || (g->nEdges > 0 && (!d_edgeR || !d_edgeT || !d_edgeS))) {
+        cs_set_error("cs_posegraph_relax_scaled_dev: null pointer");
+        return CS_ERR_INVALID;
+    }
+    if (d_newR == d_nodeR || d_newT == d_nodeT) {
+        cs_set_error("cs_posegraph_relax_scaled_dev: the new poses must not alias the node poses (free nodes read their fixed neighbours)");
+        return CS_ERR_INVALID;
+    }
+    if (g->nNodes == 0) return CS_OK;
+    CS_HIP(hipSetDevice(g->device));
+    if (g->nEdges) CS_HIP(hipMemsetAsync(d_edgeS, 0, sizeof(double) * (size_t)g->nEdges, (hipStream_t)hip_stream));
+    // the plain components and the fixed nodes: the launch of cs_posegraph_relax_dev
+    const int grid = g->nComp + (g->nNodes + 63) / 64;
+    hipLaunchKernelGGL(k_posegraph_relax, dim3(grid), dim3(64), g->ldsBytes, (hipStream_t)hip_stream, g->plan, d_nodeR, d_nodeT, d_edgeR,
+                       d_edgeT, d_newR, d_newT);
+    CS_CHECK_LAUNCH();
+    if (g->nSComp) {
+        hipLaunchKernelGGL(k_posegraph_relax_scaled, dim3(g->nSComp), dim3(PGS_THREADS), g->sLdsBytes, (hipStream_t)hip_stream, g->splan,
+                           d_nodeR, d_nodeT, d_edgeR, d_edgeT, d_newR, d_newT, d_edgeS);
+        CS_CHECK_LAUNCH();
+    }
     return CS_OK;
 }
 
@@ -611,12 +1166,12 @@ extern "C" int cs_posegraph_status(cs_posegraph* g, void* hip_stream, int* nFail
     if (nFailed) *nFailed = 0;
     if (firstFailedGraph) *firstFailedGraph = -1;
     CS_HIP(hipSetDevice(g->device));
-    std::vector<int> st(g->nComp);
-    if (g->nComp)
-        CS_HIP(hipMemcpyAsync(st.data(), g->plan.status, 4 * (size_t)g->nComp, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
+    const int nAll = g->nComp + g->nSComp;
+    std::vector<int> st(nAll);
+    if (nAll) CS_HIP(hipMemcpyAsync(st.data(), g->plan.status, 4 * (size_t)nAll, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
     CS_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
     int bad = 0, first = -1, code = 0;
-    for (int c = 0; c < g->nComp; ++c)
+    for (int c = 0; c < nAll; ++c)
         if (st[c]) {
             if (first < 0) first = g->compGraph[c], code = st[c];
             ++bad;
@@ -625,7 +1180,9 @@ extern "C" int cs_posegraph_status(cs_posegraph* g, void* hip_stream, int* nFail
     if (firstFailedGraph) *firstFailedGraph = first;
     if (bad) {
         cs_set_error("pose-graph relaxation: %d component(s) failed, first in graph %d (%s)", bad, first,
-                     code == 1 ? "a free node is not constrained by any edge" : "a solved 3x3 block is singular");
+                     code == 1   ? "a free node is not constrained by any edge"
+                     : code == 3 ? "a scale unknown is not determined: the translations of its edges are zero or dependent"
+                                 : "a solved 3x3 block is singular");
         return CS_ERR_NUMERIC;
     }
     return CS_OK;
@@ -653,6 +1210,32 @@ extern "C" int cs_posegraph_relax(cs_posegraph* g, const double* nodeR, const do
     if (rc != CS_OK) return rc;
     CS_HIP(hipMemcpyAsync(newR, d + inD, 9 * N * 8, hipMemcpyDeviceToHost, s));
     CS_HIP(hipMemcpyAsync(newT, d + inD + 9 * N, 3 * N * 8, hipMemcpyDeviceToHost, s));
+    rc = cs_posegraph_status(g, s, nullptr, nullptr);  // synchronises the stream
+    return rc;
+}
+
+extern "C" int cs_posegraph_relax_scaled(cs_posegraph* g, const double* nodeR, const double* nodeT, const double* edgeR,
+                                         const double* edgeT, double* newR, double* newT, double* edgeS) {
+    if (!g || (g->nNodes > 0 && (!nodeR || !nodeT || !newR || !newT)) || (g->nEdges > 0 && (!edgeR || !edgeT || !edgeS))) {
+        cs_set_error("cs_posegraph_relax_scaled: null pointer");
+        return CS_ERR_INVALID;
+    }
+    if (g->nNodes == 0) return CS_OK;
+    CS_HIP(hipSetDevice(g->device));
+    const size_t N = g->nNodes, E = g->nEdges, inD = 12 * N + 12 * E;
+    double* d = g->dIn;
+    hipStream_t s = nullptr;
+    CS_HIP(hipMemcpyAsync(d, nodeR, 9 * N * 8, hipMemcpyHostToDevice, s));
+    CS_HIP(hipMemcpyAsync(d + 9 * N, nodeT, 3 * N * 8, hipMemcpyHostToDevice, s));
+    if (E) {
+        CS_HIP(hipMemcpyAsync(d + 12 * N, edgeR, 9 * E * 8, hipMemcpyHostToDevice, s));
+        CS_HIP(hipMemcpyAsync(d + 12 * N + 9 * E, edgeT, 3 * E * 8, hipMemcpyHostToDevice, s));
+    }
+    int rc = cs_posegraph_relax_scaled_dev(g, s, d, d + 9 * N, d + 12 * N, d + 12 * N + 9 * E, d + inD, d + inD + 9 * N, d + inD + 12 * N);
+    if (rc != CS_OK) return rc;
+    CS_HIP(hipMemcpyAsync(newR, d + inD, 9 * N * 8, hipMemcpyDeviceToHost, s));
+    CS_HIP(hipMemcpyAsync(newT, d + inD + 9 * N, 3 * N * 8, hipMemcpyDeviceToHost, s));
+    if (E) CS_HIP(hipMemcpyAsync(edgeS, d + inD + 12 * N, E * 8, hipMemcpyDeviceToHost, s));
     rc = cs_posegraph_status(g, s, nullptr, nullptr);  // synchronises the stream
     return rc;
 }

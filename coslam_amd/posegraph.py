@@ -1,7 +1,8 @@
 """Pose-graph relaxation of the non-key frames after a bundle adjustment (cs_posegraph_*): GlobalPoseGraph::
 computeNewCameraRotations + computeNewCameraTranslations (reference src/slam/SL_GlobalPoseEstimation.cpp:52-359) for all
 camera graphs in one launch, as RobustBundleRTS::updateNonKeyCameraPoses (src/app/SL_CoSLAMRobustBA.cpp:230-247) needs
-them after every BA."""
+them after every BA.  With scale_ids: computeNewCameraTranslations4 (:361-525) in place of computeNewCameraTranslations, the
+key-frame graph of a camera-group merge (cs_posegraph_create_scaled / cs_posegraph_relax_scaled)."""
 import ctypes as C
 
 import numpy as np
@@ -11,9 +12,11 @@ from ._lib import check, lib
 
 class PoseGraphs:
     """Topology of nGraphs pose graphs (cs_posegraph).  graphs: list of (fixed uint8[n], id1 int[e], id2 int[e]) with ids
-    local to the graph -- CamPoseNode::fixed, CamPoseEdge::id1, id2."""
+    local to the graph -- CamPoseNode::fixed, CamPoseEdge::id1, id2.  scale_ids: per graph None (all edges plain) or int[e],
+    < 0 a plain edge, >= 0 an uncertain-scale constraint edge sharing that scale unknown of its graph (CamPoseEdge::scaleId);
+    relax() then also returns the edges' solved scales."""
 
-    def __init__(self, graphs, device=0):
+    def __init__(self, graphs, device=0, scale_ids=None):
         self.device = int(device)
         self.node_ptr = np.zeros(len(graphs) + 1, dtype=np.int32)
         self.edge_ptr = np.zeros(len(graphs) + 1, dtype=np.int32)
@@ -31,6 +34,15 @@ class PoseGraphs:
         self.n_nodes, self.n_edges = int(self.node_ptr[-1]), int(self.edge_ptr[-1])
         self._h = C.c_void_p()
         p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+        self.scale_id = None
+        if scale_ids is not None:
+            assert len(scale_ids) == len(graphs)
+            sid = [np.full(len(a[g]), -1, np.int32) if s is None else np.asarray(s, dtype=np.int32).reshape(-1) for g, s in enumerate(scale_ids)]
+            assert all(len(x) == len(y) for x, y in zip(sid, a))
+            self.scale_id = cat(sid, np.int32)
+            check(lib().cs_posegraph_create_scaled(self.device, len(graphs), p(self.node_ptr), p(self.edge_ptr), p(self.fixed), p(self.id1),
+                                                   p(self.id2), p(self.scale_id), C.byref(self._h)), "cs_posegraph_create_scaled")
+            return
         check(lib().cs_posegraph_create(self.device, len(graphs), p(self.node_ptr), p(self.edge_ptr), p(self.fixed), p(self.id1),
                                         p(self.id2), C.byref(self._h)), "cs_posegraph_create")
 
@@ -47,21 +59,37 @@ class PoseGraphs:
         check(lib().cs_posegraph_counts(self._h, *[C.byref(x) for x in v]), "cs_posegraph_counts")
         return dict(zip(("nodes", "edges", "components", "max_half_bandwidth"), [x.value for x in v]))
 
+    def scaled_counts(self):
+        """dict(scales, border_nodes, max_interior_half_bandwidth) (cs_posegraph_scaled_counts)"""
+        v = [C.c_int() for _ in range(3)]
+        check(lib().cs_posegraph_scaled_counts(self._h, *[C.byref(x) for x in v]), "cs_posegraph_scaled_counts")
+        return dict(zip(("scales", "border_nodes", "max_interior_half_bandwidth"), [x.value for x in v]))
+
     def global_ends(self):
         """(ge1, ge2): the edges' ends as indices into the flat node arrays"""
         base = np.repeat(self.node_ptr[:-1], np.diff(self.edge_ptr))
         return self.id1 + base, self.id2 + base
 
     def relax(self, nodeR, nodeT, edgeR, edgeT):
-        """host arrays in and out (cs_posegraph_relax): returns (newR [N,9], newT [N,3])"""
+        """host arrays in and out (cs_posegraph_relax): returns (newR [N,9], newT [N,3]), with scale_ids (newR, newT, edgeS [E])"""
         nodeR = np.ascontiguousarray(nodeR, dtype=np.float64).reshape(self.n_nodes, 9)
         nodeT = np.ascontiguousarray(nodeT, dtype=np.float64).reshape(self.n_nodes, 3)
         edgeR = np.ascontiguousarray(edgeR, dtype=np.float64).reshape(self.n_edges, 9)
         edgeT = np.ascontiguousarray(edgeT, dtype=np.float64).reshape(self.n_edges, 3)
         newR, newT = np.zeros((self.n_nodes, 9)), np.zeros((self.n_nodes, 3))
         p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+        if self.scale_id is not None:
+            edgeS = np.zeros(self.n_edges)
+            check(lib().cs_posegraph_relax_scaled(self._h, p(nodeR), p(nodeT), p(edgeR), p(edgeT), p(newR), p(newT), p(edgeS)),
+                  "cs_posegraph_relax_scaled")
+            return newR, newT, edgeS
         check(lib().cs_posegraph_relax(self._h, p(nodeR), p(nodeT), p(edgeR), p(edgeT), p(newR), p(newT)), "cs_posegraph_relax")
         return newR, newT
+
+    def relax_scaled_dev(self, stream_ptr, d_nodeR, d_nodeT, d_edgeR, d_edgeT, d_newR, d_newT, d_edgeS):
+        vp = C.c_void_p
+        check(lib().cs_posegraph_relax_scaled_dev(self._h, vp(stream_ptr), vp(d_nodeR), vp(d_nodeT), vp(d_edgeR), vp(d_edgeT), vp(d_newR),
+                                                  vp(d_newT), vp(d_edgeS)), "cs_posegraph_relax_scaled_dev")
 
     def relax_dev(self, stream_ptr, d_nodeR, d_nodeT, d_edgeR, d_edgeT, d_newR, d_newT):
         vp = C.c_void_p

@@ -410,3 +410,93 @@ def make_pose_graphs(n_cams=8, n_frames=21, key_every=5, rot_adj=0.01, trans_adj
         eR.append(R.reshape(9)), eT.append(t)
     out["edgeR"], out["edgeT"] = np.array(eR), np.array(eT)
     return out
+
+
+def make_merge_pose_graph(n_cams=2, n_key=3, first_constrain=1, split=1, seed=0, scale=0.4, frames_per_interval=0, rot_drift=0.01,
+                          trans_drift=0.05, noise=0.002):
+    """The key-frame graph of a camera-group merge the way MergeCameraGroup::_constructGraphForKeyFrms builds it (reference
+    src/app/SL_MergeCameraGroup.cpp:907-1035), as records for merge_keygraph_plan: n_cams cameras x n_key key frames, cameras
+    [0, split) and [split, n_cams) two groups from key frame 1 on (one group in key frame 0).  The second group drifts apart after
+    key frame first_constrain; the constraint edges (merge infos) join the first group's cameras in that frame to the second group's
+    in the current (last) key frame, and the groups' first cameras in the current frame.  Their R / t come from the TRUE poses, t
+    multiplied by the arbitrary factor `scale` (a relative pose from two views knows no scale) plus a little noise.
+    frames_per_interval > 0 adds the per-camera chains of ALL frames (_constructGraphForAllFrms, :1037-1082).
+    Returns dict(frames, groups, cam_ids, first_constrain, camid1, camid2, infos, fixed, id1, id2, scale_id, node_kf, node_cam,
+    nodeR, nodeT (drifted), truthR, truthT, edgeR, edgeT [, chains=dict(graphs, nodeR, nodeT, key_node, node_ptr, edge_ptr)])."""
+    rng = np.random.default_rng(seed)
+    step = max(1, int(frames_per_interval))
+    n_all = (n_key - 1) * step + 1
+    truthR, truthT, curR, curT = [], [], [], []
+    for c in range(n_cams):
+        w = rng.uniform(-0.3, 0.3, 3)
+        p = np.array([rng.uniform(-2, 2), rng.uniform(-2, 2), 4 + rng.uniform(-1, 1)])
+        dw, dp = rng.uniform(-0.05, 0.05, 3) / step, rng.uniform(-0.3, 0.3, 3) / step
+        dwd, dpd = np.zeros(3), np.zeros(3)
+        tr, tt, cr, ct = [], [], [], []
+        for i in range(n_all):
+            R = rodrigues(w)
+            tr.append(R), tt.append(p.copy())
+            if c >= split and i > first_constrain * step:
+                dwd = dwd + rng.uniform(-rot_drift, rot_drift, 3) / step
+                dpd = dpd + trans_drift * rng.uniform(0.5, 1.5, 3) / step
+            cr.append(rodrigues(dwd) @ R), ct.append(p + dpd)
+            dw = dw + rng.uniform(-0.01, 0.01, 3) / step
+            dp = dp + rng.uniform(-0.05, 0.05, 3) / step
+            w, p = w + dw, p + dp
+        truthR.append(tr), truthT.append(tt), curR.append(cr), curT.append(ct)
+    frames = [10 * step * k for k in range(n_key)]
+    cam_ids = list(range(n_cams))
+    groups = [[cam_ids] if k == 0 else [g for g in (cam_ids[:split], cam_ids[split:]) if g] for k in range(n_key)]
+    L, F = n_key - 1, first_constrain
+    infos = [(frames[F], i, frames[L], split + i) for i in range(split) if split + i < n_cams]
+    infos.append((frames[L], 0, frames[L], split))
+    if n_cams - split > 1:
+        infos.append((frames[F], 0, frames[L], n_cams - 1))
+    # topology exactly as the reference's loops (restated again in tests/mergegraph_ref.py and in cs_merge_keygraph_plan)
+    node = lambda k, c: k * n_cams + c  # noqa: E731
+    id1, id2, sid = [], [], []
+    for k in range(n_key):
+        for g in groups[k]:
+            if len(g) > 1 and k <= F:
+                for i in range(1, len(g)):
+                    id1.append(node(k, g[i - 1])), id2.append(node(k, g[i])), sid.append(-1)
+                if len(g) > 2:
+                    id1.append(node(k, g[-1])), id2.append(node(k, g[0])), sid.append(-1)
+        if k > 0:
+            for c in cam_ids:
+                id1.append(node(k - 1, c)), id2.append(node(k, c)), sid.append(-1)
+    kf_of = {f: k for k, f in enumerate(frames)}
+    for (f1, c1, f2, c2) in infos:
+        id1.append(node(kf_of[f1], c1)), id2.append(node(kf_of[f2], c2)), sid.append(0)
+    node_kf = np.repeat(np.arange(n_key), n_cams).astype(np.int32)
+    node_cam = np.tile(np.arange(n_cams), n_key).astype(np.int32)
+    pick = lambda a: np.array([a[c][k * step] for k, c in zip(node_kf, node_cam)])  # noqa: E731
+    nodeR, nodeT, tR, tT = pick(curR).reshape(-1, 9), pick(curT), pick(truthR).reshape(-1, 9), pick(truthT)
+    eR, eT = [], []
+    for e in range(len(id1)):
+        src_R, src_T = (tR, tT) if sid[e] >= 0 else (nodeR, nodeT)
+        Ra, Rb = src_R[id1[e]].reshape(3, 3), src_R[id2[e]].reshape(3, 3)
+        R = Rb @ Ra.T
+        t = src_T[id2[e]] - R @ src_T[id1[e]]
+        if sid[e] >= 0:
+            R = rodrigues(rng.uniform(-noise, noise, 3)) @ R
+            t = scale * (t + rng.uniform(-noise, noise, 3))
+        eR.append(R.reshape(9)), eT.append(t)
+    fixed = (node_kf == 0).astype(np.uint8)
+    out = dict(frames=frames, groups=groups, cam_ids=cam_ids, first_constrain=F, camid1=0, camid2=split, infos=infos, fixed=fixed,
+               id1=np.array(id1, np.int32), id2=np.array(id2, np.int32), scale_id=np.array(sid, np.int32), node_kf=node_kf, node_cam=node_cam,
+               nodeR=nodeR, nodeT=nodeT, truthR=tR, truthT=tT, edgeR=np.array(eR), edgeT=np.array(eT))
+    if frames_per_interval > 0:
+        graphs, cR, cT = [], [], []
+        key_node = np.zeros(n_key * n_cams, np.int32)
+        for c in range(n_cams):
+            fx = np.zeros(n_all, np.uint8)
+            fx[::step] = 1
+            graphs.append((fx, np.arange(n_all - 1, dtype=np.int32), np.arange(1, n_all, dtype=np.int32)))
+            for k in range(n_key):
+                key_node[node(k, c)] = c * n_all + k * step
+            cR += [r.reshape(9) for r in curR[c]]
+            cT += curT[c]
+        out["chains"] = dict(graphs=graphs, nodeR=np.array(cR), nodeT=np.array(cT), key_node=key_node,
+                             node_ptr=np.arange(n_cams + 1, dtype=np.int32) * n_all, edge_ptr=np.arange(n_cams + 1, dtype=np.int32) * (n_all - 1))
+    return out

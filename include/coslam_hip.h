@@ -822,6 +822,23 @@ int cs_merge_check(int device, void* hip_stream, int nCams, const cs_merge_cam* 
                    const double* d_mapPts, const unsigned char* d_mapFlags, int W, int H, const cs_camera_groups* d_groups, int frame,
                    int minInNum, double minInAreaRatio, double maxCamDist, int allPairs, cs_merge_candidates* h_out);
 
+/* ---- the key-frame graph of a merge: MergeCameraGroup::searchFirstKeyFrameForMerge (src/app/SL_MergeCameraGroup.cpp:884-906) and the
+ * topology of _constructGraphForKeyFrms (:907-1035); host code, no device; DESIGN.md 3.20 ----
+ * In: the key frames oldest first (the last one is the current key frame): frames[k] their frame numbers, groups[k] their records; camIds
+ * (getCamIdsInBothGroups: ascending); firstConstrain = index of m_pFirstConstrainFrm; camId1 / camId2 = m_camid1 / m_camid2; infos [nInfos][4]
+ * = {frame1, cam1, frame2, cam2} of the VALID merge infos, frame numbers; nMaxKeyFrame = the search's argument (the reference passes 100).
+ * The search is restated as written: frames >= the first-constrained one are skipped without counting, the frame in which both cameras
+ * share a group becomes the fixed frame, and the count test is n <= nMaxKeyFrame.
+ * Out: *fixedKeyFrame (index; CS_ERR_INVALID where the reference asserts on a null m_pFixedKeyFrm); the node table nodeKf / nodeCam
+ * frame-major over camIds from the fixed key frame on, fixed[] = the fixed frame's nodes; id1 / id2 / scaleId in the reference's edge order
+ * (per key frame and group the chain over the group's cameras that are in camIds, in the group's order, plus the closing edge of more than
+ * two, only up to the first-constrained frame; then that frame's successive-frame edges; the constraint edges last with scale id 0);
+ * *nConstraintEdge.  *nNodes / *nEdges are always set; counts beyond nodeCap / edgeCap are CS_ERR_INVALID (call again with room). */
+int cs_merge_keygraph_plan(int nKeyFrames, const int* frames, const cs_camera_groups* groups, int nCamIds, const int* camIds,
+                           int firstConstrain, int camId1, int camId2, int nInfos, const int* infos, int nMaxKeyFrame, int* fixedKeyFrame,
+                           int nodeCap, int* nNodes, int* nodeKf, int* nodeCam, unsigned char* fixed, int edgeCap, int* nEdges, int* id1,
+                           int* id2, int* scaleId, int* nConstraintEdge);
+
 /* ---- live view: CoSLAM::getNumDynamicStaticPoints (src/app/SL_CoSLAM.cpp:1447-1471), CoSLAM::storeDynamicPoints (:1900-1911) and the
  * display's getDynTracks (src/gui/GLScenePane.cpp:19-52) -------------------------------------------------------------------------------------
  * The frame's last step (src/gui/CoSLAMThread.cpp:117-120, behind currentMapPointsRegister); DESIGN.md 3.18.  A map point TAKES PART when
@@ -1072,7 +1089,7 @@ int cs_pose_update_classify_frame_dev(cs_track_history* h, void* hip_stream, con
  * Topology is given once (create): nGraphs graphs, graph g owns nodes [nodePtr[g], nodePtr[g+1]) and edges
  * [edgePtr[g], edgePtr[g+1]) of the flat arrays; id1 / id2 are node indices LOCAL to the edge's graph (CamPoseEdge::id1,
  * id2); fixed[i] != 0 is CamPoseNode::fixed.  Any topology is accepted (band width follows the node order; CoSLAM's
- * chains give the minimum).  Edges with CamPoseEdge::uncertainScale are not supported (the shim refuses them).
+ * chains give the minimum).  Edges with CamPoseEdge::uncertainScale go through cs_posegraph_create_scaled (below).
  * Values per call, row-major: nodeR [N][9], nodeT [N][3] (CamPoseNode::R, t), edgeR [E][9], edgeT [E][3] (CamPoseEdge::R, t)
  * -> newR [N][9], newT [N][3] (CamPoseNode::newR, newt; fixed nodes are copied).  new* must not alias node*.
  * A free node that no edge constrains makes its graph fail: cs_posegraph_status / the host form return CS_ERR_NUMERIC. */
@@ -1097,6 +1114,31 @@ int cs_posegraph_edges_dev(cs_posegraph* g, void* hip_stream, const double* d_no
                            double* d_edgeT);
 int cs_posegraph_set_poses_dev(int device, void* hip_stream, int n, const int* d_nodeIdx, const double* d_R, const double* d_t,
                                double* d_nodeR, double* d_nodeT);
+/* Uncertain-scale constraint edges: GlobalPoseGraph::computeNewCameraTranslations4 (src/slam/SL_GlobalPoseEstimation.cpp:
+ * 361-525) behind computeNewCameraRotations, as MergeCameraGroup::recomputeKeyCamPoses runs them on the key-frame graph of
+ * two camera groups about to merge (src/app/SL_MergeCameraGroup.cpp:1083-1086).  scaleId[e] (one per edge, flat like id1) < 0
+ * is a plain edge; >= 0 is an edge whose translation is known up to a scale (CamPoseEdge::uncertainScale and ::constraint,
+ * MergeInfo::R / t) and that shares scale unknown scaleId[e] of ITS graph (CamPoseEdge::scaleId) with every other edge of
+ * that id: it asks for t_2 = R t_1 + s t.  Rotations treat every edge alike.  The translation unknowns are 3 per free node
+ * plus one per distinct scale id in use, ascending by id.  scaleId == NULL is cs_posegraph_create.
+ * Refused at create (CS_ERR_INVALID): a scale id >= the graph's edge count; a scale id that only edges between two fixed
+ * nodes use (a zero column); more than 4 scale unknowns in one connected component (a scale joins the components of its
+ * edges into one).  The reference only ever uses id 0.
+ * Components without a scaled edge are solved exactly as by cs_posegraph_relax_dev, bit for bit; a component with one runs
+ * on one workgroup, its scaled edges' ends ("border nodes") ordered behind the other ("interior") nodes.
+ * edgeS [E]: the solved scale of every uncertain-scale edge (CamPoseEdge::s), 0 for a plain edge.  A scale whose edges do
+ * not determine it (all t == 0) fails its graph: CS_ERR_NUMERIC from cs_posegraph_status / the host form, other graphs
+ * of the launch are solved.  cs_posegraph_relax_dev / cs_posegraph_relax refuse a handle that has a scaled edge;
+ * cs_posegraph_edges_dev leaves the rows of scaled edges as the caller wrote them; _status, _counts (components: the merged
+ * ones), _destroy take either handle.
+ * cs_posegraph_scaled_counts: scale unknowns and border nodes of the whole handle, and the largest interior half-bandwidth. */
+int cs_posegraph_create_scaled(int device, int nGraphs, const int* nodePtr, const int* edgePtr, const unsigned char* fixed,
+                               const int* id1, const int* id2, const int* scaleId, cs_posegraph** out);
+int cs_posegraph_relax_scaled_dev(cs_posegraph* g, void* hip_stream, const double* d_nodeR, const double* d_nodeT,
+                                  const double* d_edgeR, const double* d_edgeT, double* d_newR, double* d_newT, double* d_edgeS);
+int cs_posegraph_relax_scaled(cs_posegraph* g, const double* nodeR, const double* nodeT, const double* edgeR, const double* edgeT,
+                              double* newR, double* newT, double* edgeS);
+int cs_posegraph_scaled_counts(const cs_posegraph* g, int* nScales, int* nBorderNodes, int* maxInteriorHalfBandwidth);
 /* The non-key-frame update of RobustBundleRTS::output() as a follow-up of the BA (cs_ba_set_followup(b,
  * cs_posegraph_after_ba, &rec)): scatter the adjusted key poses d_Rs / d_Ts (cs_ba_result_buffers) into the nodes d_camNode
  * names (one entry per BA camera, < 0 = not a node), then relax all graphs -- two launches behind the solve's last kernel.
