@@ -465,7 +465,10 @@ __global__ __launch_bounds__(256) void k_np_reconstruct(NpArgs A) {
                 for (int kk = 0; kk < 2; ++kk) {
                     const int c = r + NP_LPT * kk, k = c - c0;   // column c; the view there, if any
                     const int kSafe = (k >= 0 && k < nv) ? k : 0;
-                    const int sv = __shfl(np_pick_i(vs0, vs1, kSafe >= NP_LPT), gbase + (kSafe & (NP_LPT - 1)), 64);
+                    // (a shuffle's operand is the SOURCE lane's: both of its views come over, the READER picks by its own k)
+                    const int src = gbase + (kSafe & (NP_LPT - 1));
+                    const int sv0 = __shfl(vs0, src, 64), sv1 = __shfl(vs1, src, 64);
+                    const int sv = np_pick_i(sv0, sv1, kSafe >= NP_LPT);
                     if (c < C) A.pointFeat[(size_t)m * C + c] = (k >= 0 && k < nv) ? sv : -1;
                 }
 #pragma unroll

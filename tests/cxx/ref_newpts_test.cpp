@@ -10,6 +10,7 @@
 // cameras, features matched INTO but not onward); the names matchBetween needs are defined here as aborts so that the class links.
 // Certain-dynamic map points with features of this frame drive decidePointType's mask (a new uncertain point with a feature within
 // 20 pixels of one stays uncertain, every other becomes certain static: setLocalStatic() clears bUncertain).
+// Four scenes: 4, 3 and 6 cameras 1.4 m apart, then 12 cameras 0.35 m apart with nearly every link kept (tracks of nine and more views).
 //   ref_newpts_test golden <out.bin>
 // out.bin (int32 / float64): nScenes; per scene: nc N frame W H; K[9]; per camera R[9] t[3]; per camera xy[2N] (x then y),
 // isStatic[N] (int32: FeaturePoint::type == STATIC), nDynFeat, dynXY[nDynFeat][2] (features of this frame on CERTAIN dynamic map
@@ -54,7 +55,9 @@ static void put(FILE* f, const std::vector<T>& v) {
 }
 static void puti(FILE* f, int v) { fwrite(&v, 4, 1, f); }
 
-static int scene(FILE* f, int nc, int N, int nDynPts) {
+// spacing: metres between neighbouring cameras' centres; pLink: a true correspondence becomes a match; pDrop: a visible scene point gets no
+// feature in a camera
+static int scene(FILE* f, int nc, int N, int nDynPts, double spacing, double pLink, double pDrop) {
     const int W = 640, H = 480, frame = 57;
     const double K[9] = {0.82 * W, 0, W / 2.0, 0, 0.82 * W, H / 2.0, 0, 0, 1};
     const double iK[9] = {1 / K[0], 0, -K[2] / K[0], 0, 1 / K[4], -K[5] / K[4], 0, 0, 1};
@@ -71,7 +74,7 @@ static int scene(FILE* f, int nc, int N, int nDynPts) {
         s->K.cloneFrom(K, 3, 3), s->iK.cloneFrom(iK, 3, 3), s->k_ud.cloneFrom(kud, 7, 1);
         const double a = 0.06 * (c - 0.5 * (nc - 1));   // a fan around the scene: rotation about y, the centre moved along x
         double R[9] = {cos(a), 0, -sin(a), 0, 1, 0, sin(a), 0, cos(a)};
-        const double C[3] = {1.4 * (c - 0.5 * (nc - 1)), 0.05 * c, 0.0};
+        const double C[3] = {spacing * (c - 0.5 * (nc - 1)), 0.05 * c, 0.0};
         double t[3];
         for (int i = 0; i < 3; ++i) t[i] = -(R[3 * i] * C[0] + R[3 * i + 1] * C[1] + R[3 * i + 2] * C[2]);
         s->m_camPos.add(frame, c, R, t);
@@ -102,7 +105,7 @@ static int scene(FILE* f, int nc, int N, int nDynPts) {
         int i = 0;
         for (int p = 0; p < nScenePts && i < N; ++p) {
             double u, v;
-            if (!project(c, p, u, v) || urand() < 0.3) continue;
+            if (!project(c, p, u, v) || urand() < pDrop) continue;
             u += 0.5 * (urand() - 0.5), v += 0.5 * (urand() - 0.5);
             FeaturePoint* fp = s->m_featPts.add(frame, c, u, v);
             fp->setIntrinsic(s->K.data), fp->setCameraPose(s->m_camPos.current());
@@ -156,7 +159,7 @@ static int scene(FILE* f, int nc, int N, int nDynPts) {
         for (int i = 0; i < N; ++i) {
             int j = -1;
             const double u = urand();
-            if (ptOf[a][i] >= 0 && byPt[ptOf[a][i]] >= 0 && u < 0.6)
+            if (ptOf[a][i] >= 0 && byPt[ptOf[a][i]] >= 0 && u < pLink)
                 j = byPt[ptOf[a][i]];
             else if (u > 0.93)
                 j = (int)(urand() * N);   // a wrong match
@@ -223,10 +226,13 @@ int main(int argc, char** argv) {
     }
     FILE* f = fopen(argv[2], "wb");
     if (!f) return 1;
-    puti(f, 3);
-    int rc = scene(f, 4, 400, 40);
-    rc |= scene(f, 3, 250, 0);     // no dynamic points: every uncertain new point becomes certain static
-    rc |= scene(f, 6, 300, 120);
+    puti(f, 4);
+    int rc = scene(f, 4, 400, 40, 1.4, 0.6, 0.3);
+    rc |= scene(f, 3, 250, 0, 1.4, 0.6, 0.3);     // no dynamic points: every uncertain new point becomes certain static
+    rc |= scene(f, 6, 300, 120, 1.4, 0.6, 0.3);
+    // twelve cameras (SLAM_MAX_NUM is 13) close together, nearly every link kept: tracks of nine and more views that start behind
+    // camera 0 (the generator runs on from scene to scene, so the three scenes above stay as they were)
+    rc |= scene(f, 12, 160, 12, 0.35, 0.97, 0.1);
     fclose(f);
     return rc;
 }

@@ -295,8 +295,8 @@ def intercam_case():
 
 def newpts_case():
     """the reference's own featTracksFromMatches + NewMapPtsNCC::reconstructTracks + decidePointType (oracle/_ref/ref_newpts_test golden,
-    CPU): three scenes of cameras, candidate features, given matches, dynamic points' features; the tracks in the reference's
-    numbering and the new map points it made of them."""
+    CPU): four scenes of cameras, candidate features, given matches, dynamic points' features (the last one of twelve cameras close
+    together: tracks of nine and more views); the tracks in the reference's numbering and the new map points it made of them."""
     import subprocess
     import tempfile
 

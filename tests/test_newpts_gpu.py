@@ -128,9 +128,10 @@ def test_new_map_points_equal_the_restatement(hip, seed, max_disp):
     assert ((fl_new == 4) | (fl_new == 0)).sum() > 10    # uncertain, or certain static after decidePointType; dynamic ones need two DYNAMIC features
 
 
-def _run_both(S, max_disp, cap=None, pair_cap=4096):
+def _run_both(S, max_disp, cap=None, pair_cap=4096, min_len=2):
     """oracle.new_map_points_from_pairs and cs_newpts_from_pairs_dev on scene S (map arrays cut to `cap` entries, candidate lists cut
-    to `pair_cap` on the oracle's side -- the device is TOLD the full count); returns (oracle's result, oracle's arrays, device arrays)"""
+    to `pair_cap` on the oracle's side -- the device is TOLD the full count); returns (oracle's result, oracle's arrays, device arrays:
+    the map, the cameras' records, out = the counts, match / rows = the scratch's partners and matched-row bits per pair)"""
     import torch
 
     import oracle
@@ -143,7 +144,7 @@ def _run_both(S, max_disp, cap=None, pair_cap=4096):
              first=np.zeros(cap, np.int32), pf=S["pf"][:cap].copy(), s2m=[x.copy() for x in S["s2m"]], reproj=[np.zeros(N) for _ in range(nC)])
     res = oracle.new_map_points_from_pairs(N, [pl[:pair_cap] for pl in S["pairs"]], [sc.K] * nC, [sc.iK] * nC, S["R"], S["t"], S["xy"], S["state"],
                                            o["s2m"], S["is_static"], o["mapPts"], o["mapCov"], o["flags"], o["newPt"], o["first"], o["pf"], nMap,
-                                           S["frame"], max_disp=max_disp, reproj=o["reproj"], W=W_IMG, H=H_IMG)
+                                           S["frame"], max_disp=max_disp, min_len=min_len, reproj=o["reproj"], W=W_IMG, H=H_IMG)
     dev = torch.device("cuda:0")
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
     dK, diK = d(sc.K.reshape(9)), d(sc.iK.reshape(9))
@@ -170,9 +171,14 @@ def _run_both(S, max_disp, cap=None, pair_cap=4096):
     dR, dT = d(S["R"]), d(S["t"])
     newpts_from_pairs_dev(torch.cuda.current_stream().cuda_stream, job, N, pair_cap, dR.data_ptr(), dT.data_ptr(), dM.data_ptr(), dC.data_ptr(),
                           dF.data_ptr(), dNew.data_ptr(), dFirst.data_ptr(), dPf.data_ptr(), cap, dCount.data_ptr(), S["frame"], dScr.data_ptr(),
-                          dOut.data_ptr(), maxDisp=max_disp, W=W_IMG, H=H_IMG)
+                          dOut.data_ptr(), maxDisp=max_disp, minLen=min_len, W=W_IMG, H=H_IMG)
     torch.cuda.synchronize()
-    g = dict(mapPts=dM.cpu().numpy(), mapCov=dC.cpu().numpy(), flags=dF.cpu().numpy(), newPt=dNew.cpu().numpy(), first=dFirst.cpu().numpy(),
+    scr = dScr.view(torch.int32).cpu().numpy()
+    nW = (N + 31) // 32
+    rows = scr[(nC - 1) * N:(nC - 1) * (N + nW)].view(np.uint32).reshape(nC - 1, nW)
+    g = dict(match=scr[:(nC - 1) * N].reshape(nC - 1, N).copy(),
+             rows=np.stack([((rows[a][np.arange(N) >> 5] >> (np.arange(N) & 31).astype(np.uint32)) & 1).astype(bool) for a in range(nC - 1)]),
+             mapPts=dM.cpu().numpy(), mapCov=dC.cpu().numpy(), flags=dF.cpu().numpy(), newPt=dNew.cpu().numpy(), first=dFirst.cpu().numpy(),
              pf=dPf.cpu().numpy(), s2m=[ds2m[c].cpu().numpy() for c in range(nC)], reproj=[drep[c].cpu().numpy() for c in range(nC)],
              out=dOut.cpu().tolist(), count=int(dCount.item()))
     return res, o, g
