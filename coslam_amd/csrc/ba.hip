@@ -12,8 +12,8 @@
 //   k_linearize   one wave per point: residual + analytic Jacobians per measurement (lane = measurement),
 //                 W_ij = Jc^T Jp to HBM, V_i and g_i folded across the wave with butterflies, V_i^-1 stored;
 //                 k_linearize_seg8 / k_update_seg8: EIGHT lanes per point (eight points per wave) when no point has more
-//                 than 8 measurements -- the local-BA case, where a wave per point leaves 59 lanes idle
-//                 (COSLAM_BA_SEG8=0 forces the wave-per-point kernels, for A/B runs);
+//                 than 8 measurements -- the local-BA case, where a wave per point leaves 59 lanes idle (the plan picks
+//                 the layout from maxObsPerPoint; there is no switch);
 //   k_schur_part  (orders <= 36) one WAVE per (camera pair, point slice): partial S_jk, rhs_j, U_j, g_j, the 69 sums
 //                 folded with a transposed butterfly; k_schur (larger systems): one workgroup per camera pair writes
 //                 S_jk = [j==k](U_j + lambda I) - sum_i W_ij V_i^-1 W_ik^T through the dense table;
@@ -204,6 +204,198 @@ __device__ __forceinline__ bool inv33(const double* V, double* Vi) {
 
 #define BA_ACTIVE(D) (!((D).st->all_done) && !((D).st->inner_done))
 
+// ---- the terms of the normal equations and of the tentative step: ONE body each, called from every lane layout ----------
+// (wave per point, eight lanes per point, whole points packed into waves: ba_packed_dev.h).  The layouts differ in who
+// loads what and how the sums are folded; the arithmetic of a term is the same expression for all of them, and with
+// contraction off a force-inlined body gives each caller the operations, order and association it had written out.
+
+// point terms of one measurement: V upper triangle (6) and g (3)
+__device__ __forceinline__ void ba_point_terms(const double* Jp, const double* e, double* t) {
+    t[0] = Jp[0] * Jp[0] + Jp[3] * Jp[3];
+    t[1] = Jp[0] * Jp[1] + Jp[3] * Jp[4];
+    t[2] = Jp[0] * Jp[2] + Jp[3] * Jp[5];
+    t[3] = Jp[1] * Jp[1] + Jp[4] * Jp[4];
+    t[4] = Jp[1] * Jp[2] + Jp[4] * Jp[5];
+    t[5] = Jp[2] * Jp[2] + Jp[5] * Jp[5];
+    t[6] = Jp[0] * e[0] + Jp[3] * e[1];
+    t[7] = Jp[1] * e[0] + Jp[4] * e[1];
+    t[8] = Jp[2] * e[0] + Jp[5] * e[1];
+}
+
+// Vi = (V + lambda I)^-1 from the summed upper triangle acc[0..5]; zero for a held point and when V cannot be inverted
+__device__ __forceinline__ void ba_damped_inverse(const double* acc, double lambda, bool freeP, double* Vi) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) Vi[q] = 0;
+    if (freeP) {
+        double V[9] = {acc[0] + lambda, acc[1], acc[2], acc[1], acc[3] + lambda, acc[4], acc[2], acc[4], acc[5] + lambda};
+        if (!inv33(V, Vi)) {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) Vi[q] = 0;
+        }
+    }
+}
+
+// W = Jc^T Jp (6 x 3), zero unless the measurement is an inlier of a free point and a free camera
+__device__ __forceinline__ void ba_w_block(const double* Jc, const double* Jp, bool w, double* W) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double v = Jc[r] * Jp[c] + Jc[6 + r] * Jp[3 + c];
+            W[3 * r + c] = w ? v : 0.0;
+        }
+}
+
+// Y = W V^-1 (6 x 3)
+__device__ __forceinline__ void ba_y_block(const double* W, const double* Vi, double* Y) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Y[3 * r + c] = W[3 * r] * Vi[c] + W[3 * r + 1] * Vi[3 + c] + W[3 * r + 2] * Vi[6 + c];
+}
+
+// Schur sums of one pair entry: acc[0..35] += Y Wb^T and, on a diagonal pair, acc[36..41] += Y g
+__device__ __forceinline__ void ba_schur_sums(const double* Y, const double* Wb, const double* g, bool diag, double* acc) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) acc[6 * r + c] += Y[3 * r] * Wb[3 * c] + Y[3 * r + 1] * Wb[3 * c + 1] + Y[3 * r + 2] * Wb[3 * c + 2];
+    if (diag) {
+#pragma unroll
+        for (int r = 0; r < 6; ++r) acc[36 + r] += Y[3 * r] * g[0] + Y[3 * r + 1] * g[1] + Y[3 * r + 2] * g[2];
+    }
+}
+
+// camera terms of one measurement: u[0..20] += upper triangle of Jc^T Jc, u[21..26] += Jc^T e
+__device__ __forceinline__ void ba_cam_terms(const double* J, double e0, double e1, double* u) {
+    int q = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = r; c < 6; ++c) u[q++] += J[r] * J[c] + J[6 + r] * J[6 + c];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) u[21 + r] += J[r] * e0 + J[6 + r] * e1;
+}
+
+// camera pair of a linear index, the diagonal pairs first: they carry the longest lists (+ U_j, g_j), so they must not be a
+// launch's last workgroups
+__device__ __forceinline__ void schur_pair_of(const BaDev& D, int pi, int& ja, int& jb) {
+    if (pi < D.nc) {
+        ja = jb = pi;
+    } else {
+        int pair = pi - D.nc;
+        ja = 0;
+        while (pair >= D.nc - 1 - ja) {
+            pair -= D.nc - 1 - ja;
+            ++ja;
+        }
+        jb = ja + 1 + pair;
+    }
+}
+// the same pairs in row order (ja, ja), (ja, ja + 1), ...: the numbering of schurPart (k_schur_part, solve_reg_combine)
+__device__ __forceinline__ void schur_row_pair_of(const BaDev& D, int pi, int& ja, int& jb) {
+    ja = 0;
+    while (pi >= D.nc - ja) {
+        pi -= D.nc - ja;
+        ++ja;
+    }
+    jb = ja + pi;
+}
+// upper-triangular rank of entry (r, c) of a symmetric 6 x 6 block: where U_j keeps it among its 21 sums
+__device__ __forceinline__ int ba_uq(int r, int c) {
+    const int rr = r < c ? r : c, cc = r < c ? c : r;
+    return rr * 6 - (rr * (rr - 1)) / 2 + (cc - rr);
+}
+
+// the four waves' values of a workgroup, in LDS `stride` apart, added in wave order
+__device__ __forceinline__ double fold4(const double* p, int stride = 1) {
+    return ((p[0] + p[stride]) + p[2 * stride]) + p[3 * stride];
+}
+
+// entry q (0..41) of camera pair (ja, jb) into S || rhs.  s: the entry's Schur total; uTotal(k): total k of the 27 sums of
+// U_j, g_j (asked for on diagonal pairs only): S_jj = (U_j + lambda I) - sum, rhs_j = g_j - sum, S_jk = S_kj^T = -sum
+template <class UTotal>
+__device__ __forceinline__ void ba_pair_write(const BaDev& D, int ja, int jb, int q, double s, UTotal uTotal, double lambda) {
+    const int n = D.n;
+    const bool diag = (ja == jb);
+    if (q < 36) {
+        const int r = q / 6, c = q - 6 * r;
+        if (diag) {
+            D.S[(size_t)(6 * ja + r) * n + 6 * ja + c] = (uTotal(ba_uq(r, c)) + ((r == c && D.addLambda) ? lambda : 0.0)) - s;
+        } else {
+            D.S[(size_t)(6 * ja + r) * n + 6 * jb + c] = -s;
+            D.S[(size_t)(6 * jb + c) * n + 6 * ja + r] = -s;
+        }
+    } else if (diag) {
+        D.rhs[6 * ja + (q - 36)] = uTotal(21 + (q - 36)) - s;
+    }
+}
+
+// point step: b -= W^T dc for one measurement, and (behind the layout's own sum of b) d = V^-1 (g + b)
+__device__ __forceinline__ void ba_point_rhs(const double* W, const double* dc, double* b) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 6; ++r) b[c] -= W[3 * r + c] * dc[r];
+}
+__device__ __forceinline__ void ba_point_step(const double* Vi, const double* g, const double* b, double* d) {
+    const double g0 = g[0] + b[0], g1 = g[1] + b[1], g2 = g[2] + b[2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) d[r] = Vi[3 * r] * g0 + Vi[3 * r + 1] * g1 + Vi[3 * r + 2] * g2;
+}
+
+// tentative pose of one camera: R exp(w), t + dt for its solved step dc = (w, dt); a fixed camera (!moves) keeps its pose
+// and dc is not read
+__device__ __forceinline__ void ba_tentative_pose(const double* Rc, const double* Tc, const double* dc, bool moves, double* Rn,
+                                                  double* Tn) {
+    if (moves) {
+        double w[3] = {dc[0], dc[1], dc[2]}, dR[9];
+        so3_exp(w, dR);
+        mat33AB(Rc, dR, Rn);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) Tn[q] = Tc[q] + dc[3 + q];
+    } else {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) Rn[q] = Rc[q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) Tn[q] = Tc[q];
+    }
+}
+// squared residual of one measurement at the tentative estimate
+__device__ __forceinline__ double ba_tentative_res2(const double* K, const double* Rc, const double* Tc, const double* dc, bool moves,
+                                                    const double* Mn, const double* xy) {
+    double Rn[9], Tn[3], e[2];
+    ba_tentative_pose(Rc, Tc, dc, moves, Rn, Tn);
+    residual<false>(K, Rn, Tn, Mn, xy, e, nullptr, nullptr);
+    return e[0] * e[0] + e[1] * e[1];
+}
+
+// the LM rules as a pure function of (state, cost of the tentative step, squared step)
+struct LmRule {
+    int acc, done;
+    double lambda, cost;
+};
+__device__ __forceinline__ LmRule lm_rule(int chol_ok, double cost_old, double lambda, int inner_it, int innerMaxIter, double cost_sum,
+                                          double step2) {
+    LmRule r;
+    const double cost_new = chol_ok ? cost_sum : 1e300;
+    r.acc = (chol_ok && cost_new <= cost_old) ? 1 : 0;
+    r.done = 0;
+    r.lambda = lambda;
+    r.cost = cost_old;
+    if (r.acc) {
+        const double dec = cost_old - cost_new;
+        r.cost = cost_new;
+        r.lambda = lambda / 10;
+        if (dec < 1e-9 * cost_new + 1e-15 || step2 < 1e-20) r.done = 1;
+    } else {
+        r.lambda = lambda * 10;
+        if (lambda * 10 > 1e12) r.done = 1;
+    }
+    if (inner_it + 1 >= innerMaxIter) r.done = 1;
+    return r;
+}
+
 // ---- one wave per point --------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_linearize(BaDev D) {
     CS_BA_SETPRIO();
@@ -240,33 +432,18 @@ __global__ __launch_bounds__(256) void k_linearize(BaDev D) {
         D.e[2 * (size_t)o] = e[0];
         D.e[2 * (size_t)o + 1] = e[1];
         const bool freeC = (j >= D.nCamsCon);
+        double t[9];
         if (in && freeP) {
-            acc[0] += Jp[0] * Jp[0] + Jp[3] * Jp[3];
-            acc[1] += Jp[0] * Jp[1] + Jp[3] * Jp[4];
-            acc[2] += Jp[0] * Jp[2] + Jp[3] * Jp[5];
-            acc[3] += Jp[1] * Jp[1] + Jp[4] * Jp[4];
-            acc[4] += Jp[1] * Jp[2] + Jp[4] * Jp[5];
-            acc[5] += Jp[2] * Jp[2] + Jp[5] * Jp[5];
-            acc[6] += Jp[0] * e[0] + Jp[3] * e[1];
-            acc[7] += Jp[1] * e[0] + Jp[4] * e[1];
-            acc[8] += Jp[2] * e[0] + Jp[5] * e[1];
+            ba_point_terms(Jp, e, t);
+#pragma unroll
+            for (int q = 0; q < 9; ++q) acc[q] += t[q];
         }
-        const bool w = in && freeP && freeC;
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) Wo[3 * r + c] = w ? (Jc[r] * Jp[c] + Jc[6 + r] * Jp[3 + c]) : 0.0;
+        ba_w_block(Jc, Jp, in && freeP && freeC, Wo);
     }
     cs_wave_sum_many_d<9>(acc);
     if (lane == 0) {
-        double Vi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (freeP) {
-            double V[9] = {acc[0] + lambda, acc[1], acc[2], acc[1], acc[3] + lambda, acc[4], acc[2], acc[4], acc[5] + lambda};
-            if (!inv33(V, Vi)) {
-#pragma unroll
-                for (int q = 0; q < 9; ++q) Vi[q] = 0;
-            }
-        }
+        double Vi[9];
+        ba_damped_inverse(acc, lambda, freeP, Vi);
 #pragma unroll
         for (int q = 0; q < 9; ++q) D.Vinv[9 * (size_t)i + q] = Vi[q];
         D.gp[3 * (size_t)i] = acc[6];
@@ -318,41 +495,20 @@ __global__ __launch_bounds__(256) void k_linearize_seg8(BaDev D) {
     for (int q = 0; q < 6; ++q) Jp[q] = 0;
     if (in) residual<true>(D.Ks + 9 * j, D.Rs + 9 * j, D.Ts + 3 * j, M, D.obs_xy + 2 * (size_t)o, e, Jc, Jp);
     double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // V upper (6) + g (3)
-    if (in && freeP) {
-        acc[0] = Jp[0] * Jp[0] + Jp[3] * Jp[3];
-        acc[1] = Jp[0] * Jp[1] + Jp[3] * Jp[4];
-        acc[2] = Jp[0] * Jp[2] + Jp[3] * Jp[5];
-        acc[3] = Jp[1] * Jp[1] + Jp[4] * Jp[4];
-        acc[4] = Jp[1] * Jp[2] + Jp[4] * Jp[5];
-        acc[5] = Jp[2] * Jp[2] + Jp[5] * Jp[5];
-        acc[6] = Jp[0] * e[0] + Jp[3] * e[1];
-        acc[7] = Jp[1] * e[0] + Jp[4] * e[1];
-        acc[8] = Jp[2] * e[0] + Jp[5] * e[1];
-    }
+    if (in && freeP) ba_point_terms(Jp, e, acc);
     if (o >= 0) {
-        double* Wo = D.W + 18 * (size_t)o;
         double* Jo = D.Jc + 12 * (size_t)o;
 #pragma unroll
         for (int q = 0; q < 12; ++q) Jo[q] = Jc[q];
         D.e[2 * (size_t)o] = e[0];
         D.e[2 * (size_t)o + 1] = e[1];
-        const bool w = in && freeP && (j >= D.nCamsCon);
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) Wo[3 * r + c] = w ? (Jc[r] * Jp[c] + Jc[6 + r] * Jp[3 + c]) : 0.0;
+        ba_w_block(Jc, Jp, in && freeP && (j >= D.nCamsCon), D.W + 18 * (size_t)o);
     }
 #pragma unroll
     for (int q = 0; q < 9; ++q) acc[q] = seg8_sum(acc[q]);
     if (hasP && k == 0) {
-        double Vi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (freeP) {
-            double V[9] = {acc[0] + lambda, acc[1], acc[2], acc[1], acc[3] + lambda, acc[4], acc[2], acc[4], acc[5] + lambda};
-            if (!inv33(V, Vi)) {
-#pragma unroll
-                for (int q = 0; q < 9; ++q) Vi[q] = 0;
-            }
-        }
+        double Vi[9];
+        ba_damped_inverse(acc, lambda, freeP, Vi);
 #pragma unroll
         for (int q = 0; q < 9; ++q) D.Vinv[9 * (size_t)i + q] = Vi[q];
         D.gp[3 * (size_t)i] = acc[6];
@@ -369,20 +525,8 @@ __global__ __launch_bounds__(256) void k_schur(BaDev D) {
     if (!BA_ACTIVE(D)) return;
     __shared__ double red[4][42];
     __shared__ double redU[4][27];
-    // decode the pair from the linear block index over the upper triangle
-    // the diagonal pairs first: they carry the longest lists (+ U_j, g_j), so they must not be the launch's last workgroups
     int ja, jb;
-    if ((int)blockIdx.x < D.nc) {
-        ja = jb = blockIdx.x;
-    } else {
-        int pair = blockIdx.x - D.nc;
-        ja = 0;
-        while (pair >= D.nc - 1 - ja) {
-            pair -= D.nc - 1 - ja;
-            ++ja;
-        }
-        jb = ja + 1 + pair;
-    }
+    schur_pair_of(D, blockIdx.x, ja, jb);
     const int ca = ja + D.nCamsCon, cb = jb + D.nCamsCon;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const bool diag = (ja == jb);
@@ -419,35 +563,12 @@ __global__ __launch_bounds__(256) void k_schur(BaDev D) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (diag && ip[t] >= 0) {  // U_j, g_j: every inlier measurement of the camera, fixed points included
-                const double* J = D.Jc + 12 * (size_t)oa[t];
-                const double e0 = D.e[2 * (size_t)oa[t]], e1 = D.e[2 * (size_t)oa[t] + 1];
-                int q = 0;
-#pragma unroll
-                for (int r = 0; r < 6; ++r)
-#pragma unroll
-                    for (int c = r; c < 6; ++c) u[q++] += J[r] * J[c] + J[6 + r] * J[6 + c];
-#pragma unroll
-                for (int r = 0; r < 6; ++r) u[21 + r] += J[r] * e0 + J[6 + r] * e1;
+                ba_cam_terms(D.Jc + 12 * (size_t)oa[t], D.e[2 * (size_t)oa[t]], D.e[2 * (size_t)oa[t] + 1], u);
             }
             if (ob[t] < 0) continue;
-            const double* Wa = D.W + 18 * (size_t)oa[t];
-            const double* Wb = D.W + 18 * (size_t)ob[t];
-            const double* Vi = D.Vinv + 9 * (size_t)ip[t];
             double Y[18];
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) Y[3 * r + c] = Wa[3 * r] * Vi[c] + Wa[3 * r + 1] * Vi[3 + c] + Wa[3 * r + 2] * Vi[6 + c];
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = 0; c < 6; ++c)
-                    acc[6 * r + c] += Y[3 * r] * Wb[3 * c] + Y[3 * r + 1] * Wb[3 * c + 1] + Y[3 * r + 2] * Wb[3 * c + 2];
-            if (diag) {
-                const double* g = D.gp + 3 * (size_t)ip[t];
-#pragma unroll
-                for (int r = 0; r < 6; ++r) acc[36 + r] += Y[3 * r] * g[0] + Y[3 * r + 1] * g[1] + Y[3 * r + 2] * g[2];
-            }
+            ba_y_block(D.W + 18 * (size_t)oa[t], D.Vinv + 9 * (size_t)ip[t], Y);
+            ba_schur_sums(Y, D.W + 18 * (size_t)ob[t], D.gp + 3 * (size_t)ip[t], diag, acc);
         }
     }
     if (diag) {
@@ -463,25 +584,7 @@ __global__ __launch_bounds__(256) void k_schur(BaDev D) {
     __syncthreads();
     if (threadIdx.x < 42) {
         const int q = threadIdx.x;
-        const double s = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
-        const int n = D.n;
-        if (q < 36) {
-            const int r = q / 6, c = q - 6 * r;
-            if (diag) {
-                // U_j entry (upper-triangular rank of (min,max)) + lambda on the diagonal - Schur sum
-                const int rr = r < c ? r : c, cc = r < c ? c : r;
-                const int uq = rr * 6 - (rr * (rr - 1)) / 2 + (cc - rr);
-                const double uv = ((redU[0][uq] + redU[1][uq]) + redU[2][uq]) + redU[3][uq];
-                D.S[(size_t)(6 * ja + r) * n + 6 * ja + c] = (uv + ((r == c && D.addLambda) ? D.st->lambda : 0.0)) - s;
-            } else {
-                D.S[(size_t)(6 * ja + r) * n + 6 * jb + c] = -s;
-                D.S[(size_t)(6 * jb + c) * n + 6 * ja + r] = -s;
-            }
-        } else if (diag) {
-            const int r = q - 36;
-            const double gv = ((redU[0][21 + r] + redU[1][21 + r]) + redU[2][21 + r]) + redU[3][21 + r];
-            D.rhs[6 * ja + r] = gv - s;
-        }
+        ba_pair_write(D, ja, jb, q, fold4(&red[0][q], 42), [&](int k) { return fold4(&redU[0][k], 27); }, D.st->lambda);
     }
 }
 
@@ -492,25 +595,11 @@ __global__ __launch_bounds__(256) void k_schur(BaDev D) {
 // V^-1 = 0 for a held point, so those entries add zeros; only another rank's points (not linearised here: stale) are skipped.
 __global__ __launch_bounds__(256) void k_schur_pairs(BaDev D) {
     CS_BA_SETPRIO();
-#ifdef CS_SCHUR_PROBE
-    const unsigned long long p0 = __builtin_amdgcn_s_memtime();
-#endif
     if (!BA_ACTIVE(D)) return;
     __shared__ double red[4][42];
     __shared__ double redU[4][27];
-    // the diagonal pairs first: they carry the longest lists (+ U_j, g_j), so they must not be the launch's last workgroups
     int ja, jb;
-    if ((int)blockIdx.x < D.nc) {
-        ja = jb = blockIdx.x;
-    } else {
-        int pair = blockIdx.x - D.nc;
-        ja = 0;
-        while (pair >= D.nc - 1 - ja) {
-            pair -= D.nc - 1 - ja;
-            ++ja;
-        }
-        jb = ja + 1 + pair;
-    }
+    schur_pair_of(D, blockIdx.x, ja, jb);
     const int ca = ja + D.nCamsCon, cb = jb + D.nCamsCon;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const bool diag = (ja == jb);
@@ -525,40 +614,12 @@ __global__ __launch_bounds__(256) void k_schur_pairs(BaDev D) {
         const int4 E = D.pairEnt[en];
         const int oa = E.x, ob = E.y, ip = E.z;
         if (ip < D.pLo || ip >= D.pHi) continue;  // another rank's point
-        if (diag) {  // U_j, g_j: every measurement of the camera (outliers carry Jc = e = 0), fixed points included
-            const double* J = D.Jc + 12 * (size_t)oa;
-            const double e0 = D.e[2 * (size_t)oa], e1 = D.e[2 * (size_t)oa + 1];
-            int q = 0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = r; c < 6; ++c) u[q++] += J[r] * J[c] + J[6 + r] * J[6 + c];
-#pragma unroll
-            for (int r = 0; r < 6; ++r) u[21 + r] += J[r] * e0 + J[6 + r] * e1;
-        }
-        const double* Wa = D.W + 18 * (size_t)oa;
-        const double* Wb = D.W + 18 * (size_t)ob;
-        const double* Vi = D.Vinv + 9 * (size_t)ip;
+        if (diag)  // U_j, g_j: every measurement of the camera (outliers carry Jc = e = 0), fixed points included
+            ba_cam_terms(D.Jc + 12 * (size_t)oa, D.e[2 * (size_t)oa], D.e[2 * (size_t)oa + 1], u);
         double Y[18];
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) Y[3 * r + c] = Wa[3 * r] * Vi[c] + Wa[3 * r + 1] * Vi[3 + c] + Wa[3 * r + 2] * Vi[6 + c];
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < 6; ++c)
-                acc[6 * r + c] += Y[3 * r] * Wb[3 * c] + Y[3 * r + 1] * Wb[3 * c + 1] + Y[3 * r + 2] * Wb[3 * c + 2];
-        if (diag) {
-            const double* g = D.gp + 3 * (size_t)ip;
-#pragma unroll
-            for (int r = 0; r < 6; ++r) acc[36 + r] += Y[3 * r] * g[0] + Y[3 * r + 1] * g[1] + Y[3 * r + 2] * g[2];
-        }
+        ba_y_block(D.W + 18 * (size_t)oa, D.Vinv + 9 * (size_t)ip, Y);
+        ba_schur_sums(Y, D.W + 18 * (size_t)ob, D.gp + 3 * (size_t)ip, diag, acc);
     }
-#ifdef CS_SCHUR_PROBE
-    asm volatile("" : "+v"(acc[0]));
-    const unsigned long long p1 = __builtin_amdgcn_s_memtime();
-#endif
     if (diag) {
         cs_reduce_many<27>(u, lane);
         const int q = cs_reduce_index<27>(lane);
@@ -569,34 +630,10 @@ __global__ __launch_bounds__(256) void k_schur_pairs(BaDev D) {
         const int q = cs_reduce_index<42>(lane);
         if (q >= 0) red[wv][q] = acc[0];
     }
-#ifdef CS_SCHUR_PROBE
-    const unsigned long long p2 = __builtin_amdgcn_s_memtime();
-#endif
     __syncthreads();
-#ifdef CS_SCHUR_PROBE
-    if (threadIdx.x == 0 && (diag ? ja < 3 : blockIdx.x == 7) && D.st->nIterTotal == 3)
-        printf("k_schur_pairs block %d diag %d (%d entries): state+loop %llu reduce %llu\n", (int)blockIdx.x, (int)diag, eEnd - eBeg, p1 - p0, p2 - p1);
-#endif
     if (threadIdx.x < 42) {
         const int q = threadIdx.x;
-        const double s = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
-        const int n = D.n;
-        if (q < 36) {
-            const int r = q / 6, c = q - 6 * r;
-            if (diag) {
-                const int rr = r < c ? r : c, cc = r < c ? c : r;
-                const int uq = rr * 6 - (rr * (rr - 1)) / 2 + (cc - rr);
-                const double uv = ((redU[0][uq] + redU[1][uq]) + redU[2][uq]) + redU[3][uq];
-                D.S[(size_t)(6 * ja + r) * n + 6 * ja + c] = (uv + ((r == c && D.addLambda) ? D.st->lambda : 0.0)) - s;
-            } else {
-                D.S[(size_t)(6 * ja + r) * n + 6 * jb + c] = -s;
-                D.S[(size_t)(6 * jb + c) * n + 6 * ja + r] = -s;
-            }
-        } else if (diag) {
-            const int r = q - 36;
-            const double gv = ((redU[0][21 + r] + redU[1][21 + r]) + redU[2][21 + r]) + redU[3][21 + r];
-            D.rhs[6 * ja + r] = gv - s;
-        }
+        ba_pair_write(D, ja, jb, q, fold4(&red[0][q], 42), [&](int k) { return fold4(&redU[0][k], 27); }, D.st->lambda);
     }
 }
 
@@ -613,12 +650,8 @@ __global__ __launch_bounds__(64) void k_schur_part(BaDev D) {
     // wide: every load whose address is known is issued before the first value is looked at.
     const int lane = threadIdx.x;
     const int pairIdx = blockIdx.x / D.nSlices, slice = blockIdx.x - pairIdx * D.nSlices;
-    int ja = 0, pr = pairIdx;
-    while (pr >= D.nc - ja) {
-        pr -= D.nc - ja;
-        ++ja;
-    }
-    const int jb = ja + pr;
+    int ja, jb;
+    schur_row_pair_of(D, pairIdx, ja, jb);
     const int ca = ja + D.nCamsCon, cb = jb + D.nCamsCon;
     const bool diag = (ja == jb);
     const int nFree = D.P - D.nPtsCon;
@@ -696,19 +729,8 @@ __global__ __launch_bounds__(64) void k_schur_part(BaDev D) {
             for (int q = 0; q < 3; ++q) g[q] = diag ? D.gp[3 * (size_t)i + q] : 0.0;
         }
         double Y[18];
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) Y[3 * r + c] = Wa[3 * r] * Vi[c] + Wa[3 * r + 1] * Vi[3 + c] + Wa[3 * r + 2] * Vi[6 + c];
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < 6; ++c)
-                acc[6 * r + c] += Y[3 * r] * Wb[3 * c] + Y[3 * r + 1] * Wb[3 * c + 1] + Y[3 * r + 2] * Wb[3 * c + 2];
-        if (diag) {
-#pragma unroll
-            for (int r = 0; r < 6; ++r) acc[36 + r] += Y[3 * r] * g[0] + Y[3 * r + 1] * g[1] + Y[3 * r + 2] * g[2];
-        }
+        ba_y_block(Wa, Vi, Y);
+        ba_schur_sums(Y, Wb, g, diag, acc);
     }
     // round trip 3 (diagonal pairs; independent of the loop above, so it is in flight under it): Jc, e of the list entry
     int outU0 = 1;
@@ -745,13 +767,7 @@ __global__ __launch_bounds__(64) void k_schur_part(BaDev D) {
                 e0 = D.e[2 * (size_t)o];
                 e1 = D.e[2 * (size_t)o + 1];
             }
-            int q = 0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = r; c < 6; ++c) u[q++] += J[r] * J[c] + J[6 + r] * J[6 + c];
-#pragma unroll
-            for (int r = 0; r < 6; ++r) u[21 + r] += J[r] * e0 + J[6 + r] * e1;
+            ba_cam_terms(J, e0, e1, u);
         }
         cs_reduce_many<27>(u, lane);
         const int q = cs_reduce_index<27>(lane);
@@ -1132,41 +1148,14 @@ __device__ __forceinline__ void sb_panel_mfma(double* A, int I, int kb, int lane
 #endif
 #include "ba_cholflow_dev.h"
 
-// memory flavour of the solver's (and the packed LM-step functions') traffic: plain when a kernel boundary separates producer
-// and consumer, relaxed agent-scope atomics (sc1: never served from a stale L1 / non-coherent L2 line) when both run inside
-// ONE launch (the dataflow Cholesky, ba_cholflow_dev.h)
-template <bool COH>
-__device__ __forceinline__ double ldm(const double* p) {
-    if (COH) return cf_ld(p);
-    return *p;
-}
-template <bool COH>
-__device__ __forceinline__ void stm(double* p, double v) {
-    if (COH)
-        cf_st(p, v);
-    else
-        *p = v;
-}
-
-// NW waves (16: k_solve_blocked's own workgroup; 8: inside the persistent LM kernel); n > 0; `skip` = the LM state says there
-// is nothing to do (evaluated by the caller, consumed behind the matrix loads); *okFlagP (shared) = 1 iff every pivot was
-// positive.  Which wave takes which block does not enter the arithmetic: the result is the same for every NW.
-template <int NW, bool COH>
+// NW waves (k_solve_blocked's workgroup: 4 or 8); n > 0; `skip` = the LM state says there is nothing to do (evaluated by the
+// caller, consumed behind the matrix loads); *okFlagP (shared) = 1 iff every pivot was positive.  Which wave takes which block
+// does not enter the arithmetic: the result is the same for every NW.
+template <int NW>
 __device__ __forceinline__ void sb_solve_body(const BaDev& D, double* sm, int* okFlagP, const bool skip) {
     const int n = D.n, tid = threadIdx.x;
     constexpr int NT = NW * 64;
     const int NB = (n + SB - 1) / SB, NBT = NB * (NB + 1) / 2;
-#ifdef CS_SOLVE_PROBE
-    unsigned long long pT0 = __builtin_amdgcn_s_memtime(), pLoad = 0, pDiag = 0, pPanel = 0, pTrail = 0, pBack = 0, pT = 0;
-#define CS_PROBE(acc)                                      \
-    do {                                                   \
-        unsigned long long _t = __builtin_amdgcn_s_memtime(); \
-        acc += _t - pT;                                    \
-        pT = _t;                                           \
-    } while (0)
-#else
-#define CS_PROBE(acc) ((void)0)
-#endif
     double* A = sm;
     double* b = sm + (size_t)NBT * SBLK;  // the right-hand side: one more row of the matrix
     // ---- load the lower triangle (identity padding beyond n).  One wave per 16 x 16 block, four entries per lane (a lane
@@ -1189,7 +1178,7 @@ __device__ __forceinline__ void sb_solve_body(const BaDev& D, double* sm, int* o
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     v[q][u] = (gi == gj + u) ? 1.0 : 0.0;
-                    if (gi < n && gj + u < n) v[q][u] = ldm<COH>(&D.S[(size_t)gi * n + gj + u]);
+                    if (gi < n && gj + u < n) v[q][u] = D.S[(size_t)gi * n + gj + u];
                 }
             }
         }
@@ -1203,20 +1192,15 @@ __device__ __forceinline__ void sb_solve_body(const BaDev& D, double* sm, int* o
             }
         }
     }
-    for (int q = tid; q < NB * SB; q += NT) b[q] = (q < n) ? ldm<COH>(&D.rhs[q]) : 0.0;
+    for (int q = tid; q < NB * SB; q += NT) b[q] = (q < n) ? D.rhs[q] : 0.0;
     if (tid == 0) *okFlagP = 1;
     __syncthreads();
-#ifdef CS_SOLVE_PROBE
-    pT = __builtin_amdgcn_s_memtime();
-    pLoad = pT - pT0;
-#endif
     // the first diagonal block; every later one is factored by wave 0 NEXT TO the trailing update of the step before
     // (look-ahead), so the serial column chain -- the longest phase -- is off the critical path
     if (tid < 64) {
         if (!sb_factor_diag(A + sb_off(0, 0), tid) && tid == 0) *okFlagP = 0;
     }
     __syncthreads();
-    CS_PROBE(pDiag);
 
     for (int kb = 0; kb < NB; ++kb) {
         // ---- panel: A[I][kb] <- A[I][kb] Linv^T, one block per wave on the matrix cores; the right-hand side's block kb
@@ -1234,10 +1218,9 @@ __device__ __forceinline__ void sb_solve_body(const BaDev& D, double* sm, int* o
             }
         }
         __syncthreads();
-        CS_PROBE(pPanel);
         if (m == 0) break;
         // ---- trailing update A[I][J] -= P_I P_J^T for kb < J <= I (one block per wave and turn, on the matrix cores) and
-        // b_J -= b_kb P_J^T.  Wave 0 takes the next diagonal block and then factors it; waves 1..15 take everything else.
+        // b_J -= b_kb P_J^T.  Wave 0 takes the next diagonal block and then factors it; waves 1..NW-1 take everything else.
         if (tid < 64) {
             sb_block_update_mfma(A, kb + 1, kb + 1, kb, tid);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1265,7 +1248,6 @@ __device__ __forceinline__ void sb_solve_body(const BaDev& D, double* sm, int* o
             }
         }
         __syncthreads();
-        CS_PROBE(pTrail);
     }
     // b now holds y = L^-1 rhs.  Back substitution L^T x = y, block by block from the bottom; the diagonal blocks hold
     // their inverses, so x_kb = Linv^T y_kb is sixteen independent dot products: x_c = sum_{j >= c} Linv[j][c] y_j.
@@ -1289,20 +1271,13 @@ __device__ __forceinline__ void sb_solve_body(const BaDev& D, double* sm, int* o
         }
         __syncthreads();
     }
-    for (int q = tid; q < n; q += NT) stm<COH>(&D.rhs[q], b[q]);
-#ifdef CS_SOLVE_PROBE
-    CS_PROBE(pBack);
-    if (tid == 0 && D.st->nIterTotal == 3)
-        printf("k_solve_blocked n=%d NB=%d cycles: load %llu diag %llu panel %llu trail %llu back %llu total %llu\n", n, NB, pLoad,
-               pDiag, pPanel, pTrail, pBack, __builtin_amdgcn_s_memtime() - pT0);
-#endif
-#undef CS_PROBE
+    for (int q = tid; q < n; q += NT) D.rhs[q] = b[q];
 }
 
-// NW waves.  16 (1024 threads, 4 waves of 112 VGPRs per SIMD) is the fastest solve on an idle chip and needs a compute unit with
-// NOTHING else on it -- next to the persistent tracker it waited 35-45 us per LM step for one to drain
-// (profiles/r03_key_frame_interval_per_queue.txt); 8 (2 waves per SIMD) starts on any compute unit whose tracker workgroup
-// leaves half the register file, 4 on nearly any.  Same arithmetic and bits for every NW (sb_solve_body).
+// NW waves: 8 (2 waves per SIMD) starts on any compute unit whose tracker workgroup leaves half the register file, 4 on nearly
+// any.  (16 waves were the fastest solve on an idle chip but need a compute unit with NOTHING else on it -- next to the
+// persistent tracker the launch waited 35-45 us per LM step for one to drain, profiles/r03_key_frame_interval_per_queue.txt --
+// and are no longer built.)  Same arithmetic and bits for every NW (sb_solve_body).
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void k_solve_blocked(BaDev D) {
     if (CS_SOLVE_PRIO) __builtin_amdgcn_s_setprio(CS_SOLVE_PRIO);
@@ -1313,18 +1288,17 @@ __global__ __launch_bounds__(NW * 64) void k_solve_blocked(BaDev D) {
         if (threadIdx.x == 0) D.st->chol_ok = 1;
         return;
     }
-    sb_solve_body<NW, false>(D, sm, &okFlag, stAllDone || stInnerDone);
+    sb_solve_body<NW>(D, sm, &okFlag, stAllDone || stInnerDone);
     if (stAllDone || stInnerDone) return;
     if (threadIdx.x == 0) D.st->chol_ok = okFlag;  // (behind the body's last workgroup barrier)
 }
 static int sb_solve_waves(int n) { return n <= 64 ? 4 : 8; }
 static void sb_launch_solve(hipStream_t stream, const BaDev& D) {
     const size_t lds = sb_lds_bytes(D.n);
-    switch (sb_solve_waves(D.n)) {
-        case 4: hipLaunchKernelGGL(k_solve_blocked<4>, dim3(1), dim3(256), lds, stream, D); break;
-        case 8: hipLaunchKernelGGL(k_solve_blocked<8>, dim3(1), dim3(512), lds, stream, D); break;
-        default: hipLaunchKernelGGL(k_solve_blocked<16>, dim3(1), dim3(1024), lds, stream, D); break;
-    }
+    if (sb_solve_waves(D.n) == 4)
+        hipLaunchKernelGGL(k_solve_blocked<4>, dim3(1), dim3(256), lds, stream, D);
+    else
+        hipLaunchKernelGGL(k_solve_blocked<8>, dim3(1), dim3(512), lds, stream, D);
 }
 
 // ---- one WAVE, rows in REGISTERS: reduced camera systems of order n <= NMAX <= 36 -----------------------
@@ -1342,21 +1316,12 @@ __device__ __forceinline__ void solve_reg_combine(const BaDev& D, double* Ssm) {
         const int nPairs = D.nc * (D.nc + 1) / 2;
         for (int w = threadIdx.x; w < nPairs * 42; w += 256) {
             const int pi = w / 42, q = w - 42 * pi;
-            int a = 0, pr = pi;
-            while (pr >= D.nc - a) {
-                pr -= D.nc - a;
-                ++a;
-            }
-            const int b = a + pr;
+            int a, b;
+            schur_row_pair_of(D, pi, a, b);
             const double* p = D.schurPart + (size_t)pi * D.nSlices * 72;
             int uq = -1;
             if (a == b) {
-                if (q < 36) {
-                    const int r = q / 6, c = q - 6 * r, rr = r < c ? r : c, cc = r < c ? c : r;
-                    uq = rr * 6 - (rr * (rr - 1)) / 2 + (cc - rr);
-                } else {
-                    uq = 21 + (q - 36);
-                }
+                uq = (q < 36) ? ba_uq(q / 6, q % 6) : 21 + (q - 36);
             }
             // all slice loads of this entry are issued before the first is consumed (a loop with a run-time trip count
             // is not unrolled, and eight dependent round trips were 6.4 us of this 17 us kernel, s_memtime); the slices
@@ -1452,6 +1417,31 @@ __device__ __forceinline__ void solve_reg_factor(const BaDev& D, double* Ssm, in
     __syncthreads();
 }
 
+// end of k_update / k_update_seg8: the workgroup's partial cost (the four waves' sums in wave order) and, thread per
+// camera, the tentative poses Rn / Tn with the squared camera steps stepPart[P + j]
+__device__ __forceinline__ void update_tail(const BaDev& D, const double* rhs, double cost, double* red /* shared, 4 */) {
+    cost = wsum(cost);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cost;
+    __syncthreads();
+    if (threadIdx.x == 0) D.costPart[blockIdx.x] = fold4(red);
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < D.C) {
+        const bool moves = (j >= D.nCamsCon);
+        const double* dc = moves ? rhs + 6 * (j - D.nCamsCon) : rhs;
+        double Rn[9], Tn[3], s2 = 0;
+        ba_tentative_pose(D.Rs + 9 * j, D.Ts + 3 * j, dc, moves, Rn, Tn);
+#pragma unroll
+        for (int q = 0; q < 9; ++q) D.Rn[9 * j + q] = Rn[q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) D.Tn[3 * j + q] = Tn[q];
+        if (moves) {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) s2 += dc[q] * dc[q];
+        }
+        D.stepPart[D.P + j] = s2;
+    }
+}
+
 // ---- tentative step + its cost ----------------------------------------------------------------------
 // Wave per point: back-substituted point step, then (lane = measurement) the squared inlier residuals of that point
 // at the tentative estimate.  The tentative pose of a measurement's camera is re-derived in the lane from the
@@ -1522,30 +1512,17 @@ __global__ __launch_bounds__(256) void k_update(BaDev D) {
                 const bool first = (o == o0 + lane);
                 const int j = (first ? pj : D.obs_cam[o]) - D.nCamsCon;
                 if (j < 0 || (first ? pout : D.outlier[o])) continue;
-                const double* dc = rhs + 6 * j;
-                if (first) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-#pragma unroll
-                        for (int r = 0; r < 6; ++r) b[c] -= pW[3 * r + c] * dc[r];
-                } else {
-                    const double* Wo = D.W + 18 * (size_t)o;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-#pragma unroll
-                        for (int r = 0; r < 6; ++r) b[c] -= Wo[3 * r + c] * dc[r];
-                }
+                if (first)
+                    ba_point_rhs(pW, rhs + 6 * j, b);
+                else
+                    ba_point_rhs(D.W + 18 * (size_t)o, rhs + 6 * j, b);
             }
         }
         b[0] = wsum(b[0]);
         b[1] = wsum(b[1]);
         b[2] = wsum(b[2]);
         double d[3] = {0, 0, 0};
-        if (i >= D.nPtsCon) {
-            const double g0 = pg[0] + b[0], g1 = pg[1] + b[1], g2 = pg[2] + b[2];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) d[r] = pVi[3 * r] * g0 + pVi[3 * r + 1] * g1 + pVi[3 * r + 2] * g2;
-        }
+        if (i >= D.nPtsCon) ba_point_step(pVi, pg, b, d);
         double Mn[3];
 #pragma unroll
         for (int r = 0; r < 3; ++r) Mn[r] = pM[r] + d[r];
@@ -1580,52 +1557,11 @@ __global__ __launch_bounds__(256) void k_update(BaDev D) {
                 xy[0] = D.obs_xy[2 * (size_t)o];
                 xy[1] = D.obs_xy[2 * (size_t)o + 1];
             }
-            double Rn[9], Tn[3];
-            if (j >= D.nCamsCon) {
-                const double* dc = rhs + 6 * (j - D.nCamsCon);
-                double w[3] = {dc[0], dc[1], dc[2]}, dR[9];
-                so3_exp(w, dR);
-                mat33AB(Rc, dR, Rn);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) Tn[q] = Tc[q] + dc[3 + q];
-            } else {
-#pragma unroll
-                for (int q = 0; q < 9; ++q) Rn[q] = Rc[q];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) Tn[q] = Tc[q];
-            }
-            double e[2];
-            residual<false>(Kc, Rn, Tn, Mn, xy, e, nullptr, nullptr);
-            cost += e[0] * e[0] + e[1] * e[1];
+            const bool moves = (j >= D.nCamsCon);
+            cost += ba_tentative_res2(Kc, Rc, Tc, moves ? rhs + 6 * (j - D.nCamsCon) : rhs, moves, Mn, xy);
         }
     }
-    cost = wsum(cost);
-    if (lane == 0) red[threadIdx.x >> 6] = cost;
-    __syncthreads();
-    if (threadIdx.x == 0) D.costPart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t < D.C) {
-        const int j = t;
-        double s2 = 0;
-        if (j >= D.nCamsCon) {
-            const double* dc = rhs + 6 * (j - D.nCamsCon);
-            double w[3] = {dc[0], dc[1], dc[2]}, dR[9], Rn[9];
-            so3_exp(w, dR);
-            mat33AB(D.Rs + 9 * j, dR, Rn);
-#pragma unroll
-            for (int q = 0; q < 9; ++q) D.Rn[9 * j + q] = Rn[q];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) D.Tn[3 * j + q] = D.Ts[3 * j + q] + dc[3 + q];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) s2 += dc[q] * dc[q];
-        } else {
-#pragma unroll
-            for (int q = 0; q < 9; ++q) D.Rn[9 * j + q] = D.Rs[9 * j + q];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) D.Tn[3 * j + q] = D.Ts[3 * j + q];
-        }
-        D.stepPart[D.P + j] = s2;
-    }
+    update_tail(D, rhs, cost, red);
 }
 
 // ---- tentative step + its cost, eight lanes per point (see k_linearize_seg8): 32 points per workgroup, so the redundant
@@ -1639,7 +1575,7 @@ __global__ __launch_bounds__(256) void k_update_seg8(BaDev D) {
     __shared__ double Ssm[NMAX * NMAX + NMAX];
     __shared__ int okSh;
     solve_reg_combine<NMAX>(D, Ssm);
-    const int lane = threadIdx.x & 63, k = threadIdx.x & 7;
+    const int k = threadIdx.x & 7;
     const int gw = blockIdx.x * 32 + (threadIdx.x >> 3);
     const bool mine = gw < D.P && gw >= D.pLo && gw < D.pHi;
     int o = -1, pj = 0, pout = 1;
@@ -1689,22 +1625,12 @@ __global__ __launch_bounds__(256) void k_update_seg8(BaDev D) {
         const int i = gw;
         const bool inl = (o >= 0) && !pout;
         double b[3] = {0, 0, 0};
-        if (i >= D.nPtsCon && inl && pj >= D.nCamsCon) {
-            const double* dc = rhs + 6 * (pj - D.nCamsCon);
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-#pragma unroll
-                for (int r = 0; r < 6; ++r) b[c] -= pW[3 * r + c] * dc[r];
-        }
+        if (i >= D.nPtsCon && inl && pj >= D.nCamsCon) ba_point_rhs(pW, rhs + 6 * (pj - D.nCamsCon), b);
         b[0] = seg8_sum(b[0]);
         b[1] = seg8_sum(b[1]);
         b[2] = seg8_sum(b[2]);
         double d[3] = {0, 0, 0};
-        if (i >= D.nPtsCon) {
-            const double g0 = pg[0] + b[0], g1 = pg[1] + b[1], g2 = pg[2] + b[2];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) d[r] = pVi[3 * r] * g0 + pVi[3 * r + 1] * g1 + pVi[3 * r + 2] * g2;
-        }
+        if (i >= D.nPtsCon) ba_point_step(pVi, pg, b, d);
         double Mn[3];
 #pragma unroll
         for (int r = 0; r < 3; ++r) Mn[r] = pM[r] + d[r];
@@ -1714,62 +1640,16 @@ __global__ __launch_bounds__(256) void k_update_seg8(BaDev D) {
             D.stepPart[i] = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
         }
         if (inl) {
-            double Rn[9], Tn[3];
-            if (pj >= D.nCamsCon) {
-                const double* dc = rhs + 6 * (pj - D.nCamsCon);
-                double w[3] = {dc[0], dc[1], dc[2]}, dR[9];
-                so3_exp(w, dR);
-                mat33AB(pR, dR, Rn);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) Tn[q] = pT[q] + dc[3 + q];
-            } else {
-#pragma unroll
-                for (int q = 0; q < 9; ++q) Rn[q] = pR[q];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) Tn[q] = pT[q];
-            }
-            double e[2];
-            residual<false>(pK, Rn, Tn, Mn, pxy, e, nullptr, nullptr);
-            cost = e[0] * e[0] + e[1] * e[1];
+            const bool moves = (pj >= D.nCamsCon);
+            cost = ba_tentative_res2(pK, pR, pT, moves ? rhs + 6 * (pj - D.nCamsCon) : rhs, moves, Mn, pxy);
         }
     }
-    cost = wsum(cost);
-    if (lane == 0) red[threadIdx.x >> 6] = cost;
-    __syncthreads();
-    if (threadIdx.x == 0) D.costPart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t < D.C) {
-        const int j = t;
-        double s2 = 0;
-        if (j >= D.nCamsCon) {
-            const double* dc = rhs + 6 * (j - D.nCamsCon);
-            double w[3] = {dc[0], dc[1], dc[2]}, dR[9], Rn[9];
-            so3_exp(w, dR);
-            mat33AB(D.Rs + 9 * j, dR, Rn);
-#pragma unroll
-            for (int q = 0; q < 9; ++q) D.Rn[9 * j + q] = Rn[q];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) D.Tn[3 * j + q] = D.Ts[3 * j + q] + dc[3 + q];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) s2 += dc[q] * dc[q];
-        } else {
-#pragma unroll
-            for (int q = 0; q < 9; ++q) D.Rn[9 * j + q] = D.Rs[9 * j + q];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) D.Tn[3 * j + q] = D.Ts[3 * j + q];
-        }
-        D.stepPart[D.P + j] = s2;
-    }
+    update_tail(D, rhs, cost, red);
 }
 
-// ---- cost at the tentative (which=1) or current (which=0) estimate ------------------------------------
-__global__ __launch_bounds__(256) void k_cost(BaDev D, int which) {
-    if (D.st->all_done) return;
-    if (which == 1 && D.st->inner_done) return;
+// ---- cost of the inlier measurements of this rank's points at the estimate (Rs, Ts, pts): costPart[workgroup] ------------
+__device__ __forceinline__ void cost_part(const BaDev& D, const double* Rs, const double* Ts, const double* pts) {
     __shared__ double red[4];
-    const double* Rs = which ? D.Rn : D.Rs;
-    const double* Ts = which ? D.Tn : D.Ts;
-    const double* pts = which ? D.Mn : D.pts;
     double c = 0;
     for (int o = blockIdx.x * 256 + threadIdx.x; o < D.nObs; o += gridDim.x * 256) {
         if (D.outlier[o]) continue;
@@ -1783,7 +1663,13 @@ __global__ __launch_bounds__(256) void k_cost(BaDev D, int which) {
     c = wsum(c);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
     __syncthreads();
-    if (threadIdx.x == 0) D.costPart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    if (threadIdx.x == 0) D.costPart[blockIdx.x] = fold4(red);
+}
+// at the tentative (which=1) or current (which=0) estimate
+__global__ __launch_bounds__(256) void k_cost(BaDev D, int which) {
+    if (D.st->all_done) return;
+    if (which == 1 && D.st->inner_done) return;
+    cost_part(D, which ? D.Rn : D.Rs, which ? D.Tn : D.Ts, which ? D.Mn : D.pts);
 }
 
 // ---- LM control: one workgroup -----------------------------------------------------------------------
@@ -1800,7 +1686,7 @@ __global__ __launch_bounds__(256) void k_control(BaDev D) {  // phase 0
     c = wsum(c);
     if ((tid & 63) == 0) red[tid >> 6] = c;
     __syncthreads();
-    const double cost_sum = ((red[0] + red[1]) + red[2]) + red[3];
+    const double cost_sum = fold4(red);
     if (tid == 0) {
         st->cost = cost_sum;
         st->lambda = 1e-3;
@@ -1865,27 +1751,15 @@ __global__ __launch_bounds__(256) void k_control_step(BaDev D) {
     }
     __syncthreads();
     if (tid == 0) {
-        const double cost_sum = ((red[0] + red[1]) + red[2]) + red[3];
-        const double step2 = ((red[4] + red[5]) + red[6]) + red[7];
-        const double cost_new = chol_ok ? cost_sum : 1e300;
-        int acc = (chol_ok && cost_new <= cost_old) ? 1 : 0;
-        int done = 0;
+        const LmRule r = lm_rule(chol_ok, cost_old, lambda, inner_it, D.innerMaxIter, fold4(red), fold4(red + 4));
         st->nIterTotal += 1;
         st->inner_it = inner_it + 1;
         if (!chol_ok) st->nCholFail += 1;
-        if (acc) st->nAccepted += 1;
-        if (acc) {
-            const double dec = cost_old - cost_new;
-            st->cost = cost_new;
-            st->lambda = lambda / 10;
-            if (dec < 1e-9 * cost_new + 1e-15 || step2 < 1e-20) done = 1;
-        } else {
-            st->lambda = lambda * 10;
-            if (lambda * 10 > 1e12) done = 1;
-        }
-        if (inner_it + 1 >= D.innerMaxIter) done = 1;
-        st->inner_done = done;
-        accept = acc;
+        if (r.acc) st->nAccepted += 1;
+        if (r.acc) st->cost = r.cost;
+        st->lambda = r.lambda;
+        st->inner_done = r.done;
+        accept = r.acc;
     }
     __syncthreads();
     if (accept) {
@@ -1989,7 +1863,7 @@ __global__ void k_finish(BaDev D, cs_ba_stats_dev* out) {
     __syncthreads();
     if (tid == 0) {
         out->cost0 = D.st->cost0;
-        out->cost = ((red[0] + red[1]) + red[2]) + red[3];
+        out->cost = fold4(red);
         out->nIterTotal = D.st->nIterTotal;
         out->nOuter = D.st->nOuter;
         out->nOutliers = D.st->nOutliers;
@@ -2002,21 +1876,7 @@ __global__ void k_finish(BaDev D, cs_ba_stats_dev* out) {
 }
 
 __global__ void k_cost_force(BaDev D) {  // k_cost(0) ignoring the stop flags (final report)
-    __shared__ double red[4];
-    double c = 0;
-    for (int o = blockIdx.x * 256 + threadIdx.x; o < D.nObs; o += gridDim.x * 256) {
-        if (D.outlier[o]) continue;
-        const int j = D.obs_cam[o], i = D.obs_pt[o];
-        if (i < D.pLo || i >= D.pHi) continue;
-        double e[2];
-        residual<false>(D.Ks + 9 * j, D.Rs + 9 * j, D.Ts + 3 * j, D.pts + 3 * (size_t)i, D.obs_xy + 2 * (size_t)o, e,
-                        nullptr, nullptr);
-        c += e[0] * e[0] + e[1] * e[1];
-    }
-    c = wsum(c);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) D.costPart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    cost_part(D, D.Rs, D.Ts, D.pts);
 }
 
 // ---- index building on the device -----------------------------------------------------------------
@@ -2058,7 +1918,7 @@ __global__ __launch_bounds__(256) void k_dist_pack(BaDev D, int what) {
     c = wsum(c);
     if ((tid & 63) == 0) red[tid >> 6] = c;
     __syncthreads();
-    const double cost_sum = ((red[0] + red[1]) + red[2]) + red[3];
+    const double cost_sum = fold4(red);
     __syncthreads();
     double s2 = 0;
     if (what == 1)
@@ -2068,7 +1928,7 @@ __global__ __launch_bounds__(256) void k_dist_pack(BaDev D, int what) {
     __syncthreads();
     if (tid == 0) {
         D.scal[0] = cost_sum;
-        D.scal[1] = ((red[0] + red[1]) + red[2]) + red[3];
+        D.scal[1] = fold4(red);
     }
 }
 
@@ -2454,7 +2314,6 @@ static int ba_make_plan(cs_ba* b, int C, int P, int nObs, int nCamsCon, int nPts
         if (D.n > 36 && D.n <= SB_MAX_ORDER && sb_lds_bytes(D.n) > 64 * 1024) {
             CS_HIP(hipFuncSetAttribute((const void*)k_solve_blocked<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb_lds_bytes(D.n)));
             CS_HIP(hipFuncSetAttribute((const void*)k_solve_blocked<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb_lds_bytes(D.n)));
-            CS_HIP(hipFuncSetAttribute((const void*)k_solve_blocked<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb_lds_bytes(D.n)));
         }
     }
     L.gPts = (P + 3) / 4 > 0 ? (P + 3) / 4 : 1;

@@ -4,8 +4,8 @@
 // Why.  The wave-per-point / workgroup-per-camera-pair kernels above need ~300-360 workgroups resident at once: alone on the
 // chip an LM step is 68 us, but next to the persistent tracker (every SIMD holds two of its waves) the same kernels take
 // 100-115 us per step and the 20-step joint BA is the frame loop's critical path (profiles/r03_*).  These functions do the same
-// arithmetic with a quarter of the waves, as building blocks of two schedules: one launch per phase (the k_*_packed kernels
-// below) and ONE launch for the whole LM loop (ba_persist_dev.h):
+// arithmetic (the term bodies at the head of ba.hip) with a quarter of the waves, one launch per phase (the k_*_packed kernels
+// below):
 //   lin_wave        lane = measurement, a wave holds WHOLE points back to back (a plan made at upload: waveStart[]); the
 //                   per-point sums (V, g, the inlier count) are taken over the point's lanes through the wave's LDS scratch in
 //                   measurement order -- the serial order of the oracle's loop, and the same bits in every lane of the point,
@@ -20,9 +20,8 @@
 // decision that is still pending when the inner loop ends and puts the estimate back into Rs / Ts / pts.
 // LM state hand-over without a race: k_lin_packed reads state A and (workgroup 0) writes the decided state to B; the Schur
 // kernel, the solver and k_update_packed run on B; k_update_packed's workgroup 0 copies B back to A with `pending` set.  Nobody
-// reads a state word that another workgroup of the same launch writes.
-// COH (template flag of every function here): plain loads / stores when a kernel boundary separates producer and consumer,
-// relaxed agent-scope atomics when both run inside one launch.
+// reads a state word that another workgroup of the same launch writes.  A kernel boundary separates every producer from its
+// consumer, so all accesses are plain loads and stores.
 
 __device__ __forceinline__ int lp_ld_i(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void lp_st_i(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -31,32 +30,6 @@ struct LmView {
     int active, cur;
     double lambda;
 };
-
-// the LM rules of k_control_step as a pure function of (state, cost of the tentative step, squared step)
-struct LmRule {
-    int acc, done;
-    double lambda, cost;
-};
-__device__ __forceinline__ LmRule lm_rule(int chol_ok, double cost_old, double lambda, int inner_it, int innerMaxIter, double cost_sum,
-                                          double step2) {
-    LmRule r;
-    const double cost_new = chol_ok ? cost_sum : 1e300;
-    r.acc = (chol_ok && cost_new <= cost_old) ? 1 : 0;
-    r.done = 0;
-    r.lambda = lambda;
-    r.cost = cost_old;
-    if (r.acc) {
-        const double dec = cost_old - cost_new;
-        r.cost = cost_new;
-        r.lambda = lambda / 10;
-        if (dec < 1e-9 * cost_new + 1e-15 || step2 < 1e-20) r.done = 1;
-    } else {
-        r.lambda = lambda * 10;
-        if (lambda * 10 > 1e12) r.done = 1;
-    }
-    if (inner_it + 1 >= innerMaxIter) r.done = 1;
-    return r;
-}
 
 // LM control of the previous step, by every thread of a 256-thread workgroup (all arrive at the same answer); workgroup 0 records
 // it in *D.stn.
@@ -93,9 +66,7 @@ __device__ __forceinline__ LmView lm_head(const BaDev& D, double* red /* shared,
         red[4 + (tid >> 6)] = s2;
     }
     __syncthreads();
-    const double cost_sum = ((red[0] + red[1]) + red[2]) + red[3];
-    const double step2 = ((red[4] + red[5]) + red[6]) + red[7];
-    const LmRule r = lm_rule(chol_ok, cost_old, lambda, inner_it, D.innerMaxIter, cost_sum, step2);
+    const LmRule r = lm_rule(chol_ok, cost_old, lambda, inner_it, D.innerMaxIter, fold4(red), fold4(red + 4));
     if (blockIdx.x == 0 && tid == 0) {
         BaState s = *st;
         s.nIterTotal += 1;
@@ -164,8 +135,6 @@ __device__ __forceinline__ PackLane pack_lane(const BaDev& D, int w, int lane) {
 }
 
 // linearisation of the measurements of wave w at the estimate `cur` with damping `lambda`; wl: 10 x 64 doubles of LDS
-// COH_CAM: the camera poses were written by ANOTHER workgroup of this launch (fused update + linearisation): coherent loads
-template <bool COH, bool COH_CAM = COH>
 __device__ __forceinline__ void lin_wave(const BaDev& D, int w, int lane, int cur, double lambda, double* wl) {
     const PackLane L = pack_lane(D, w, lane);
     const double* Rc = cur ? D.Rn : D.Rs;
@@ -177,11 +146,11 @@ __device__ __forceinline__ void lin_wave(const BaDev& D, int w, int lane, int cu
     T[0] = T[1] = T[2] = 0;
     if (L.has) {
 #pragma unroll
-        for (int q = 0; q < 3; ++q) M[q] = ldm<COH>(Mc + 3 * (size_t)L.i + q);
+        for (int q = 0; q < 3; ++q) M[q] = Mc[3 * (size_t)L.i + q];
 #pragma unroll
-        for (int q = 0; q < 9; ++q) R[q] = ldm<COH_CAM>(Rc + 9 * L.j + q);
+        for (int q = 0; q < 9; ++q) R[q] = Rc[9 * L.j + q];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) T[q] = ldm<COH_CAM>(Tc + 3 * L.j + q);
+        for (int q = 0; q < 3; ++q) T[q] = Tc[3 * L.j + q];
     }
     double e[2] = {0, 0}, Jc[12], Jp[6];
 #pragma unroll
@@ -190,79 +159,44 @@ __device__ __forceinline__ void lin_wave(const BaDev& D, int w, int lane, int cu
     for (int q = 0; q < 6; ++q) Jp[q] = 0;
     if (L.in) residual<true>(D.Ks + 9 * L.j, R, T, M, D.obs_xy + 2 * (size_t)L.o, e, Jc, Jp);
     double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // V upper (6) + g (3) + inlier count
-    if (L.in && L.i >= D.nPtsCon) {
-        acc[0] = Jp[0] * Jp[0] + Jp[3] * Jp[3];
-        acc[1] = Jp[0] * Jp[1] + Jp[3] * Jp[4];
-        acc[2] = Jp[0] * Jp[2] + Jp[3] * Jp[5];
-        acc[3] = Jp[1] * Jp[1] + Jp[4] * Jp[4];
-        acc[4] = Jp[1] * Jp[2] + Jp[4] * Jp[5];
-        acc[5] = Jp[2] * Jp[2] + Jp[5] * Jp[5];
-        acc[6] = Jp[0] * e[0] + Jp[3] * e[1];
-        acc[7] = Jp[1] * e[0] + Jp[4] * e[1];
-        acc[8] = Jp[2] * e[0] + Jp[5] * e[1];
-    }
+    if (L.in && L.i >= D.nPtsCon) ba_point_terms(Jp, e, acc);
     acc[9] = L.in ? 1.0 : 0.0;
     seg_allreduce<10>(acc, wl, lane, L.segStart, L.segLen);
     // a point seen by fewer than two inlier measurements has no depth constraint: hold it (DESIGN.md "Robust BA")
     const bool freeP = L.has && (L.i >= D.nPtsCon) && (acc[9] >= 2.0);
-    double Vi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
+    double Vi[9], g[3] = {0, 0, 0};
+    ba_damped_inverse(acc, lambda, freeP, Vi);
     if (freeP) {
-        double Vm[9] = {acc[0] + lambda, acc[1], acc[2], acc[1], acc[3] + lambda, acc[4], acc[2], acc[4], acc[5] + lambda};
-        if (!inv33(Vm, Vi)) {
-#pragma unroll
-            for (int q = 0; q < 9; ++q) Vi[q] = 0;
-        }
         g[0] = acc[6];
         g[1] = acc[7];
         g[2] = acc[8];
     }
     if (!L.has) return;
-    const bool wf = L.in && freeP && (L.j >= D.nCamsCon);
     double Wm[18], Y[18];
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Wm[3 * r + c] = wf ? (Jc[r] * Jp[c] + Jc[6 + r] * Jp[3 + c]) : 0.0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Y[3 * r + c] = Wm[3 * r] * Vi[c] + Wm[3 * r + 1] * Vi[3 + c] + Wm[3 * r + 2] * Vi[6 + c];
+    ba_w_block(Jc, Jp, L.in && freeP && (L.j >= D.nCamsCon), Wm);
+    ba_y_block(Wm, Vi, Y);
     double* Jo = D.Jc + 12 * (size_t)L.o;
     double* Wo = D.W + 18 * (size_t)L.o;
     double* Yo = D.Y + 18 * (size_t)L.o;
 #pragma unroll
-    for (int q = 0; q < 12; ++q) stm<COH>(Jo + q, Jc[q]);
-    stm<COH>(D.e + 2 * (size_t)L.o, e[0]);
-    stm<COH>(D.e + 2 * (size_t)L.o + 1, e[1]);
+    for (int q = 0; q < 12; ++q) Jo[q] = Jc[q];
+    D.e[2 * (size_t)L.o] = e[0];
+    D.e[2 * (size_t)L.o + 1] = e[1];
 #pragma unroll
-    for (int q = 0; q < 18; ++q) stm<COH>(Wo + q, Wm[q]);
+    for (int q = 0; q < 18; ++q) Wo[q] = Wm[q];
 #pragma unroll
-    for (int q = 0; q < 18; ++q) stm<COH>(Yo + q, Y[q]);
+    for (int q = 0; q < 18; ++q) Yo[q] = Y[q];
     if (lane == L.segStart) {
 #pragma unroll
-        for (int q = 0; q < 9; ++q) stm<COH>(D.Vinv + 9 * (size_t)L.i + q, Vi[q]);
+        for (int q = 0; q < 9; ++q) D.Vinv[9 * (size_t)L.i + q] = Vi[q];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) stm<COH>(D.gp + 3 * (size_t)L.i + q, g[q]);
-    }
-}
-
-__device__ __forceinline__ void schur_pair_of(const BaDev& D, int pi, int& ja, int& jb) {  // the diagonal pairs first
-    if (pi < D.nc) {
-        ja = jb = pi;
-    } else {
-        int pair = pi - D.nc;
-        ja = 0;
-        while (pair >= D.nc - 1 - ja) {
-            pair -= D.nc - 1 - ja;
-            ++ja;
-        }
-        jb = ja + 1 + pair;
+        for (int q = 0; q < 3; ++q) D.gp[3 * (size_t)L.i + q] = g[q];
     }
 }
 
 // One wave's share (sub of WPP) of camera pair pi: its entries' sums, folded inside the wave, into tt[72] (42 Schur sums, then on
 // the diagonal the 27 sums of U_j, g_j).  The caller synchronises the team and calls schur_finish on its first wave.
-template <bool COH, int WPP>
+template <int WPP>
 __device__ __forceinline__ void schur_pair_part(const BaDev& D, int pi, int sub, int lane, double* tt) {
     int ja, jb;
     schur_pair_of(D, pi, ja, jb);
@@ -279,20 +213,10 @@ __device__ __forceinline__ void schur_pair_part(const BaDev& D, int pi, int sub,
         const double* Wb = D.W + 18 * (size_t)E.y;
         double Y[18], Wv[18];
 #pragma unroll
-        for (int q = 0; q < 18; ++q) Y[q] = ldm<COH>(Ya + q);
+        for (int q = 0; q < 18; ++q) Y[q] = Ya[q];
 #pragma unroll
-        for (int q = 0; q < 18; ++q) Wv[q] = ldm<COH>(Wb + q);
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < 6; ++c)
-                acc[6 * r + c] += Y[3 * r] * Wv[3 * c] + Y[3 * r + 1] * Wv[3 * c + 1] + Y[3 * r + 2] * Wv[3 * c + 2];
-        if (diag) {
-            const double* g = D.gp + 3 * (size_t)E.z;
-            const double g0 = ldm<COH>(g), g1 = ldm<COH>(g + 1), g2 = ldm<COH>(g + 2);
-#pragma unroll
-            for (int r = 0; r < 6; ++r) acc[36 + r] += Y[3 * r] * g0 + Y[3 * r + 1] * g1 + Y[3 * r + 2] * g2;
-        }
+        for (int q = 0; q < 18; ++q) Wv[q] = Wb[q];
+        ba_schur_sums(Y, Wv, D.gp + 3 * (size_t)E.z, diag, acc);
     }
     {
         cs_reduce_many<42>(acc, lane);
@@ -308,15 +232,8 @@ __device__ __forceinline__ void schur_pair_part(const BaDev& D, int pi, int sub,
             const double* Jg = D.Jc + 12 * (size_t)oa;
             double J[12];
 #pragma unroll
-            for (int q = 0; q < 12; ++q) J[q] = ldm<COH>(Jg + q);
-            const double e0 = ldm<COH>(D.e + 2 * (size_t)oa), e1 = ldm<COH>(D.e + 2 * (size_t)oa + 1);
-            int q = 0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = r; c < 6; ++c) u[q++] += J[r] * J[c] + J[6 + r] * J[6 + c];
-#pragma unroll
-            for (int r = 0; r < 6; ++r) u[21 + r] += J[r] * e0 + J[6 + r] * e1;
+            for (int q = 0; q < 12; ++q) J[q] = Jg[q];
+            ba_cam_terms(J, D.e[2 * (size_t)oa], D.e[2 * (size_t)oa + 1], u);
         }
         cs_reduce_many<27>(u, lane);
         const int q = cs_reduce_index<27>(lane);
@@ -324,38 +241,22 @@ __device__ __forceinline__ void schur_pair_part(const BaDev& D, int pi, int sub,
     }
 }
 // the team's first wave: the WPP waves' totals (tt0[sub * 72 + q]) added in wave order, the pair's block of S || rhs written
-template <bool COH, int WPP>
+template <int WPP>
 __device__ __forceinline__ void schur_finish(const BaDev& D, int pi, int lane, const double* tt0, double lambda) {
     if (lane >= 42) return;
     int ja, jb;
     schur_pair_of(D, pi, ja, jb);
-    const bool diag = (ja == jb);
-    const int q = lane, n = D.n;
     auto total = [&](int k) {
         double s = tt0[k];
 #pragma unroll
         for (int u = 1; u < WPP; ++u) s += tt0[u * 72 + k];
         return s;
     };
-    const double s = total(q);
-    if (q < 36) {
-        const int r = q / 6, c = q - 6 * r;
-        if (diag) {
-            const int rr = r < c ? r : c, cc = r < c ? c : r;
-            const int uq = rr * 6 - (rr * (rr - 1)) / 2 + (cc - rr);
-            stm<COH>(&D.S[(size_t)(6 * ja + r) * n + 6 * ja + c], (total(42 + uq) + ((r == c && D.addLambda) ? lambda : 0.0)) - s);
-        } else {
-            stm<COH>(&D.S[(size_t)(6 * ja + r) * n + 6 * jb + c], -s);
-            stm<COH>(&D.S[(size_t)(6 * jb + c) * n + 6 * ja + r], -s);
-        }
-    } else if (diag) {
-        stm<COH>(&D.rhs[6 * ja + (q - 36)], total(42 + 21 + (q - 36)) - s);
-    }
+    ba_pair_write(D, ja, jb, lane, total(lane), [&](int k) { return total(42 + k); }, lambda);
 }
 
 // tentative step of the points of wave w and the tentative cost of its measurements (per lane, to be summed by the caller);
 // rhs = the solved camera step; wl: 3 x 64 doubles of LDS
-template <bool COH, bool COH_RHS = COH>
 __device__ __forceinline__ void update_wave(const BaDev& D, int w, int lane, int cur, double* wl, double& cost, double& step) {
     const double* Rc = cur ? D.Rn : D.Rs;
     const double* Tc = cur ? D.Tn : D.Ts;
@@ -368,17 +269,14 @@ __device__ __forceinline__ void update_wave(const BaDev& D, int w, int lane, int
     const int jf = L.j - D.nCamsCon;
     if (L.has && jf >= 0) {
 #pragma unroll
-        for (int q = 0; q < 6; ++q) dc[q] = ldm<COH_RHS>(rhs + 6 * jf + q);
+        for (int q = 0; q < 6; ++q) dc[q] = rhs[6 * jf + q];
     }
     if (L.has && L.in && jf >= 0 && L.i >= D.nPtsCon) {
         const double* Wo = D.W + 18 * (size_t)L.o;
         double Wm[18];
 #pragma unroll
-        for (int q = 0; q < 18; ++q) Wm[q] = ldm<COH>(Wo + q);
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int r = 0; r < 6; ++r) b[c] -= Wm[3 * r + c] * dc[r];
+        for (int q = 0; q < 18; ++q) Wm[q] = Wo[q];
+        ba_point_rhs(Wm, dc, b);
     }
     seg_allreduce<3>(b, wl, lane, L.segStart, L.segLen);
     if (!L.has) return;
@@ -386,77 +284,50 @@ __device__ __forceinline__ void update_wave(const BaDev& D, int w, int lane, int
     const double* Mp = Mc + 3 * (size_t)L.i;
     if (L.i >= D.nPtsCon) {
         const double* Vi = D.Vinv + 9 * (size_t)L.i;
-        const double* gp = D.gp + 3 * (size_t)L.i;
         double V9[9];
 #pragma unroll
-        for (int q = 0; q < 9; ++q) V9[q] = ldm<COH>(Vi + q);
-        const double g0 = ldm<COH>(gp) + b[0], g1 = ldm<COH>(gp + 1) + b[1], g2 = ldm<COH>(gp + 2) + b[2];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) d[r] = V9[3 * r] * g0 + V9[3 * r + 1] * g1 + V9[3 * r + 2] * g2;
+        for (int q = 0; q < 9; ++q) V9[q] = Vi[q];
+        ba_point_step(V9, D.gp + 3 * (size_t)L.i, b, d);
     }
 #pragma unroll
-    for (int r = 0; r < 3; ++r) Mn[r] = ldm<COH>(Mp + r) + d[r];
+    for (int r = 0; r < 3; ++r) Mn[r] = Mp[r] + d[r];
     if (lane == L.segStart) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) stm<COH>(Mt + 3 * (size_t)L.i + r, Mn[r]);
+        for (int r = 0; r < 3; ++r) Mt[3 * (size_t)L.i + r] = Mn[r];
         step += d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
     }
     if (L.in) {
-        double Rn[9], Tn[3], Rcur[9];
-        const double* Rj = Rc + 9 * L.j;
-        const double* Tj = Tc + 3 * L.j;
+        double Rcur[9];
 #pragma unroll
-        for (int q = 0; q < 9; ++q) Rcur[q] = ldm<COH>(Rj + q);
-        if (jf >= 0) {
-            double wv3[3] = {dc[0], dc[1], dc[2]}, dR[9];
-            so3_exp(wv3, dR);
-            mat33AB(Rcur, dR, Rn);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) Tn[q] = ldm<COH>(Tj + q) + dc[3 + q];
-        } else {
-#pragma unroll
-            for (int q = 0; q < 9; ++q) Rn[q] = Rcur[q];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) Tn[q] = ldm<COH>(Tj + q);
-        }
-        double e[2];
-        residual<false>(D.Ks + 9 * L.j, Rn, Tn, Mn, D.obs_xy + 2 * (size_t)L.o, e, nullptr, nullptr);
-        cost += e[0] * e[0] + e[1] * e[1];
+        for (int q = 0; q < 9; ++q) Rcur[q] = Rc[9 * L.j + q];
+        cost += ba_tentative_res2(D.Ks + 9 * L.j, Rcur, Tc + 3 * L.j, dc, jf >= 0, Mn, D.obs_xy + 2 * (size_t)L.o);
     }
 }
 
 // tentative pose of camera j and its squared step
-// COH_OUT: the tentative pose is read by OTHER workgroups of this launch (fused update + linearisation): coherent stores
-template <bool COH, bool COH_RHS = COH, bool COH_OUT = COH>
 __device__ __forceinline__ void update_cam(const BaDev& D, int j, int cur, double& step) {
     const double* Rc = cur ? D.Rn : D.Rs;
     const double* Tc = cur ? D.Tn : D.Ts;
     double* Rt = cur ? D.Rs : D.Rn;
     double* Tt = cur ? D.Ts : D.Tn;
-    double Rcur[9];
+    const bool moves = (j >= D.nCamsCon);
+    double Rcur[9], dc[6] = {0, 0, 0, 0, 0, 0}, Rn[9], Tn[3];
 #pragma unroll
-    for (int q = 0; q < 9; ++q) Rcur[q] = ldm<COH>(Rc + 9 * j + q);
-    if (j >= D.nCamsCon) {
-        const double* dcj = D.rhs + 6 * (j - D.nCamsCon);
-        double dc[6];
+    for (int q = 0; q < 9; ++q) Rcur[q] = Rc[9 * j + q];
+    if (moves) {
 #pragma unroll
-        for (int q = 0; q < 6; ++q) dc[q] = ldm<COH_RHS>(dcj + q);
-        double wv3[3] = {dc[0], dc[1], dc[2]}, dR[9], Rn[9];
-        so3_exp(wv3, dR);
-        mat33AB(Rcur, dR, Rn);
+        for (int q = 0; q < 6; ++q) dc[q] = D.rhs[6 * (j - D.nCamsCon) + q];
+    }
+    ba_tentative_pose(Rcur, Tc + 3 * j, dc, moves, Rn, Tn);
 #pragma unroll
-        for (int q = 0; q < 9; ++q) stm<COH_OUT>(Rt + 9 * j + q, Rn[q]);
+    for (int q = 0; q < 9; ++q) Rt[9 * j + q] = Rn[q];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) stm<COH_OUT>(Tt + 3 * j + q, ldm<COH>(Tc + 3 * j + q) + dc[3 + q]);
+    for (int q = 0; q < 3; ++q) Tt[3 * j + q] = Tn[q];
+    if (moves) {
         double s2 = 0;
 #pragma unroll
         for (int q = 0; q < 6; ++q) s2 += dc[q] * dc[q];
         step += s2;
-    } else {
-#pragma unroll
-        for (int q = 0; q < 9; ++q) stm<COH_OUT>(Rt + 9 * j + q, Rcur[q]);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) stm<COH_OUT>(Tt + 3 * j + q, ldm<COH>(Tc + 3 * j + q));
     }
 }
 
@@ -469,7 +340,7 @@ __global__ __launch_bounds__(256) void k_lin_packed(BaDev D) {
     if (!V.active) return;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, w = blockIdx.x * 4 + wv;
     if (w >= D.nPackWaves) return;
-    lin_wave<false>(D, w, lane, V.cur, V.lambda, segl[wv]);
+    lin_wave(D, w, lane, V.cur, V.lambda, segl[wv]);
 }
 
 #ifndef CS_SCHUR_WPP
@@ -489,9 +360,9 @@ __global__ __launch_bounds__(256) CS_SCHUR_ATTR void k_schur_wave(BaDev D) {
     __shared__ double tot[4][72];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, team = wv / WPP, sub = wv % WPP;
     const int pi = blockIdx.x * TEAMS + team, nPairs = D.nc * (D.nc + 1) / 2;
-    if (pi < nPairs) schur_pair_part<false, WPP>(D, pi, sub, lane, tot[wv]);
+    if (pi < nPairs) schur_pair_part<WPP>(D, pi, sub, lane, tot[wv]);
     __syncthreads();
-    if (pi < nPairs && sub == 0) schur_finish<false, WPP>(D, pi, lane, tot[team * WPP], D.st->lambda);
+    if (pi < nPairs && sub == 0) schur_finish<WPP>(D, pi, lane, tot[team * WPP], D.st->lambda);
 }
 
 // tentative step + its cost; D.st = the state k_lin_packed decided (B), D.stn = the state the next k_lin_packed reads (A)
@@ -510,10 +381,10 @@ __global__ __launch_bounds__(256) void k_update_packed(BaDev D) {
     if (!active) return;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, w = blockIdx.x * 4 + wv;
     double cost = 0, step = 0;
-    if (w < D.nPackWaves) update_wave<false>(D, w, lane, cur, segl[wv], cost, step);  // (wave-uniform)
+    if (w < D.nPackWaves) update_wave(D, w, lane, cur, segl[wv], cost, step);  // (wave-uniform)
     {   // tentative camera poses: camera t of this launch's first ceil(C / 256) workgroups
         const int j = blockIdx.x * 256 + threadIdx.x;
-        if (j < D.C) update_cam<false>(D, j, cur, step);
+        if (j < D.C) update_cam(D, j, cur, step);
     }
     cost = wsum(cost);
     step = wsum(step);
@@ -523,8 +394,8 @@ __global__ __launch_bounds__(256) void k_update_packed(BaDev D) {
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        D.costPart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-        D.stepPart[blockIdx.x] = ((red[4] + red[5]) + red[6]) + red[7];
+        D.costPart[blockIdx.x] = fold4(red);
+        D.stepPart[blockIdx.x] = fold4(red + 4);
     }
 }
 

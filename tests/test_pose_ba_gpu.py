@@ -71,6 +71,10 @@ def ba_inputs(**kw):
     (dict(n_cams=22, n_pts=500, visibility=0.5, seed=10), 2, 2, 2, 8),                 # order 120: LDS workgroup Cholesky
     (dict(n_cams=40, n_pts=400, visibility=0.5, seed=11), 2, 2, 2, 8),                 # order 228: the dataflow Cholesky (k_cholflow)
     (dict(n_cams=120, n_pts=300, visibility=0.25, seed=12, W=1920, H=1080), 8, 2, 1, 6),  # cfg5 camera count (4 x 30 KF), order 672
+    # order <= 36 with points of more than 8 measurements: the wave-per-point kernels in front of the register Cholesky
+    # (k_linearize, k_schur_part, k_update<N>; every other order <= 36 case in the suite has at most 8 cameras: the seg8 kernels)
+    (dict(n_cams=12, n_pts=48, seed=41), 6, 2, 2, 10),                                  # order 36, every point in all 12 cameras
+    (dict(n_cams=11, n_pts=40, visibility=0.95, seed=43), 8, 2, 2, 10),                 # order 18, 9 to 11 measurements per point
 ])
 def test_ba_matches_oracle(hip, kw, ncon, npcon, maxIter, inner):
     kw = dict(kw)
