@@ -27,6 +27,7 @@ HIP_SOURCES = [
     "grouping.hip",
     "merge.hip",
     "merge_graph.cpp",
+    "merge_apply.hip",
     "liveview.hip",
     "poseupdate.hip",
     "ncc.hip",

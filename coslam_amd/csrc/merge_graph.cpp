@@ -127,3 +127,81 @@ extern "C" int cs_merge_keygraph_plan(int nKeyFrames, const int* frames, const c
     }
     return CS_OK;
 }
+
+// ---- MergeCameraGroup::mergeMatchedGroups (src/app/SL_MergeCameraGroup.cpp:1117-1174) and the m_groupId loop behind it
+// (src/app/SL_CoSLAM.cpp:1419-1424) over a host record.  Groups joined by a valid merge info become one: the connected components of the
+// group graph (findConnectedComponents is un-vendored LibVisualSLAM; the order is this library's definition, DESIGN 5.1: components by
+// ascending smallest member, members ascending), the cameras appended group by group in each old group's own order (:1141-1148).
+// mergedGid: the first new group that holds camid1 or camid2 (:1162-1171); none: the reference asserts, here an error and the record is
+// left as it was.  Entries behind the new counts are cleared as cs_camera_grouping_dev leaves them (-1 / 0).
+extern "C" int cs_merge_matched_groups(cs_camera_groups* groups, int nInfo, const int* gid1, const int* gid2, int camid1, int camid2,
+                                       int* groupId, int* mergedGid) {
+    if (mergedGid) *mergedGid = -1;
+    if (!groups || nInfo < 0 || (nInfo > 0 && (!gid1 || !gid2)) || !groupId || !mergedGid || groups->groupNum < 1 || groups->groupNum > 16) {
+        cs_set_error("cs_merge_matched_groups: bad argument");
+        return CS_ERR_INVALID;
+    }
+    const int nG = groups->groupNum;
+    for (int g = 0; g < nG; ++g)
+        if (groups->num[g] < 0 || groups->num[g] > 16) {
+            cs_set_error("cs_merge_matched_groups: group %d holds %d cameras", g, groups->num[g]);
+            return CS_ERR_INVALID;
+        }
+    bool A[16][16] = {};
+    for (int i = 0; i < nInfo; ++i) {
+        if (gid1[i] < 0 || gid1[i] >= nG || gid2[i] < 0 || gid2[i] >= nG) {
+            cs_set_error("cs_merge_matched_groups: merge info %d names group %d / %d of %d", i, gid1[i], gid2[i], nG);
+            return CS_ERR_INVALID;
+        }
+        A[gid1[i]][gid2[i]] = A[gid2[i]][gid1[i]] = true;
+    }
+    int comp[16], nComp = 0;
+    for (int g = 0; g < nG; ++g) comp[g] = -1;
+    for (int g = 0; g < nG; ++g) {   // ascending smallest member
+        if (comp[g] >= 0) continue;
+        int stack[16], top = 0;
+        stack[top++] = g, comp[g] = nComp;
+        while (top > 0) {
+            const int a = stack[--top];
+            for (int b = 0; b < nG; ++b)
+                if (A[a][b] && comp[b] < 0) comp[b] = nComp, stack[top++] = b;
+        }
+        ++nComp;
+    }
+    cs_camera_groups out;
+    memset(&out, 0xFF, sizeof(out));
+    out.groupNum = nComp;
+    for (int g = 0; g < 16; ++g) out.num[g] = 0;
+    for (int k = 0; k < nComp; ++k)
+        for (int g = 0; g < nG; ++g) {   // members ascending
+            if (comp[g] != k) continue;
+            for (int i = 0; i < groups->num[g]; ++i) {
+                if (out.num[k] >= 16) {
+                    cs_set_error("cs_merge_matched_groups: more than 16 cameras in the merged group %d", k);
+                    return CS_ERR_INVALID;
+                }
+                out.camIds[k][out.num[k]++] = groups->camIds[g][i];
+            }
+        }
+    int mg = -1;
+    for (int k = 0; k < nComp && mg < 0; ++k)
+        for (int i = 0; i < out.num[k]; ++i)
+            if (out.camIds[k][i] == camid1 || out.camIds[k][i] == camid2) {
+                mg = k;
+                break;
+            }
+    if (mg < 0) {
+        cs_set_error("cs_merge_matched_groups: neither camera %d nor camera %d is in a group", camid1, camid2);
+        return CS_ERR_INVALID;
+    }
+    for (int c = 0; c < 16; ++c) groupId[c] = groups->groupId[c];   // (:1419-1424 writes the cameras of the groups only)
+    for (int k = 0; k < nComp; ++k)
+        for (int i = 0; i < out.num[k]; ++i) {
+            const int c = out.camIds[k][i];
+            if (c >= 0 && c < 16) groupId[c] = k;
+        }
+    for (int c = 0; c < 16; ++c) out.groupId[c] = groupId[c];
+    *groups = out;
+    *mergedGid = mg;
+    return CS_OK;
+}

@@ -38,6 +38,7 @@
 // components of a scaled handle, run k_posegraph_relax exactly as before.
 // Not built: a one-wave natural-order path for scaled components, and the workgroup path for plain components that are wide.
 #include "cs_common.h"
+#include "posegraph_view.h"
 
 #include <algorithm>
 #include <new>
@@ -1186,6 +1187,12 @@ extern "C" int cs_posegraph_status(cs_posegraph* g, void* hip_stream, int* nFail
         return CS_ERR_NUMERIC;
     }
     return CS_OK;
+}
+
+// the status words on the device, for a guard that must not wait for the host (csrc/merge_apply.hip)
+void cs_posegraph_status_words(const cs_posegraph* g, const int** d_status, int* n) {
+    *d_status = g ? g->plan.status : nullptr;
+    *n = g ? g->nComp + g->nSComp : 0;
 }
 
 extern "C" int cs_posegraph_relax(cs_posegraph* g, const double* nodeR, const double* nodeT, const double* edgeR,

@@ -42,6 +42,7 @@
 
 #include "cs_common.h"
 #include "project_dev.h"
+#include "triangulate_dev.h"
 #include "history_view.h"
 #include "register_rows_dev.h"
 #include "small_ops.h"
@@ -211,8 +212,6 @@ __device__ __forceinline__ void pu_fmat(const double* __restrict__ iK, const dou
         }
     pu_mat33_ab(T, iK, F);
 }
-
-__device__ __forceinline__ void up_cam_center(const double* __restrict__ R, const double* __restrict__ t, double* C);
 
 __global__ __launch_bounds__(256) void k_pose_update(PuArgs A) {
     extern __shared__ double Fs[];  // dynamic role: [nHist][9]
@@ -678,47 +677,6 @@ struct UpArgs {
 constexpr int UP_LPP = 64;  // a WAVE per map point
 
 static_assert(UP_LPP == 64 && PU_MAX_CAMS <= UP_LPP, "the covariance tail broadcasts from lane = camera of the point's own wave");
-
-struct UpNormalEq {
-    double N[6], g[3];
-};
-__device__ __forceinline__ void up_add_view(UpNormalEq& E, const double* __restrict__ iK, const double* __restrict__ R,
-                                            const double* __restrict__ t, double mx, double my) {
-    const double w = (iK[6] * mx + iK[7] * my) + iK[8];
-    const double x = ((iK[0] * mx + iK[1] * my) + iK[2]) / w, y = ((iK[3] * mx + iK[4] * my) + iK[5]) / w;  // normPoint
-    const double a0[3] = {R[0] - x * R[6], R[1] - x * R[7], R[2] - x * R[8]}, a1[3] = {R[3] - y * R[6], R[4] - y * R[7], R[5] - y * R[8]};
-    const double b0 = x * t[2] - t[0], b1 = y * t[2] - t[1];
-    E.N[0] = E.N[0] + (a0[0] * a0[0] + a1[0] * a1[0]);
-    E.N[1] = E.N[1] + (a0[0] * a0[1] + a1[0] * a1[1]);
-    E.N[2] = E.N[2] + (a0[0] * a0[2] + a1[0] * a1[2]);
-    E.N[3] = E.N[3] + (a0[1] * a0[1] + a1[1] * a1[1]);
-    E.N[4] = E.N[4] + (a0[1] * a0[2] + a1[1] * a1[2]);
-    E.N[5] = E.N[5] + (a0[2] * a0[2] + a1[2] * a1[2]);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) E.g[q] = E.g[q] + (a0[q] * b0 + a1[q] * b1);
-}
-__device__ __forceinline__ void up_add_jtj(double* S, const double* J) {
-    S[0] = S[0] + (J[0] * J[0] + J[3] * J[3]);
-    S[1] = S[1] + (J[0] * J[1] + J[3] * J[4]);
-    S[2] = S[2] + (J[0] * J[2] + J[3] * J[5]);
-    S[3] = S[3] + (J[1] * J[1] + J[4] * J[4]);
-    S[4] = S[4] + (J[1] * J[2] + J[4] * J[5]);
-    S[5] = S[5] + (J[2] * J[2] + J[5] * J[5]);
-}
-// symmetric 3x3 {n00, n01, n02, n11, n12, n22}: cofactors (same order) and the determinant
-__device__ __forceinline__ double up_sym33_cof(const double* N, double* c) {
-    c[0] = N[3] * N[5] - N[4] * N[4];
-    c[1] = N[2] * N[4] - N[1] * N[5];
-    c[2] = N[1] * N[4] - N[2] * N[3];
-    c[3] = N[0] * N[5] - N[2] * N[2];
-    c[4] = N[1] * N[2] - N[0] * N[4];
-    c[5] = N[0] * N[3] - N[1] * N[1];
-    return (N[0] * c[0] + N[1] * c[1]) + N[2] * c[2];
-}
-__device__ __forceinline__ void up_cam_center(const double* __restrict__ R, const double* __restrict__ t, double* C) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) C[i] = -((R[i] * t[0] + R[3 + i] * t[1]) + R[6 + i] * t[2]);
-}
 
 // ---- walks along FeaturePoint::preFrame ------------------------------------------------------------------------------------------------------
 // A point's feature in a camera as the reference holds it: MapPoint::pFeatures[c] -- of this frame, or an older one when the camera lost
@@ -1912,6 +1870,21 @@ __global__ __launch_bounds__(256) void k_history_span(int set, int nCams, int fi
         *a = *b;
 }
 
+// k_history_span's write direction behind a guard word: nothing is stored when *guard != 0 (a solve that failed on the device must not
+// touch the state; the host learns of it only later)
+__global__ __launch_bounds__(256) void k_history_span_guarded(int nCams, int firstFrame, int nFrames, const double* __restrict__ R,
+                                                              const double* __restrict__ t, double* hR, double* hT, int H, int head,
+                                                              int lastFrame, const int* __restrict__ guard) {
+    if (*guard != 0) return;
+    const int q = blockIdx.x * 256 + threadIdx.x, i = q / 12, e = q - 12 * i;
+    if (i >= nCams * nFrames) return;
+    const int c = i / nFrames, f = firstFrame + (i - c * nFrames), rs = (head - (lastFrame - f) + 2 * H) % H;
+    if (e < 9)
+        hR[((size_t)c * H + rs) * 9 + e] = R[9 * (size_t)i + e];
+    else
+        hT[((size_t)c * H + rs) * 3 + (e - 9)] = t[3 * (size_t)i + (e - 9)];
+}
+
 // the entry at ring slot rs of every camera (pixels [2N], R [9], t [3]) into archive entry a (same layout, archCap for H)
 __global__ __launch_bounds__(256) void k_history_archive(int nCams, int N, int H, int rs, int archCap, int a, const double* __restrict__ xy,
                                                          const double* __restrict__ R, const double* __restrict__ t, double* axy, double* aR,
@@ -2343,6 +2316,31 @@ extern "C" int cs_track_history_get_span_dev(const cs_track_history* h, void* hi
 extern "C" int cs_track_history_set_span_dev(cs_track_history* h, void* hip_stream, int firstFrame, int nFrames, const double* d_R,
                                              const double* d_t) {
     return hist_span("cs_track_history_set_span_dev", h, hip_stream, 1, firstFrame, nFrames, (double*)d_R, (double*)d_t);
+}
+extern "C" int cs_track_history_set_span_guarded_dev(cs_track_history* h, void* hip_stream, int firstFrame, int nFrames, const double* d_R,
+                                                     const double* d_t, const int* d_guard) {
+    const char* who = "cs_track_history_set_span_guarded_dev";
+    if (!h || nFrames < 0 || (nFrames > 0 && (!d_R || !d_t)) || !d_guard) {
+        cs_set_error("%s: bad arguments", who);
+        return CS_ERR_INVALID;
+    }
+    if (nFrames == 0) return CS_OK;
+    if (firstFrame + nFrames - 1 > h->lastFrame || h->lastFrame - firstFrame >= h->count) {
+        cs_set_error("%s: frames %d..%d are not all in the ring (it holds %d frame(s), the newest %d)", who, firstFrame, firstFrame + nFrames - 1,
+                     h->count, h->lastFrame);
+        return CS_ERR_INVALID;
+    }
+    // (whether the poses move only the device knows: the bookkeeping is that of a write)
+    h->ringVersion += 1;
+    if (firstFrame <= h->lastFrame - h->walkLen) {
+        h->tailEpoch += 1;
+        if (firstFrame < h->tailFromMin) h->tailFromMin = firstFrame;
+    }
+    CS_HIP(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_history_span_guarded, dim3((h->nCams * nFrames * 12 + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, h->nCams,
+                       firstFrame, nFrames, d_R, d_t, h->R, h->t, h->H, h->head, h->lastFrame, d_guard);
+    CS_HIP(hipGetLastError());
+    return CS_OK;
 }
 extern "C" int cs_track_history_newest_frame(const cs_track_history* h) { return h ? h->lastFrame : -0x7fffffff; }
 extern "C" int cs_track_history_cams(const cs_track_history* h) { return h ? h->nCams : 0; }

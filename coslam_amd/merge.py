@@ -172,3 +172,132 @@ class MergePoseCorrection:
     def close(self):
         self.key.close()
         self.chains.close()
+
+
+def _camera_groups_record(groups, group_id=None):
+    """a list of camera-id lists (or a CameraGroups) -> a CameraGroups record, unused entries -1 / 0"""
+    from .grouping import CameraGroups
+
+    if isinstance(groups, CameraGroups):
+        return CameraGroups.from_buffer_copy(bytes(groups))
+    rec = CameraGroups()
+    C.memset(C.byref(rec), 0xFF, C.sizeof(CameraGroups))
+    rec.groupNum = len(groups)
+    for g in range(MAX_CAMS):
+        rec.num[g] = len(groups[g]) if g < len(groups) else 0
+    for g, cams in enumerate(groups):
+        for i, c in enumerate(cams):
+            rec.camIds[g][i] = int(c)
+            rec.groupId[int(c)] = g
+    if group_id is not None:
+        for c, g in enumerate(group_id):
+            rec.groupId[c] = int(g)
+    return rec
+
+
+def merge_matched_groups(groups, gid1, gid2, camid1, camid2):
+    """cs_merge_matched_groups (host code): MergeCameraGroup::mergeMatchedGroups + the m_groupId loop of CoSLAM::mergeCamGroups.  groups: a
+    CameraGroups record or a list of camera-id lists; gid1 / gid2: the group ids of the valid merge infos.  Returns dict(record, groups,
+    group_id [16], merged_gid); raises CoslamHipError where the reference asserts (neither camera in a group)."""
+    import numpy as np
+
+    rec = _camera_groups_record(groups)
+    a, b = np.ascontiguousarray(gid1, dtype=np.int32).reshape(-1), np.ascontiguousarray(gid2, dtype=np.int32).reshape(-1)
+    assert len(a) == len(b)
+    gid, mg = np.zeros(MAX_CAMS, np.int32), C.c_int(-1)
+    p = lambda v: C.c_void_p(v.ctypes.data) if len(v) else None  # noqa: E731
+    check(lib().cs_merge_matched_groups(C.byref(rec), len(a), p(a), p(b), int(camid1), int(camid2), C.c_void_p(gid.ctypes.data), C.byref(mg)),
+          "cs_merge_matched_groups")
+    return dict(record=rec, groups=rec.groups(), group_id=gid, merged_gid=mg.value)
+
+
+def recompute_map_points_keyfrms_dev(history, stream_ptr, cams, d_featRef, nMap, d_mapCount, d_firstFrame, d_lastFrame, d_mapFlags, f_start,
+                                     f_end, d_keyFrames, nKey, d_mapPts, d_mapCov, pixelErrVar, updateCov=True, d_counts=None, d_guard=None):
+    """cs_recompute_map_points_keyfrms_dev: CoSLAM::getMapPts(f_start, f_end) + MergeCameraGroup::recomputeMapPoints -- every certain-static
+    map point of the span triangulated again from its key-frame views (updateStaticPointPositionAtKeyFrms) over the history's poses, in
+    place, one launch.  history: a TrackHistory; cams: K, iK per camera; d_keyFrames: ascending int32 frame numbers in device memory."""
+    from .poseupdate import poseupdate_cams
+
+    vp = C.c_void_p
+    check(lib().cs_recompute_map_points_keyfrms_dev(vp(history._h), vp(stream_ptr), poseupdate_cams(cams), vp(d_featRef), int(nMap), vp(d_mapCount),
+                                                    vp(d_firstFrame), vp(d_lastFrame), vp(d_mapFlags), int(f_start), int(f_end), vp(d_keyFrames),
+                                                    int(nKey), vp(d_mapPts), vp(d_mapCov), C.c_double(pixelErrVar), 1 if updateCov else 0,
+                                                    vp(d_counts), vp(d_guard)), "cs_recompute_map_points_keyfrms_dev")
+
+
+class MergeApply:
+    """cs_merge_apply: a merge's pose correction fed from and written to a TrackHistory, and the map behind it -- from "valid MergeInfo {R, t}
+    exist" to "history and map are the merged ones" on one stream, no host wait.  plan: merge_keygraph_plan's dict (node_kf counted over ALL
+    key frames given to the plan); key_frames: the frame numbers of those key frames, oldest first, the current key frame last; n_cams: the
+    history's cameras (every one gets its chain, also those outside the plan).  MergePoseCorrection is the host-fed form of the same solve."""
+
+    def __init__(self, plan, key_frames, n_cams, device=0):
+        import numpy as np
+        import torch
+
+        L = lib()
+        L.cs_merge_apply_create.restype = C.c_void_p
+        L.cs_merge_apply_guard.restype = C.c_void_p
+        self._L, self.device, self.n_cams = L, int(device), int(n_cams)
+        fx = int(plan["fixed_kf"]) if "fixed_kf" in plan else int(np.min(plan["node_kf"]))
+        self.key_frames = np.ascontiguousarray(np.asarray(key_frames, dtype=np.int32)[fx:])
+        node_kf = np.ascontiguousarray(np.asarray(plan["node_kf"], dtype=np.int32) - fx)
+        node_cam = np.ascontiguousarray(plan["node_cam"], dtype=np.int32)
+        fixed = np.ascontiguousarray(plan["fixed"], dtype=np.uint8)
+        id1, id2 = np.ascontiguousarray(plan["id1"], dtype=np.int32), np.ascontiguousarray(plan["id2"], dtype=np.int32)
+        sid = np.ascontiguousarray(plan["scale_id"], dtype=np.int32)
+        self.n_edges, self.n_constraint = len(id1), int((sid >= 0).sum())
+        p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+        self._a = L.cs_merge_apply_create(self.device, self.n_cams, len(self.key_frames), p(self.key_frames), len(node_kf), p(node_kf), p(node_cam),
+                                          p(fixed), len(id1), p(id1), p(id2), p(sid))
+        if not self._a:
+            check(-1, "cs_merge_apply_create")
+        dev = torch.device("cuda", self.device)
+        self._torch = torch
+        self.d_edgeS = torch.zeros(max(self.n_edges, 1), dtype=torch.float64, device=dev)
+        self.d_key_frames = torch.as_tensor(self.key_frames, device=dev)
+        self._keep = None
+
+    @property
+    def guard_ptr(self):
+        """device pointer of the guard word (1 when the last run's solves failed)"""
+        return int(self._L.cs_merge_apply_guard(C.c_void_p(self._a)) or 0)
+
+    def run(self, history, info_R, info_T, stream_ptr=None):
+        """cs_merge_apply_run_dev: info_R [nConstraint][9] / info_T [nConstraint][3] = MergeInfo::R / t of the constraint edges in edge order
+        (torch device tensors, or host arrays that are uploaded first).  Enqueues only; the solved scales land in self.d_edgeS."""
+        torch = self._torch
+        dev = self.d_edgeS.device
+        dR = torch.as_tensor(info_R, dtype=torch.float64).reshape(-1, 9).to(dev).contiguous()
+        dT = torch.as_tensor(info_T, dtype=torch.float64).reshape(-1, 3).to(dev).contiguous()
+        assert dR.shape[0] == self.n_constraint and dT.shape[0] == self.n_constraint
+        self._keep = (dR, dT)
+        s = torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        vp = C.c_void_p
+        check(self._L.cs_merge_apply_run_dev(vp(self._a), vp(history._h), vp(s), vp(dR.data_ptr()), vp(dT.data_ptr()), vp(self.d_edgeS.data_ptr())),
+              "cs_merge_apply_run_dev")
+
+    def recompute(self, history, cams, d_featRef, nMap, d_mapCount, d_firstFrame, d_lastFrame, d_mapFlags, d_mapPts, d_mapCov, f_start,
+                  pixelErrVar, updateCov=True, d_counts=None, stream_ptr=None):
+        """MergeCameraGroup::recomputeMapPoints behind run(), guarded by its solves: f_end = the current key frame; the caller forms
+        f_start = max(fixed frame, last release frame) as CoSLAM::mergeCamGroups does (reference src/app/SL_CoSLAM.cpp:1430-1434)."""
+        s = self._torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        recompute_map_points_keyfrms_dev(history, s, cams, d_featRef, nMap, d_mapCount, d_firstFrame, d_lastFrame, d_mapFlags, f_start,
+                                         int(self.key_frames[-1]), self.d_key_frames.data_ptr(), len(self.key_frames), d_mapPts, d_mapCov,
+                                         pixelErrVar, updateCov, d_counts, self.guard_ptr)
+
+    def status(self, stream_ptr=None):
+        """cs_merge_apply_status: waits; raises CoslamHipError (CS_ERR_NUMERIC) naming the failed graph"""
+        s = self._torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        check(self._L.cs_merge_apply_status(C.c_void_p(self._a), C.c_void_p(s)), "cs_merge_apply_status")
+
+    def close(self):
+        if self._a:
+            self._L.cs_merge_apply_destroy(C.c_void_p(self._a))
+            self._a = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

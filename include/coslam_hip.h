@@ -628,6 +628,10 @@ int cs_track_history_set_poses_dev(cs_track_history* h, void* hip_stream, int n,
  * All of firstFrame .. firstFrame + nFrames - 1 must be in the ring. */
 int cs_track_history_get_span_dev(const cs_track_history* h, void* hip_stream, int firstFrame, int nFrames, double* d_R, double* d_t);
 int cs_track_history_set_span_dev(cs_track_history* h, void* hip_stream, int firstFrame, int nFrames, const double* d_R, const double* d_t);
+/* cs_track_history_set_span_dev behind a guard: *d_guard (one int in device memory, read by the launch) != 0 stores nothing.  For a
+ * write-back whose producer can fail on the device while the host has not waited for it (cs_merge_apply_run_dev). */
+int cs_track_history_set_span_guarded_dev(cs_track_history* h, void* hip_stream, int firstFrame, int nFrames, const double* d_R,
+                                          const double* d_t, const int* d_guard);
 int cs_track_history_newest_frame(const cs_track_history* h); /* the frame of the newest entry */
 int cs_track_history_cams(const cs_track_history* h);
 /* The WHOLE-RUN ARCHIVE behind the store: capFrames (0 = none, the default) frames of what the store holds per frame -- every slot's
@@ -839,6 +843,18 @@ int cs_merge_keygraph_plan(int nKeyFrames, const int* frames, const cs_camera_gr
                            int nodeCap, int* nNodes, int* nodeKf, int* nodeCam, unsigned char* fixed, int edgeCap, int* nEdges, int* id1,
                            int* id2, int* scaleId, int* nConstraintEdge);
 
+/* ---- what a merge does to the groups and the map behind its pose correction; DESIGN.md 3.21 ----
+ * MergeCameraGroup::mergeMatchedGroups (src/app/SL_MergeCameraGroup.cpp:1117-1174) and the m_groupId loop behind it
+ * (src/app/SL_CoSLAM.cpp:1419-1424); host code, no device.  groups: the current record (m_groups / m_groupNum / m_groupId), in / out, in
+ * HOST memory; gid1 / gid2 [nInfo]: groupId1 / groupId2 of the VALID merge infos, in either order.  Groups joined by an info become one:
+ * the connected components of the group graph -- ordered by ascending smallest member, members ascending (findConnectedComponents is
+ * un-vendored LibVisualSLAM: this order is the library's definition) --, the cameras appended group by group in each old
+ * group's own order.  groupId [16]: m_groupId afterwards (also written into the record; cameras of no group keep their entry); *mergedGid:
+ * the first new group that holds camid1 or camid2 (m_camid1 / m_camid2).  CS_ERR_INVALID where the reference asserts (neither camera in a
+ * group) and for ids outside the record; the record is then left as it was. */
+int cs_merge_matched_groups(cs_camera_groups* groups, int nInfo, const int* gid1, const int* gid2, int camid1, int camid2, int* groupId,
+                            int* mergedGid);
+
 /* ---- live view: CoSLAM::getNumDynamicStaticPoints (src/app/SL_CoSLAM.cpp:1447-1471), CoSLAM::storeDynamicPoints (:1900-1911) and the
  * display's getDynTracks (src/gui/GLScenePane.cpp:19-52) -------------------------------------------------------------------------------------
  * The frame's last step (src/gui/CoSLAMThread.cpp:117-120, behind currentMapPointsRegister); DESIGN.md 3.18.  A map point TAKES PART when
@@ -989,6 +1005,66 @@ int cs_update_new_poses_points_ref_dev(const cs_track_history* h, void* hip_stre
                                        int* d_counts);
 int cs_refine_map_points_ref_dev(const cs_track_history* h, void* hip_stream, const cs_poseupdate_cam* cams, const cs_feat_ref* d_featRef,
                                  int nMap, const unsigned char* d_select, double* d_mapPts, double* d_mapCov, double pixelErrVar, int* d_count);
+/* ---- the corrected poses of a merge into the history ----
+ * MergeCameraGroup::recomputeKeyCamPoses + recomputeAllCameraPoses (src/app/SL_MergeCameraGroup.cpp:1083-1116) from "valid MergeInfo {R, t}
+ * exist" to "the history holds the corrected poses", enqueued on one stream with no host wait in between.  The handle is built per merge
+ * (host work): keyFrames [nKey] ascending frame numbers, [0] = the FIXED key frame, [nKey - 1] = the current key frame; the node table and
+ * the edges are cs_merge_keygraph_plan's output with nodeKf counted from the fixed key frame (index into keyFrames).  create builds the
+ * scaled key graph (cs_posegraph_create_scaled) and the nCams chain graphs of _constructGraphForAllFrms (:1037-1082) for ALL cameras of the
+ * history, not only the plan's: one node per frame of keyFrames[0] .. keyFrames[nKey - 1], fixed at the key frames, one edge per
+ * consecutive pair.  NULL on failure (cs_last_error).
+ * run_dev: the span out of the history (cs_track_history_get_span_dev), the key nodes gathered from it, the plain key edges and all chain
+ * edges from the poses BEFORE the correction, the constraint rows from d_infoR [nConstraint][9] / d_infoT [nConstraint][3] (MergeInfo::R / t
+ * in edge order, DEVICE memory), the key graph relaxed, its poses into the chains' fixed nodes, the chains relaxed, the span written back.
+ * d_edgeS [nEdges] or NULL: the key graph's solved scales.  The same kernels on the same inputs as the host-fed sequence, bit for bit.
+ * Refused with CS_ERR_INVALID before anything is enqueued: the history's newest frame is not keyFrames[nKey - 1]; a frame of the span has
+ * left the store (an archived pose is final, see cs_track_history_set_archive).
+ * A FAILED SOLVE DOES NOT TOUCH THE STATE: a component of either graph can fail numerically while the host has not waited, so the
+ * write-back reads the solvers' status words on the device and stores nothing when any is non-zero (cs_track_history_set_span_guarded_dev
+ * behind the handle's guard word; cs_merge_apply_guard returns it for cs_recompute_map_points_keyfrms_dev).
+ * status: waits for hip_stream; CS_OK, or CS_ERR_NUMERIC naming the failed graph. */
+typedef struct cs_merge_apply cs_merge_apply;
+cs_merge_apply* cs_merge_apply_create(int device, int nCams, int nKey, const int* keyFrames, int nNodes, const int* nodeKf, const int* nodeCam,
+                                      const unsigned char* fixed, int nEdges, const int* id1, const int* id2, const int* scaleId);
+int cs_merge_apply_run_dev(cs_merge_apply* a, cs_track_history* h, void* hip_stream, const double* d_infoR, const double* d_infoT,
+                           double* d_edgeS);
+int cs_merge_apply_status(cs_merge_apply* a, void* hip_stream);
+const int* cs_merge_apply_guard(const cs_merge_apply* a); /* device pointer: 1 when the last run_dev's solves failed, else 0 */
+/* the handle's copy of keyFrames in DEVICE memory (what cs_recompute_map_points_keyfrms_dev takes as d_keyFrames) */
+const int* cs_merge_apply_key_frames(const cs_merge_apply* a, int* nKey);
+void cs_merge_apply_destroy(cs_merge_apply* a);
+/* ---- the map behind a merge's pose correction (cs_merge_matched_groups is its companion) ----
+ * CoSLAM::getMapPts(fStart, fEnd) (src/app/SL_CoSLAM.cpp:1818-1851) followed by MergeCameraGroup::recomputeMapPoints
+ * (src/app/SL_MergeCameraGroup.cpp:1175-1183) in one launch: every selected map point is triangulated again from its KEY-FRAME views by
+ * updateStaticPointPositionAtKeyFrms (src/slam/SL_CoSLAMHelper.cpp:395-451), in place.  The poses are the history's as they stand (after a
+ * merge: as corrected), the pixels the history's, the features the references d_featRef [nMap][nCams] with h's linked-segment pools.
+ *   selection   row m takes part when m < *d_mapCount (NULL: nMap), d_mapFlags[m] == 0 (isCertainStatic), d_lastFrame[m] >= fStart and
+ *               d_firstFrame[m] <= fEnd (the reference scans all three map lists; the arrays hold all of them).
+ *   key frames  d_keyFrames [nKey]: the key frames' numbers, ASCENDING, in device memory.  A key frame is one of every camera (addKeyFrame
+ *               calls addKeyPose per camera): FeaturePoint::bKeyFrm of a node is "its frame is on the list".
+ *   views       per camera c ascending: the head d_featRef[m][c] is a view only when its slot is >= 0 and its frame is a key frame the store
+ *               holds -- otherwise the camera gives NOTHING, whatever older nodes of the chain are (:402).  Behind the head the WHOLE chain is
+ *               walked (the run [first, frame - 1] on the head's slot, then the linked segments {slot, last, first, next}); of its key-frame
+ *               nodes the one whose camera centre subtends the largest angle with the head's centre at the point's CURRENT position is the
+ *               second view.  The comparison is strict from 0 (:427), so the first node of the backward walk (the newest) wins among equals
+ *               and an angle of 0 never wins.  COSINES are compared, not angles, as in every walk of this library (acos is monotone; two
+ *               cosines closer than acos resolves may order differently).
+ *   output      with at least two views triangulateMultiView in that view order and, when updateCov != 0, getTriangulateCovMat at the new
+ *               point, into d_mapPts [nMap][3] / d_mapCov [nMap][9]; a row with fewer than two views is not written.
+ *   walk limits a walk ends at the store's oldest frame (older nodes are no views); there is NO node cap (histLen does not bound it); a
+ *               segment index outside the pool, a segment of no slot, or more hops than the pool has segments end it (a corrupt pool
+ *               cannot loop or read out of bounds).
+ *   d_counts    [4] or NULL, accumulated, never cleared here: rows selected, rows re-triangulated, rows left with fewer than two views,
+ *               walks cut by the store's end or the hop guard.
+ * d_guard (one int in device memory, or NULL): != 0 when the launch runs -> nothing is selected, written or counted; cs_merge_apply_guard's
+ * word lets the re-triangulation be enqueued behind cs_merge_apply_run_dev without a wait.
+ * cams: K and iK of every camera of h.  A wave per map point; the lanes step over the KEY FRAMES of a run (two binary searches map a run of
+ * frames to a slice of the list), so a walk's cost scales with key frames, not frames.  One launch, no host wait, no scratch of h. */
+int cs_recompute_map_points_keyfrms_dev(const cs_track_history* h, void* hip_stream, const cs_poseupdate_cam* cams,
+                                        const cs_feat_ref* d_featRef, int nMap, const int* d_mapCount, const int* d_firstFrame,
+                                        const int* d_lastFrame, const unsigned char* d_mapFlags, int fStart, int fEnd, const int* d_keyFrames,
+                                        int nKey, double* d_mapPts, double* d_mapCov, double pixelErrVar, int updateCov, int* d_counts,
+                                        const int* d_guard);
 
 /* CoSLAM::mapPointsClassify (src/app/SL_CoSLAM.cpp:418-520) over the references: from the next call on cs_map_points_classify_dev and
  * cs_pose_update_classify_frame_dev read d_featRef ([nMap][nCams], the table cs_feat_ref_advance_dev keeps: as the END of the previous
