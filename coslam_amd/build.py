@@ -28,6 +28,7 @@ HIP_SOURCES = [
     "merge.hip",
     "merge_graph.cpp",
     "merge_apply.hip",
+    "merge_constraints.hip",
     "liveview.hip",
     "poseupdate.hip",
     "ncc.hip",

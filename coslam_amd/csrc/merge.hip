@@ -8,9 +8,10 @@
 // (x, y) is set when the integer point gives <= 0 on every edge with the hull's own orientation function; a hull with fewer than three
 // vertices sets no pixel.
 //
-// NOT BUILT: everything behind the gate (storeFeaturePoints, matchMergableCameras, the pose graphs, the merge BAs, mergeMatchedGroups,
-// recomputeMapPoints), and the m_lastFrmGroupMerge + 130 hold-off of mergeCamGroups (:1376): nothing ever merges here, so m_lastFrmGroupMerge
-// never moves and the hold-off could never fire.
+// NOT BUILT HERE: what stands behind the gate.  Of it storeFeaturePoints and the front of matchMergableCameras (SURF, estimateEMat, the
+// guided matcher) stay on the host; genMergeInfoVer2 up to and behind its solver call is merge_constraints.hip, the pose graphs
+// posegraph.hip / merge_graph.cpp (3.20), mergeMatchedGroups and recomputeMapPoints merge_apply.hip (3.21).  The m_lastFrmGroupMerge + 130
+// hold-off of mergeCamGroups (:1376) is the caller's: no loop merges yet, so m_lastFrmGroupMerge never moves and it could never fire.
 //
 // One launch: one workgroup per ORDERED camera pair (i, j).  It compacts camera i's features with a non-false map point in slot
 // order, projects them with camera j's K, R, t (project_dev.h), keeps the in-image projections in LDS (nInCam), takes their hull when

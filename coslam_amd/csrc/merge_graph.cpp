@@ -1,4 +1,5 @@
-// merge_graph.cpp -- the key-frame pose graph of a camera-group merge as a host plan (no device work), DESIGN 3.20.
+// merge_graph.cpp -- the key-frame pose graph of a camera-group merge as a host plan (no device work); behind it the host
+// halves of 3.21 (cs_merge_matched_groups) and 3.22 (cs_merge_first_constrain).
 //
 // Replaces MergeCameraGroup::searchFirstKeyFrameForMerge (src/app/SL_MergeCameraGroup.cpp:884-906) and the topology of
 // _constructGraphForKeyFrms (:907-1035) over host copies of the key frames' records: which key frame is held fixed, the
@@ -203,5 +204,52 @@ extern "C" int cs_merge_matched_groups(cs_camera_groups* groups, int nInfo, cons
     for (int c = 0; c < 16; ++c) out.groupId[c] = groupId[c];
     *groups = out;
     *mergedGid = mg;
+    return CS_OK;
+}
+
+// ---- MergeCameraGroup::buildIdMapForSelfKeyPoses(camIds, nSelfMotion = 2) (src/app/SL_MergeCameraGroup.cpp:512-555) over host arrays: which
+// key frame is m_pFirstConstrainFrm, and the pose order of the merge's bundle adjustment.  The loop is restated as written:
+//   min_kf = current; for c in camIds: for (kf = current->prev, nself = 0; kf && nself < 2; kf = kf->prev)
+//       if (kf->pPose[c]->bSelfMotion) { if (min_kf->f >= kf->f) min_kf = kf; nself++; }
+// With no self-motion key frame at all min_kf stays the current key frame and the reference's ind_to_order maps both halves of the order onto
+// the second one; that is refused here.
+extern "C" int cs_merge_first_constrain(int nKeyFrames, const int* frames, const unsigned char* selfMotion, int nCams, int nCamIds,
+                                        const int* camIds, int* firstConstrain, int* orderFrame, int* orderCam) {
+    if (firstConstrain) *firstConstrain = -1;
+    if (nKeyFrames <= 0 || !frames || !selfMotion || nCams < 1 || nCams > 16 || nCamIds <= 0 || nCamIds > 16 || !camIds || !firstConstrain ||
+        !orderFrame || !orderCam) {
+        cs_set_error("cs_merge_first_constrain: bad argument");
+        return CS_ERR_INVALID;
+    }
+    for (int k = 1; k < nKeyFrames; ++k)
+        if (frames[k] <= frames[k - 1]) {
+            cs_set_error("cs_merge_first_constrain: key frames must be given oldest first (frame %d behind %d)", frames[k], frames[k - 1]);
+            return CS_ERR_INVALID;
+        }
+    for (int i = 0; i < nCamIds; ++i)
+        if (camIds[i] < 0 || camIds[i] >= nCams || (i > 0 && camIds[i] <= camIds[i - 1])) {
+            cs_set_error("cs_merge_first_constrain: camIds must be ascending camera ids below %d", nCams);
+            return CS_ERR_INVALID;
+        }
+    int mn = nKeyFrames - 1;
+    for (int i = 0; i < nCamIds; ++i) {
+        const int c = camIds[i];
+        int nself = 0;
+        for (int k = nKeyFrames - 2; k >= 0 && nself < 2; --k)
+            if (selfMotion[(size_t)k * nCams + c]) {
+                if (frames[mn] >= frames[k]) mn = k;
+                nself++;
+            }
+    }
+    if (mn == nKeyFrames - 1) {
+        cs_set_error("cs_merge_first_constrain: no camera of the two groups has a self-motion key frame behind frame %d: no first-constrained frame",
+                     frames[nKeyFrames - 1]);
+        return CS_ERR_INVALID;
+    }
+    *firstConstrain = mn;
+    for (int i = 0; i < nCamIds; ++i) {
+        orderFrame[i] = frames[nKeyFrames - 1], orderCam[i] = camIds[i];
+        orderFrame[nCamIds + i] = frames[mn], orderCam[nCamIds + i] = camIds[i];
+    }
     return CS_OK;
 }

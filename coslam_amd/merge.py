@@ -277,6 +277,14 @@ class MergeApply:
         check(self._L.cs_merge_apply_run_dev(vp(self._a), vp(history._h), vp(s), vp(dR.data_ptr()), vp(dT.data_ptr()), vp(self.d_edgeS.data_ptr())),
               "cs_merge_apply_run_dev")
 
+    def run_dev(self, history, d_infoR, d_infoT, stream_ptr=None):
+        """cs_merge_apply_run_dev with MergeInfo::R / t given as DEVICE POINTERS ([nConstraint][9] / [3] doubles in edge order), e.g.
+        MergeConstraints.buf.infoR / infoT as cs_merge_info_dev left them.  Enqueues only."""
+        s = self._torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        vp = C.c_void_p
+        check(self._L.cs_merge_apply_run_dev(vp(self._a), vp(history._h), vp(s), vp(d_infoR), vp(d_infoT), vp(self.d_edgeS.data_ptr())),
+              "cs_merge_apply_run_dev")
+
     def recompute(self, history, cams, d_featRef, nMap, d_mapCount, d_firstFrame, d_lastFrame, d_mapFlags, d_mapPts, d_mapCov, f_start,
                   pixelErrVar, updateCov=True, d_counts=None, stream_ptr=None):
         """MergeCameraGroup::recomputeMapPoints behind run(), guarded by its solves: f_end = the current key frame; the caller forms
@@ -295,6 +303,173 @@ class MergeApply:
         if self._a:
             self._L.cs_merge_apply_destroy(C.c_void_p(self._a))
             self._a = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def merge_first_constrain(frames, self_motion, cam_ids):
+    """cs_merge_first_constrain (host code): MergeCameraGroup::buildIdMapForSelfKeyPoses(camIds, 2).  frames: the key frames' numbers, oldest
+    first, the current key frame last; self_motion [nKey][nCams]: KeyPose::bSelfMotion; cam_ids ascending.  Returns (index of the
+    first-constrained key frame -- merge_keygraph_plan's first_constrain --, [(frame, cam)] in the pose order of the merge's bundle
+    adjustment); raises CoslamHipError where no camera has a self-motion key frame behind the current one."""
+    import numpy as np
+
+    fr = np.ascontiguousarray(frames, dtype=np.int32)
+    sm = np.ascontiguousarray(np.asarray(self_motion) != 0, dtype=np.uint8).reshape(len(fr), -1)
+    ids = np.ascontiguousarray(cam_ids, dtype=np.int32)
+    of, oc = np.zeros(2 * max(len(ids), 1), np.int32), np.zeros(2 * max(len(ids), 1), np.int32)
+    fc = C.c_int(-1)
+    p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+    check(lib().cs_merge_first_constrain(len(fr), p(fr), p(sm), sm.shape[1], len(ids), p(ids), C.byref(fc), p(of), p(oc)), "cs_merge_first_constrain")
+    return fc.value, [(int(f), int(c)) for f, c in zip(of[:2 * len(ids)], oc[:2 * len(ids)])]
+
+
+MERGE_OK, MERGE_REJECT, MERGE_FEW, MERGE_BAD_GROUPS = 1, 0, -1, -2
+MERGE_VIEW_FROM_M2, MERGE_VIEW_DETACHED, MERGE_VIEW_PREV, MERGE_VIEW_PREV_DETACHED = 1, 2, 4, 8
+
+
+class MergeConstraintsHeader(C.Structure):
+    """== cs_merge_constraints_header (include/coslam_hip.h)."""
+
+    _fields_ = [(n, C.c_int) for n in ("verdict", "nPose", "P", "nObs", "nMergedTracks", "nUnmerged", "nPrevViews", "skippedMatches", "nMergeViews",
+                                       "f1", "f2", "nCamIds")] + [("camIds", C.c_int * MAX_CAMS), ("nInfo", C.c_int), ("reserved", C.c_int),
+                                                                  ("avgErr", C.c_double)]
+
+
+class MergeConstraintsBuffers(C.Structure):
+    """== cs_merge_constraints_buffers (include/coslam_hip.h)."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("header", "views", "Ks", "Rs", "Ts", "pts", "pointMap", "obsPtr", "obsCam", "obsXY", "info", "infoValid",
+                                          "infoR", "infoT")] + [(n, C.c_int) for n in ("maxPoints", "maxObs", "maxViews", "maxInfo")] + \
+               [(n, C.c_void_p) for n in ("solvedRs", "solvedTs", "solvedPts", "outlier")]
+
+
+class MergeConstraints:
+    """cs_merge_constraints: MergeCameraGroup::genMergeInfoVer2 on the device, from the matched features of two cameras to the merge's
+    bundle-adjustment problem (assemble) and from a set of poses to the MergeInfo {R, t} list (info).  The buffers stay in device memory
+    (d_info_R / d_info_T are what MergeApply.run takes); problem() / views() / infos() download them for a host-side caller."""
+
+    def __init__(self, n_cams, N, max_matches, max_map, device=0):
+        L = lib()
+        L.cs_merge_constraints_create.restype = C.c_void_p
+        self._L, self.device, self.n_cams, self.N = L, int(device), int(n_cams), int(N)
+        self._m = L.cs_merge_constraints_create(self.device, self.n_cams, self.N, int(max_matches), int(max_map))
+        if not self._m:
+            check(-1, "cs_merge_constraints_create")
+        self.buf = MergeConstraintsBuffers()
+        check(L.cs_merge_constraints_buffers_get(C.c_void_p(self._m), C.byref(self.buf)), "cs_merge_constraints_buffers_get")
+        self._keep = None
+
+    def _stream(self, stream_ptr):
+        import torch
+
+        return torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+
+    def assemble(self, history, cams, d_featRef, nMap, d_mapPts, d_groups, gId1, gId2, maxiCam, maxjCam, f1, f2, matches, stream_ptr=None):
+        """cs_merge_constraints_assemble_dev.  cams: a merge_cams() array or a list of dicts of device pointers (xy, state, slot2map, K of the
+        current key frame); matches: an int32 [K][2] slot-pair table.  A torch DEVICE tensor is taken as it is and must be ready on the
+        stream the launch goes to (nothing is copied, the call only enqueues); a host array goes through cs_merge_constraints_assemble,
+        which copies it into the handle's own table on that same stream in front of the launch."""
+        import numpy as np
+        import torch
+
+        vp = C.c_void_p
+        arr = merge_cams(cams)
+        head = (vp(self._m), vp(history._h), vp(self._stream(stream_ptr)), arr, vp(d_featRef), int(nMap), vp(d_mapPts), vp(d_groups), int(gId1),
+                int(gId2), int(maxiCam), int(maxjCam), int(f1), int(f2))
+        if isinstance(matches, torch.Tensor) and matches.is_cuda:
+            dm = matches.to(torch.int32).reshape(-1, 2).contiguous()
+            self._keep = dm
+            check(self._L.cs_merge_constraints_assemble_dev(*head, vp(dm.data_ptr()) if dm.shape[0] else None, int(dm.shape[0])),
+                  "cs_merge_constraints_assemble_dev")
+        else:
+            hm = np.ascontiguousarray(np.asarray(matches, dtype=np.int32).reshape(-1, 2))
+            check(self._L.cs_merge_constraints_assemble(*head, vp(hm.ctypes.data) if len(hm) else None, len(hm)), "cs_merge_constraints_assemble")
+
+    def info(self, d_groups, gId1, gId2, d_Rs=None, d_Ts=None, stream_ptr=None):
+        """cs_merge_info_dev from the poses d_Rs / d_Ts (device pointers, [nPose][9] / [3] in the assembled order; default: the assembled,
+        unsolved poses).  Enqueues only."""
+        vp = C.c_void_p
+        check(self._L.cs_merge_info_dev(vp(self._m), vp(self._stream(stream_ptr)), vp(d_groups), int(gId1), int(gId2),
+                                        vp(self.buf.Rs if d_Rs is None else d_Rs), vp(self.buf.Ts if d_Ts is None else d_Ts)), "cs_merge_info_dev")
+
+    def solve(self, stream_ptr=None):
+        """cs_merge_constraints_solve: the two solves of :646-647 on the assembled problem (the existing robust BA, fed the problem read
+        back to the host); waits.  Nothing is solved behind a verdict other than MERGE_OK; a failed solve raises CoslamHipError."""
+        check(self._L.cs_merge_constraints_solve(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr))), "cs_merge_constraints_solve")
+
+    def solution(self, which):
+        """-> dict(Rs, Ts, pts, outlier, stats) of solve `which` (0: maxErr 800, 1 x 100; 1: maxErr 30, 5 x 30) of the last solve()"""
+        import numpy as np
+
+        from .ba import BAStats
+
+        h = self.header()
+        Rs, Ts, pts = np.zeros((h.nPose, 9)), np.zeros((h.nPose, 3)), np.zeros((h.P, 3))
+        out, st = np.zeros(max(h.nObs, 1), np.int32), BAStats()
+        p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+        check(self._L.cs_merge_constraints_solution(C.c_void_p(self._m), int(which), p(Rs), p(Ts), p(pts), p(out), C.byref(st)),
+              "cs_merge_constraints_solution")
+        return dict(Rs=Rs, Ts=Ts, pts=pts, outlier=out[:h.nObs], stats=st)
+
+    def info_solved(self, d_groups, gId1, gId2, stream_ptr=None):
+        """cs_merge_constraints_info_dev: the MergeInfo list from the SOLVED poses; nInfo = 0 behind a rejected verdict, a failed solve or
+        no solve at all.  Enqueues only."""
+        check(self._L.cs_merge_constraints_info_dev(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(d_groups), int(gId1),
+                                                    int(gId2)), "cs_merge_constraints_info_dev")
+
+    def header(self, stream_ptr=None):
+        """the header on the host; waits for the stream"""
+        h = MergeConstraintsHeader()
+        check(self._L.cs_merge_constraints_header_get(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.byref(h)),
+              "cs_merge_constraints_header_get")
+        return h
+
+    def _down(self, ptr, n, dtype, stream_ptr=None):
+        import numpy as np
+
+        out = np.zeros(n, dtype)
+        if out.nbytes:
+            check(self._L.cs_merge_constraints_download(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(ptr),
+                                                        C.c_void_p(out.ctypes.data), C.c_size_t(out.nbytes)), "cs_merge_constraints_download")
+        return out
+
+    def problem(self, stream_ptr=None):
+        """-> dict(header, Ks, Rs, Ts, pts, pointMap, obs_ptr, obs_cam, obs_xy) as numpy, cut to the header's counts"""
+        import numpy as np
+
+        h, b = self.header(stream_ptr), self.buf
+        d = self._down
+        return dict(header=h, Ks=d(b.Ks, 9 * h.nPose, np.float64).reshape(-1, 9), Rs=d(b.Rs, 9 * h.nPose, np.float64).reshape(-1, 9),
+                    Ts=d(b.Ts, 3 * h.nPose, np.float64).reshape(-1, 3), pts=d(b.pts, 3 * h.P, np.float64).reshape(-1, 3),
+                    pointMap=d(b.pointMap, h.P, np.int32), obs_ptr=d(b.obsPtr, h.P + 1, np.int32) if h.verdict == MERGE_OK else np.zeros(1, np.int32),
+                    obs_cam=d(b.obsCam, h.nObs, np.int32), obs_xy=d(b.obsXY, 2 * h.nObs, np.float64).reshape(-1, 2))
+
+    def views(self, stream_ptr=None):
+        """the merge list -> int32 [nMergeViews][7]: track, cam, slot, point, from, flags, prevSlot"""
+        import numpy as np
+
+        h = self.header(stream_ptr)
+        return self._down(self.buf.views, 8 * h.nMergeViews, np.int32).reshape(-1, 8)[:, :7]
+
+    def infos(self, stream_ptr=None):
+        """-> (int32 [nInfo][7]: frame1, cam1, gid1, frame2, cam2, gid2, valid; R [nInfo][9]; t [nInfo][3])"""
+        import numpy as np
+
+        h, b = self.header(stream_ptr), self.buf
+        ints = self._down(b.info, 6 * h.nInfo, np.int32).reshape(-1, 6)
+        valid = self._down(b.infoValid, h.nInfo, np.uint8).astype(np.int32).reshape(-1, 1)
+        return np.concatenate([ints, valid], axis=1), self._down(b.infoR, 9 * h.nInfo, np.float64).reshape(-1, 9), \
+            self._down(b.infoT, 3 * h.nInfo, np.float64).reshape(-1, 3)
+
+    def close(self):
+        if self._m:
+            self._L.cs_merge_constraints_destroy(C.c_void_p(self._m))
+            self._m = None
 
     def __del__(self):
         try:

@@ -1066,6 +1066,116 @@ int cs_recompute_map_points_keyfrms_dev(const cs_track_history* h, void* hip_str
                                         int nKey, double* d_mapPts, double* d_mapCov, double pixelErrVar, int updateCov, int* d_counts,
                                         const int* d_guard);
 
+/* ---- merge constraints: MergeCameraGroup::genMergeInfoVer2 (src/app/SL_MergeCameraGroup.cpp:557-725) from the matched features of two
+ * cameras to the merge's bundle-adjustment problem and, from a set of poses, to the MergeInfo {R, t} list; DESIGN.md 3.22 ----
+ * cs_merge_first_constrain (host code, no device): buildIdMapForSelfKeyPoses(camIds, 2) (:512-555).  frames [nKeyFrames]: the key frames'
+ * numbers, oldest first, the current key frame last; selfMotion [nKeyFrames][nCams]: KeyPose::bSelfMotion per key frame and camera (the
+ * current key frame's row is not read); camIds [nCamIds]: getCamIdsInBothGroups, ascending.  Per camera the newest two self-motion key
+ * frames behind the current one are visited, the oldest of all of them wins (the `>=` of :523).  Out: *firstConstrain = the index of
+ * m_pFirstConstrainFrm (what cs_merge_keygraph_plan takes), and the pose order orderFrame / orderCam [2 * nCamIds]: the current key frame x
+ * camIds, then the first-constrained key frame x camIds.  Where no camera has a self-motion key frame behind the current one the
+ * reference degenerates (both halves of the order name the current key frame); here that is CS_ERR_INVALID. */
+int cs_merge_first_constrain(int nKeyFrames, const int* frames, const unsigned char* selfMotion, int nCams, int nCamIds, const int* camIds,
+                             int* firstConstrain, int* orderFrame, int* orderCam);
+/* The assembly, on the device, read-only on every table it is given.  In the reference's order (every output order is pinned by
+ * tests/golden/mergeconstraints_golden.npz, the reference's own function with a solver stand-in):
+ *   tracks    per match (slot in maxiCam, slot in maxjCam) with both slots features (state 0 / 1) of map points m1 / m2: over the cameras c
+ *             of either group ascending, m1's reference in c when its frame is f2, then m2's (getCorresFeatPtsAndMapPts).  Any other
+ *             match -- a slot outside the table, no feature, no map point -- is counted in skippedMatches.
+ *   verdict   the pixel distance of m1 projected with (K, R, t) of each view's camera at f2 from the view's pixel; the mean of the three
+ *             largest over all views of all tracks > 500: CS_MERGE_REJECT (checkMergeMapPoints).  No track, or fewer than three views:
+ *             CS_MERGE_FEW (the reference asserts / reads past the end).  Otherwise CS_MERGE_OK.  Unless OK nothing else is produced.
+ *   views     the merge list (mergeMapPoints, EMITTED, not applied): one cs_merge_view per view of a merged track in track and view order.
+ *             The later steps see the state as if it were applied: a feature's point is the m1 of the last track that holds it.
+ *   unmerged  the features of the groups' cameras (cameras ascending, slots ascending) whose point is no m1 contribute it -- a point seen
+ *             by k cameras k times --, ordered by numVisCam (its references at f2 over ALL cameras) descending, STABLY (sortWithInd is
+ *             un-vendored: stable is this library's definition); each gives the track of its references at f2 in the groups' cameras;
+ *             tracks with a view are appended until there are 20 x nMergedTracks (getUnMergedFeatureTracks).
+ *   f1 views  behind every view its chain is walked (the run [first, frame] on the slot, then the camera's linked segments); a node at
+ *             frame f1 becomes a view of the track, behind the f2 views, in view order (getCorresFeatPtsInPrevSelfKeyPoses).  A walk ends at
+ *             the first run that is wholly older than f1, at a segment outside the pool and after as many hops as the pool has segments.
+ *   problem   tracks of more than one view, in REVERSE order; per point the views in order, one whose (frame, camera) the point already has
+ *             dropped (CS_MERGE_VIEW_DETACHED / _PREV_DETACHED in the merge list: `fp->mpt = 0`, :631-634); the camera index is the pose
+ *             order of cs_merge_first_constrain.  Ks / Rs / Ts [nPose], pts [P][3], obsPtr [P + 1], obsCam, obsXY in cs_ba_upload's layout,
+ *             pointMap [P] the map index of each point.
+ * Capacities follow from maxMatches (points <= 21 x maxMatches, measurements <= 32 per point): there is no overflow path.
+ * Refused with CS_ERR_INVALID before any launch: f2 is not the history's newest frame, f1 >= f2 or f1 has left the store, nMatches >
+ * maxMatches, nMap > maxMap, camera ids outside the rig.  A record d_groups that does not hold the two groups gives CS_MERGE_BAD_GROUPS.
+ * cams [nCams] (host array of device pointers): xy / state / slot2map of the CURRENT key frame (the history's newest frame) and K; R / t are
+ * not read (the poses are the history's).  d_matches [nMatches][2].  One launch of one workgroup; no host wait. */
+enum { CS_MERGE_OK = 1, CS_MERGE_REJECT = 0, CS_MERGE_FEW = -1, CS_MERGE_BAD_GROUPS = -2 };
+enum { CS_MERGE_VIEW_FROM_M2 = 1, CS_MERGE_VIEW_DETACHED = 2, CS_MERGE_VIEW_PREV = 4, CS_MERGE_VIEW_PREV_DETACHED = 8 };
+typedef struct {
+    int verdict;                      /* CS_MERGE_* */
+    int nPose, P, nObs;               /* the problem (0 unless CS_MERGE_OK) */
+    int nMergedTracks, nUnmerged, nPrevViews, skippedMatches;
+    int nMergeViews;                  /* entries of the merge list */
+    int f1, f2, nCamIds;
+    int camIds[16];                   /* getCamIdsInBothGroups */
+    int nInfo, reserved;              /* cs_merge_info_dev: entries of the MergeInfo list */
+    double avgErr;
+} cs_merge_constraints_header;
+typedef struct {
+    int track, cam, slot;             /* the view: a feature of the current key frame */
+    int point;                        /* the point it belongs to after the merge (the track's m1) */
+    int from;                         /* the point whose reference it was (m1 or m2) */
+    int flags;                        /* CS_MERGE_VIEW_* */
+    int prevSlot;                     /* the slot of its chain's node at f1, or -1 */
+    int reserved;
+} cs_merge_view;
+typedef struct {
+    const cs_merge_constraints_header* header;
+    const cs_merge_view* views;       /* [32 * maxMatches] */
+    const double *Ks, *Rs, *Ts;       /* [32][9], [32][9], [32][3] */
+    const double* pts;                /* [maxPoints][3] */
+    const int* pointMap;              /* [maxPoints] */
+    const int* obsPtr;                /* [maxPoints + 1] */
+    const int* obsCam;                /* [maxObs] */
+    const double* obsXY;              /* [maxObs][2] */
+    const cs_merge_info* info;        /* [48] */
+    const unsigned char* infoValid;   /* [48] */
+    const double *infoR, *infoT;      /* [48][9], [48][3]: what cs_merge_apply_run_dev takes as d_infoR / d_infoT */
+    int maxPoints, maxObs, maxViews, maxInfo;
+    const double *solvedRs, *solvedTs;   /* [32][9], [32][3]: the poses behind cs_merge_constraints_solve */
+    const double* solvedPts;          /* [maxPoints][3]: the solved coordinates of the problem's points (pointMap names their map rows) */
+    const int* outlier;               /* [maxObs]: the second solve's outlier flags */
+} cs_merge_constraints_buffers;
+typedef struct cs_merge_constraints cs_merge_constraints;
+/* nCams 1..16, N >= 1 slots per camera, maxMatches >= 1, maxMap >= 1 map rows.  NULL on failure (cs_last_error). */
+cs_merge_constraints* cs_merge_constraints_create(int device, int nCams, int N, int maxMatches, int maxMap);
+void cs_merge_constraints_destroy(cs_merge_constraints* mc);
+int cs_merge_constraints_assemble_dev(cs_merge_constraints* mc, const cs_track_history* h, void* hip_stream, const cs_merge_cam* cams,
+                                      const cs_feat_ref* d_featRef, int nMap, const double* d_mapPts, const cs_camera_groups* d_groups, int gId1,
+                                      int gId2, int maxiCam, int maxjCam, int f1, int f2, const int* d_matches, int nMatches);
+/* the same with the matches in HOST memory (h_matches [nMatches][2]): copied into a table of the handle's own on hip_stream, then the launch */
+int cs_merge_constraints_assemble(cs_merge_constraints* mc, const cs_track_history* h, void* hip_stream, const cs_merge_cam* cams,
+                                  const cs_feat_ref* d_featRef, int nMap, const double* d_mapPts, const cs_camera_groups* d_groups, int gId1,
+                                  int gId2, int maxiCam, int maxjCam, int f1, int f2, const int* h_matches, int nMatches);
+/* The MergeInfo list of :681-722 from poses d_Rs / d_Ts [nPose] in the assembled pose order (the handle's own Rs / Ts: the unsolved poses;
+ * a caller's buffers: the solved ones), one small launch behind the assembly on the same stream: groups[gId1].camIds[0] against every
+ * camera of gId2, groups[gId2].camIds[0] against cameras 1.. of gId1, then per camera of camIds (f2, c) -> (f1, c) with group ids -1; R, t
+ * by getRigidTransFromTo.  E is not formed.  A verdict other than CS_MERGE_OK gives nInfo = 0 and writes nothing else. */
+int cs_merge_info_dev(cs_merge_constraints* mc, void* hip_stream, const cs_camera_groups* d_groups, int gId1, int gId2, const double* d_Rs,
+                      const double* d_Ts);
+/* The two solves of :646-647 on the assembled problem -- bundleAdjustRobust(1, ..., 1, ..., 800, 1, 100), then (..., 30, 5, 30) started from
+ * the first one's result -- as two runs of the existing robust BA: the problem is read back (the header first: the stage's one host wait
+ * before the solve; the step in front of it is host code anyway) and handed to cs_ba_robust_h on a workspace of the handle's own.  Waits.
+ * A verdict other than CS_MERGE_OK: CS_OK, nothing solved.  A failed solve returns its error and touches nothing.  On success the second
+ * solve's poses, points and outlier flags are in solvedRs / solvedTs / solvedPts / outlier; applying the points to the map is the caller's. */
+int cs_merge_constraints_solve(cs_merge_constraints* mc, void* hip_stream);
+/* host copies of solve `which` (0 / 1) of the last successful cs_merge_constraints_solve; any output may be NULL */
+struct cs_ba_stats;
+int cs_merge_constraints_solution(const cs_merge_constraints* mc, int which, double* Rs, double* Ts, double* pts, int* outlier,
+                                  struct cs_ba_stats* stats);
+/* cs_merge_info_dev on the solved poses; nInfo = 0 and nothing else written after a rejected verdict, a failed solve or no solve at all */
+int cs_merge_constraints_info_dev(cs_merge_constraints* mc, void* hip_stream, const cs_camera_groups* d_groups, int gId1, int gId2);
+/* the device buffers (valid for the handle's life) */
+int cs_merge_constraints_buffers_get(const cs_merge_constraints* mc, cs_merge_constraints_buffers* out);
+/* the header copied to the host; waits for hip_stream */
+int cs_merge_constraints_header_get(cs_merge_constraints* mc, void* hip_stream, cs_merge_constraints_header* h_out);
+/* bytes of one of the handle's device buffers (d_src inside cs_merge_constraints_buffers_get's ranges) to the host; waits for hip_stream */
+int cs_merge_constraints_download(cs_merge_constraints* mc, void* hip_stream, const void* d_src, void* h_dst, size_t bytes);
+
 /* CoSLAM::mapPointsClassify (src/app/SL_CoSLAM.cpp:418-520) over the references: from the next call on cs_map_points_classify_dev and
  * cs_pose_update_classify_frame_dev read d_featRef ([nMap][nCams], the table cs_feat_ref_advance_dev keeps: as the END of the previous
  * frame left it, or already at this frame) next to d_pointFeat (this frame's features): a camera that lost the point still gives
