@@ -4,7 +4,8 @@
 // with its helpers getCamIdsInBothGroups (:489-511), getCorresFeatPtsAndMapPts (:762-811), checkMergeMapPoints (:425-467), mergeMapPoints
 // (:468-488, emitted as a list, not applied), getUnMergedFeatureTracks (:812-882), getCorresFeatPtsInPrevSelfKeyPoses (:726-761) and
 // getRigidTransFromToWithEMat (:1211-1219).  Everything it reads lives on the device: the current key frame's slot tables, the feature
-// references with the history's linked segments, the history's pixels and poses, the map.  It writes only the handle's own buffers.
+// references with the history's linked segments, the history's pixels and poses, the map.  It writes only the handle's own buffers;
+// k_merge_apply_map is the one kernel here that writes the live tables: the merge list and the solved points applied.
 //
 // It runs once per merge, so it is ONE workgroup of 1024 lanes that walks the reference's steps in order, a barrier between them; every
 // output position comes from a scan (matches -> tracks -> views; tracks -> points -> measurements, in reverse track order) or from ballots
@@ -26,6 +27,10 @@ struct cs_merge_constraints {
     int *slotView, *candKey, *candRank, *candPt, *unm;
     unsigned* isM1;
     int* matches;   // [maxMatches][2]: cs_merge_constraints_assemble's copy of a host list
+    // cs_merge_constraints_apply_map_dev: winner tables (all -1 between calls) and the rows gathered from the pre-call table
+    int *winSlot, *winRow, *winPt;   // [nCams][N], [maxMap][nCams], [maxMap]
+    int4* gRef;                      // [maxViews]
+    unsigned char* gStat;            // [maxViews]
     std::vector<int> hMatches;
     // the two solves (:646-647): the problem on the host, the existing robust BA's workspace, both results
     cs_ba* ba;
@@ -442,6 +447,135 @@ __global__ __launch_bounds__(64) void k_merge_info(MiArgs A) {
     for (int r = 0; r < 3; ++r) A.infoT[3 * i + r] = t2[r] - (R[3 * r] * t1[0] + R[3 * r + 1] * t1[1] + R[3 * r + 2] * t1[2]);
 }
 
+struct MmArgs {
+    int nCams, N, nMap, maxViews, maxPoints, applyPts;
+    const cs_merge_constraints_header* hdr;
+    const cs_merge_view* views;
+    const int* pointMap;
+    const double* solvedPts;
+    int* slot2map[MC_MAX_CAMS];
+    int* pointFeat;             // [nMap][nCams] or NULL
+    int4* featRef;              // [nMap][nCams] {slot, frame, first, seg}
+    unsigned char* refStatic;   // [nMap][nCams] or NULL
+    double* mapPts;             // [nMap][3] (read only when applyPts)
+    int* counts;                // [6] or NULL
+    int *winSlot, *winRow, *winPt;
+    int4* gRef;
+    unsigned char* gStat;
+};
+
+__device__ __forceinline__ bool mm_view_ok(const MmArgs& A, const cs_merge_view& e) {
+    return e.cam >= 0 && e.cam < A.nCams && e.slot >= 0 && e.slot < A.N && e.point >= 0 && e.point < A.nMap && e.from >= 0 && e.from < A.nMap;
+}
+
+__device__ __forceinline__ int mm_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // (written by atomics)
+
+// mergeMapPoints (:468-488), the duplicate marks of :631-634 and the solved coordinates (:665-669) on the live tables, DESIGN 3.23.  One
+// workgroup, four passes with a barrier between them: (1) every source row is gathered from the table as it stands and every entry bids for
+// its slot (c, s), its row (m1, c) and its map row with its INDEX (atomicMax: "the last one wins" as an integer maximum); (2) the winners
+// write; (3) the detached features, whichever entry came last; (4) the winner tables go back to -1 at the entries the lists named.
+__global__ __launch_bounds__(MC_T) void k_merge_apply_map(MmArgs A) {
+    __shared__ int s_n[3], s_cnt[6];
+    const int tid = threadIdx.x, nC = A.nCams, N = A.N;
+    if (tid == 0) {
+        const int nV = A.hdr->nMergeViews, P = A.hdr->P;
+        s_n[0] = A.hdr->verdict == CS_MERGE_OK ? 1 : 0;
+        s_n[1] = nV < 0 ? 0 : nV > A.maxViews ? A.maxViews : nV;
+        s_n[2] = !A.applyPts || P < 0 ? 0 : P > A.maxPoints ? A.maxPoints : P;
+    }
+    if (tid < 6) s_cnt[tid] = 0;
+    __syncthreads();
+    if (!s_n[0]) return;   // a verdict other than CS_MERGE_OK: nothing written, nothing counted
+    const int nV = s_n[1], P = s_n[2];
+    int applied = 0, moved = 0, detached = 0, prevMarked = 0, written = 0, lost = 0;
+
+    // ---- 1. gather and bid
+    for (int v = tid; v < nV; v += MC_T) {
+        const cs_merge_view e = A.views[v];
+        if (!mm_view_ok(A, e)) {
+            ++lost;
+            continue;
+        }
+        ++applied;
+        const size_t src = (size_t)e.from * nC + e.cam;
+        A.gRef[v] = A.featRef[src];
+        A.gStat[v] = A.refStatic ? A.refStatic[src] : 0;
+        atomicMax(&A.winSlot[e.cam * N + e.slot], v);
+        atomicMax(&A.winRow[(size_t)e.point * nC + e.cam], v);
+    }
+    for (int i = tid; i < P; i += MC_T) {
+        const int m = A.pointMap[i];
+        if (m < 0 || m >= A.nMap) {
+            ++lost;
+            continue;
+        }
+        atomicMax(&A.winPt[m], i);
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    // ---- 2. the winners write: slot2map[c][s] = m1; m1's reference in c = the gathered row of `from`
+    for (int v = tid; v < nV; v += MC_T) {
+        const cs_merge_view e = A.views[v];
+        if (!mm_view_ok(A, e)) continue;
+        const bool winS = mm_load(&A.winSlot[e.cam * N + e.slot]) == v, winR = mm_load(&A.winRow[(size_t)e.point * nC + e.cam]) == v;
+        if (winS) A.slot2map[e.cam][e.slot] = e.point;
+        if (winR) {
+            const size_t dst = (size_t)e.point * nC + e.cam;
+            A.featRef[dst] = A.gRef[v];
+            if (A.refStatic) A.refStatic[dst] = A.gStat[v];
+            if (A.pointFeat) A.pointFeat[dst] = e.slot;
+            moved += e.from != e.point ? 1 : 0;
+        }
+        lost += winS && winR ? 0 : 1;
+    }
+    for (int i = tid; i < P; i += MC_T) {
+        const int m = A.pointMap[i];
+        if (m < 0 || m >= A.nMap) continue;
+        if (mm_load(&A.winPt[m]) == i) {
+            for (int q = 0; q < 3; ++q) A.mapPts[3 * (size_t)m + q] = A.solvedPts[3 * (size_t)i + q];
+            ++written;
+        } else
+            ++lost;
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    // ---- 3. `fp->mpt = 0`: a detached feature loses its point whatever entry named its slot last; the first to take the slot's winner
+    // entry counts the feature (one per slot, whoever it is)
+    for (int v = tid; v < nV; v += MC_T) {
+        const cs_merge_view e = A.views[v];
+        if (!mm_view_ok(A, e)) continue;
+        if (e.flags & CS_MERGE_VIEW_DETACHED) {
+            detached += atomicExch(&A.winSlot[e.cam * N + e.slot], -2) >= 0 ? 1 : 0;
+            A.slot2map[e.cam][e.slot] = -1;
+        }
+        prevMarked += e.flags & CS_MERGE_VIEW_PREV_DETACHED ? 1 : 0;   // a node of a past frame has no owner entry here: counted only
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    // ---- 4. the winner tables as they were
+    for (int v = tid; v < nV; v += MC_T) {
+        const cs_merge_view e = A.views[v];
+        if (!mm_view_ok(A, e)) continue;
+        A.winSlot[e.cam * N + e.slot] = -1;
+        A.winRow[(size_t)e.point * nC + e.cam] = -1;
+    }
+    for (int i = tid; i < P; i += MC_T) {
+        const int m = A.pointMap[i];
+        if (m >= 0 && m < A.nMap) A.winPt[m] = -1;
+    }
+    if (applied) atomicAdd(&s_cnt[0], applied);
+    if (moved) atomicAdd(&s_cnt[1], moved);
+    if (detached) atomicAdd(&s_cnt[2], detached);
+    if (prevMarked) atomicAdd(&s_cnt[3], prevMarked);
+    if (written) atomicAdd(&s_cnt[4], written);
+    if (lost) atomicAdd(&s_cnt[5], lost);
+    __syncthreads();
+    if (tid < 6 && A.counts) A.counts[tid] += s_cnt[tid];
+}
+
 size_t mc_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -458,7 +592,8 @@ extern "C" cs_merge_constraints* cs_merge_constraints_create(int device, int nCa
     const size_t sizes[] = {sizeof(cs_merge_constraints_header), nV * sizeof(cs_merge_view), 32 * 9 * 8, 32 * 9 * 8, 32 * 3 * 8, nP * 24, nP * 4, (nP + 1) * 4,
                             nO * 4, nO * 16, MC_MAX_INFO * sizeof(cs_merge_info), MC_MAX_INFO, MC_MAX_INFO * 72, MC_MAX_INFO * 24,
                             (size_t)maxMatches * sizeof(int4), nS * 4, nS * 4, nS * 4, nS * 4, 20 * (size_t)maxMatches * 4, ((size_t)maxMap + 31) / 32 * 4,
-                            32 * 9 * 8, 32 * 3 * 8, nP * 24, nO * 4, (size_t)maxMatches * 8};
+                            32 * 9 * 8, 32 * 3 * 8, nP * 24, nO * 4, (size_t)maxMatches * 8,
+                            (size_t)nCams * N * 4, (size_t)maxMap * nCams * 4, (size_t)maxMap * 4, nV * sizeof(int4), nV};
     size_t off[sizeof(sizes) / sizeof(sizes[0]) + 1] = {0};
     for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) off[i + 1] = off[i] + mc_align(sizes[i]);
     const size_t total = off[sizeof(sizes) / sizeof(sizes[0])];
@@ -479,6 +614,14 @@ extern "C" cs_merge_constraints* cs_merge_constraints_create(int device, int nCa
     mc->candPt = (int*)(b + off[18]), mc->unm = (int*)(b + off[19]), mc->isM1 = (unsigned*)(b + off[20]);
     B.solvedRs = (double*)(b + off[21]), B.solvedTs = (double*)(b + off[22]), B.solvedPts = (double*)(b + off[23]), B.outlier = (int*)(b + off[24]);
     mc->matches = (int*)(b + off[25]);
+    mc->winSlot = (int*)(b + off[26]), mc->winRow = (int*)(b + off[27]), mc->winPt = (int*)(b + off[28]);
+    mc->gRef = (int4*)(b + off[29]), mc->gStat = (unsigned char*)(b + off[30]);
+    if (hipMemset(mc->winSlot, 0xFF, off[29] - off[26]) != hipSuccess) {   // the three winner tables: -1 once, every call restores what it named
+        cs_set_error("cs_merge_constraints_create: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipFree(mc->base);
+        delete mc;
+        return nullptr;
+    }
     mc->ba = nullptr, mc->solved = 0, mc->sC = mc->sP = mc->sObs = 0;
     return mc;
 }
@@ -695,5 +838,38 @@ extern "C" int cs_merge_constraints_info_dev(cs_merge_constraints* mc, void* hip
     if (mc->solved == 1) return cs_merge_info_dev(mc, hip_stream, d_groups, gId1, gId2, mc->b.solvedRs, mc->b.solvedTs);
     CS_HIP(hipSetDevice(mc->device));
     CS_HIP(hipMemsetAsync((char*)mc->b.header + offsetof(cs_merge_constraints_header, nInfo), 0, sizeof(int), (hipStream_t)hip_stream));
+    return CS_OK;
+}
+
+// the merge list and the solved coordinates onto the live map tables: one launch of one workgroup, no host wait
+extern "C" int cs_merge_constraints_apply_map_dev(cs_merge_constraints* mc, void* hip_stream, int* const* d_slot2map, int* d_pointFeat,
+                                                  cs_feat_ref* d_featRef, unsigned char* d_refStatic, int nMap, double* d_mapPts, int applyPoints,
+                                                  int* d_counts) {
+    const char* who = "cs_merge_constraints_apply_map_dev";
+    if (!mc || !d_slot2map || !d_featRef || nMap < 0) {
+        cs_set_error("%s: null handle, slot2map list or feature references (nMap %d)", who, nMap);
+        return CS_ERR_INVALID;
+    }
+    if (nMap > mc->maxMap) {
+        cs_set_error("%s: %d map rows, the handle was created for %d", who, nMap, mc->maxMap);
+        return CS_ERR_INVALID;
+    }
+    MmArgs A;
+    memset(&A, 0, sizeof(A));
+    for (int c = 0; c < mc->nCams; ++c) {
+        if (!d_slot2map[c]) {
+            cs_set_error("%s: null slot2map of camera %d", who, c);
+            return CS_ERR_INVALID;
+        }
+        A.slot2map[c] = d_slot2map[c];
+    }
+    A.nCams = mc->nCams, A.N = mc->N, A.nMap = nMap, A.maxViews = mc->maxViews, A.maxPoints = mc->maxPoints;
+    A.applyPts = applyPoints && d_mapPts && mc->solved == 1 ? 1 : 0;   // the reference merges before it solves: the list goes in either way
+    A.hdr = mc->b.header, A.views = mc->b.views, A.pointMap = mc->b.pointMap, A.solvedPts = mc->b.solvedPts;
+    A.pointFeat = d_pointFeat, A.featRef = (int4*)d_featRef, A.refStatic = d_refStatic, A.mapPts = d_mapPts, A.counts = d_counts;
+    A.winSlot = mc->winSlot, A.winRow = mc->winRow, A.winPt = mc->winPt, A.gRef = mc->gRef, A.gStat = mc->gStat;
+    CS_HIP(hipSetDevice(mc->device));
+    hipLaunchKernelGGL(k_merge_apply_map, dim3(1), dim3(MC_T), 0, (hipStream_t)hip_stream, A);
+    CS_CHECK_LAUNCH();
     return CS_OK;
 }

@@ -422,6 +422,23 @@ class MergeConstraints:
         check(self._L.cs_merge_constraints_info_dev(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(d_groups), int(gId1),
                                                     int(gId2)), "cs_merge_constraints_info_dev")
 
+    def apply_map(self, d_slot2map, d_pointFeat, d_featRef, d_refStatic, nMap, d_mapPts=None, apply_points=True, d_counts=None, stream_ptr=None):
+        """cs_merge_constraints_apply_map_dev: the merge list (mergeMapPoints, the duplicate marks) and -- behind a successful solve() --
+        the solved coordinates onto the live tables.  d_slot2map: one device pointer per camera (or a merge_cams() array / list of dicts
+        with a slot2map field); d_pointFeat, d_refStatic, d_mapPts, d_counts ([6] int32) may be None.  The verdict is read on the device;
+        enqueues only."""
+        vp = C.c_void_p
+        if isinstance(d_slot2map, C.Array) and d_slot2map._type_ is MergeCam:
+            ptrs = [d_slot2map[c].slot2map for c in range(len(d_slot2map))]
+        else:
+            ptrs = [p.get("slot2map") if isinstance(p, dict) else p for p in d_slot2map]
+        if len(ptrs) != self.n_cams:
+            raise ValueError(f"apply_map: {len(ptrs)} slot2map pointers, the handle has {self.n_cams} cameras")
+        arr = (vp * self.n_cams)(*[vp(int(p)) if p else None for p in ptrs])
+        check(self._L.cs_merge_constraints_apply_map_dev(vp(self._m), vp(self._stream(stream_ptr)), arr, vp(d_pointFeat), vp(d_featRef),
+                                                         vp(d_refStatic), int(nMap), vp(d_mapPts), 1 if apply_points else 0, vp(d_counts)),
+              "cs_merge_constraints_apply_map_dev")
+
     def header(self, stream_ptr=None):
         """the header on the host; waits for the stream"""
         h = MergeConstraintsHeader()
@@ -470,6 +487,121 @@ class MergeConstraints:
         if self._m:
             self._L.cs_merge_constraints_destroy(C.c_void_p(self._m))
             self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MERGE_HOLD_OFF = 130   # CoSLAM::mergeCamGroups: `curFrame < m_lastFrmGroupMerge + 130` (reference src/app/SL_CoSLAM.cpp:1381)
+
+
+class MergeCamGroups:
+    """CoSLAM::mergeCamGroups (reference src/app/SL_CoSLAM.cpp:1375-1446) behind its matcher, as one call: from the chosen camera pair with
+    its feature matches to the merged history, map, tables and groups.  It owns a MergeConstraints handle (and, per run, a
+    MergeApply handle, whose graphs depend on the key frames) and keeps last_merge_frame for the reference's hold-off of 130 frames.
+    The closing currentMapPointsRegister(20.0, true) of :1439 is cs_register_decide_merge_dev and stays the caller's."""
+
+    def __init__(self, n_cams, N, max_matches, max_map, device=0, last_merge_frame=-(1 << 30)):
+        self.n_cams, self.N, self.device = int(n_cams), int(N), int(device)
+        self.mc = MergeConstraints(n_cams, N, max_matches, max_map, device=device)
+        self.ma = None
+        self.last_merge_frame = int(last_merge_frame)
+        self._keep = None
+
+    def run(self, history, tables, groups, key_frames, self_motion, key_groups, pair, matches, pixelErrVar, last_release_frame=None,
+            n_max_keyfrm=100, stream_ptr=None):
+        """history: the TrackHistory, its newest frame the current key frame.  tables: dict of DEVICE pointers -- cams (per camera a dict
+        xy, state, slot2map, K, iK of the current key frame), featRef, pointFeat (or None), refStatic (or None), nMap, mapPts, mapCov,
+        mapCount (or None), firstFrame, lastFrame, mapFlags.  groups: the current record (a CameraGroups or a list of camera-id lists).
+        key_frames: frame numbers oldest first, the current key frame last; self_motion [nKey][nCams]; key_groups: per key frame its record
+        (what merge_keygraph_plan takes).  pair: (gId1, gId2, maxiCam, maxjCam); matches: int32 [K][2] slot pairs (host or device tensor).
+
+        Enqueues merge_first_constrain, assemble, solve, info_solved, apply_map, merge_keygraph_plan, MergeApply.run_dev on the handle's
+        d_infoR / d_infoT, MergeApply.recompute behind its guard, merge_matched_groups.  The merge list is applied only behind a verdict
+        of MERGE_OK and two successful solves: otherwise history, map and tables are untouched, the hold-off is not armed and `status`
+        names the cause ("held_off", "rejected", "solve_failed").  "pose_failed": the pose graphs failed numerically behind the applied
+        list -- their guard kept the history and the re-triangulation from being written.
+
+        -> dict(status, merged, verdict, header (dict of the counts), apply_counts [6], recompute_counts [4], solver (BAStats of both solves),
+        groups, group_id, merged_gid, record)"""
+        import numpy as np
+        import torch
+
+        from ._lib import CoslamHipError
+
+        frames = [int(f) for f in key_frames]
+        cur = frames[-1]
+        rep = dict(status="held_off", merged=False, verdict=None, header=None, apply_counts=[0] * 6, recompute_counts=[0] * 4, solver=None,
+                   groups=None, group_id=None, merged_gid=-1, record=None, error=None)
+        if cur < self.last_merge_frame + MERGE_HOLD_OFF:
+            return rep
+        s = torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        dev = torch.device("cuda", self.device)
+        gId1, gId2, iCam, jCam = (int(v) for v in pair)
+        rec = _camera_groups_record(groups)
+        glist = rec.groups()
+        ids = sorted(set(glist[gId1]) | set(glist[gId2]))
+        d_groups = torch.from_numpy(np.frombuffer(bytes(rec), np.uint8).copy()).to(dev)
+        d_counts = torch.zeros(10, dtype=torch.int32, device=dev)
+        self._keep = (d_groups, d_counts)
+        T, mc = tables, self.mc
+        k, _order = merge_first_constrain(frames, self_motion, ids)
+        mc.assemble(history, [dict(xy=c["xy"], state=c["state"], slot2map=c["slot2map"], K=c["K"]) for c in T["cams"]], T["featRef"], T["nMap"],
+                    T["mapPts"], d_groups.data_ptr(), gId1, gId2, iCam, jCam, frames[k], cur, matches, stream_ptr=s)
+        try:
+            mc.solve(stream_ptr=s)
+        except CoslamHipError as e:
+            rep.update(status="solve_failed", error=str(e))
+        h = mc.header(stream_ptr=s)
+        rep["verdict"] = int(h.verdict)
+        rep["header"] = {n: int(getattr(h, n)) for n in ("nPose", "P", "nObs", "nMergedTracks", "nUnmerged", "nPrevViews", "skippedMatches",
+                                                         "nMergeViews", "f1", "f2", "nCamIds")}
+        rep["header"]["avgErr"] = float(h.avgErr)
+        if rep["status"] == "solve_failed":
+            return rep
+        if h.verdict != MERGE_OK:
+            rep["status"] = "rejected"
+            return rep
+        rep["solver"] = [mc.solution(w)["stats"] for w in (0, 1)]
+        mc.info_solved(d_groups.data_ptr(), gId1, gId2, stream_ptr=s)
+        ints, _R, _t = mc.infos(stream_ptr=s)
+        if len(ints) == 0 or not (ints[:, 6] == 1).all():
+            raise CoslamHipError("MergeCamGroups.run: the MergeInfo list is empty or holds an entry outside the pose order")
+        mc.apply_map([c["slot2map"] for c in T["cams"]], T.get("pointFeat"), T["featRef"], T.get("refStatic"), T["nMap"], T["mapPts"], True,
+                     d_counts.data_ptr(), stream_ptr=s)
+        plan = merge_keygraph_plan(frames, key_groups, ids, k, iCam, jCam, ints[:, [0, 1, 3, 4]], n_max_keyfrm=n_max_keyfrm)
+        if self.ma is not None:
+            self.ma.close()
+        self.ma = ma = MergeApply(plan, frames, self.n_cams, device=self.device)
+        ma.run_dev(history, mc.buf.infoR, mc.buf.infoT, stream_ptr=s)
+        fixed_frame = int(ma.key_frames[0])
+        f_start = fixed_frame if last_release_frame is None else max(fixed_frame, int(last_release_frame))
+        ma.recompute(history, [dict(K=c["K"], iK=c["iK"]) for c in T["cams"]], T["featRef"], T["nMap"], T.get("mapCount"), T["firstFrame"],
+                     T["lastFrame"], T["mapFlags"], T["mapPts"], T["mapCov"], f_start, pixelErrVar, True, d_counts[6:].data_ptr(), stream_ptr=s)
+        try:
+            ma.status(stream_ptr=s)
+        except CoslamHipError as e:
+            rep.update(status="pose_failed", error=str(e))
+        cnt = d_counts.cpu().tolist()
+        rep["apply_counts"], rep["recompute_counts"] = cnt[:6], cnt[6:]
+        if rep["status"] == "pose_failed":
+            return rep
+        valid = ints[ints[:, 2] >= 0]
+        got = merge_matched_groups(rec, valid[:, 2], valid[:, 5], iCam, jCam)
+        rep.update(status="merged", merged=True, groups=got["groups"], group_id=got["group_id"], merged_gid=got["merged_gid"], record=got["record"])
+        self.last_merge_frame = cur
+        return rep
+
+    def close(self):
+        if self.ma is not None:
+            self.ma.close()
+            self.ma = None
+        if self.mc is not None:
+            self.mc.close()
+            self.mc = None
 
     def __del__(self):
         try:

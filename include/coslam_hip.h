@@ -1085,7 +1085,7 @@ int cs_merge_first_constrain(int nKeyFrames, const int* frames, const unsigned c
  *   verdict   the pixel distance of m1 projected with (K, R, t) of each view's camera at f2 from the view's pixel; the mean of the three
  *             largest over all views of all tracks > 500: CS_MERGE_REJECT (checkMergeMapPoints).  No track, or fewer than three views:
  *             CS_MERGE_FEW (the reference asserts / reads past the end).  Otherwise CS_MERGE_OK.  Unless OK nothing else is produced.
- *   views     the merge list (mergeMapPoints, EMITTED, not applied): one cs_merge_view per view of a merged track in track and view order.
+ *   views     the merge list (mergeMapPoints, EMITTED; cs_merge_constraints_apply_map_dev applies it): one cs_merge_view per view of a merged track in track and view order.
  *             The later steps see the state as if it were applied: a feature's point is the m1 of the last track that holds it.
  *   unmerged  the features of the groups' cameras (cameras ascending, slots ascending) whose point is no m1 contribute it -- a point seen
  *             by k cameras k times --, ordered by numVisCam (its references at f2 over ALL cameras) descending, STABLY (sortWithInd is
@@ -1161,7 +1161,7 @@ int cs_merge_info_dev(cs_merge_constraints* mc, void* hip_stream, const cs_camer
  * the first one's result -- as two runs of the existing robust BA: the problem is read back (the header first: the stage's one host wait
  * before the solve; the step in front of it is host code anyway) and handed to cs_ba_robust_h on a workspace of the handle's own.  Waits.
  * A verdict other than CS_MERGE_OK: CS_OK, nothing solved.  A failed solve returns its error and touches nothing.  On success the second
- * solve's poses, points and outlier flags are in solvedRs / solvedTs / solvedPts / outlier; applying the points to the map is the caller's. */
+ * solve's poses, points and outlier flags are in solvedRs / solvedTs / solvedPts / outlier; cs_merge_constraints_apply_map_dev writes the points into the map. */
 int cs_merge_constraints_solve(cs_merge_constraints* mc, void* hip_stream);
 /* host copies of solve `which` (0 / 1) of the last successful cs_merge_constraints_solve; any output may be NULL */
 struct cs_ba_stats;
@@ -1175,6 +1175,30 @@ int cs_merge_constraints_buffers_get(const cs_merge_constraints* mc, cs_merge_co
 int cs_merge_constraints_header_get(cs_merge_constraints* mc, void* hip_stream, cs_merge_constraints_header* h_out);
 /* bytes of one of the handle's device buffers (d_src inside cs_merge_constraints_buffers_get's ranges) to the host; waits for hip_stream */
 int cs_merge_constraints_download(cs_merge_constraints* mc, void* hip_stream, const void* d_src, void* h_dst, size_t bytes);
+/* The merge list and the solved coordinates applied to the LIVE map tables (mergeMapPoints :468-488, the duplicate marks of :631-634, the
+ * write of :665-669): one launch of one workgroup behind the assembly / the solve on hip_stream, no host wait.  It reads the
+ * handle's header, views, pointMap and solvedPts; the verdict is read ON THE DEVICE: unless CS_MERGE_OK nothing is written or counted.
+ *   merge list  for view i = {cam c, slot s, point m1, from}: d_slot2map[c][s] = m1; d_featRef[m1][c] = d_featRef[from][c] AS IT STOOD BEFORE
+ *               THE CALL (all four fields: the chain hangs on the reference, so the run and the linked segments move with it);
+ *               d_refStatic[m1][c] = d_refStatic[from][c] likewise; d_pointFeat[m1][c] = s.  from's own row is not cleared (the reference
+ *               leaves m2->pFeatures as it was).  Every source row is gathered before any row is written, so a `from` that is another
+ *               track's m1 gives its old row.  Several views of one (m1, c) or one (c, s): the HIGHEST view index wins (an integer maximum
+ *               over index tables of the handle; no result depends on scheduling).
+ *   detached    a view with CS_MERGE_VIEW_DETACHED sets d_slot2map[c][s] = -1, whichever view named the slot last; d_pointFeat / d_featRef
+ *               keep the entry (the next cs_feat_ref_advance_dev clears a reference whose slot lives on without the point).
+ *               CS_MERGE_VIEW_PREV_DETACHED marks a node of a past frame; there is no per-node owner here: counted only.
+ *   points      when applyPoints != 0, d_mapPts is given and the handle holds a successful cs_merge_constraints_solve since its last
+ *               assembly: d_mapPts[pointMap[i]] = solvedPts[i], i < P, the HIGHEST i wins where pointMap names a row more than once.
+ *               Otherwise d_mapPts is not touched (the list is applied all the same).  Covariances are never touched.
+ *   d_counts    [6] or NULL, accumulated, never cleared here: views applied, references moved (from != point), current features
+ *               detached (per slot), f1 nodes marked (counted only), map rows whose coordinates were written, list entries that lost (a
+ *               view whose slot or row a later view took, a pointMap entry a later one overwrote, an entry skipped as out of range).
+ * A view or pointMap entry whose camera, slot or row lies outside the tables (nCams, N of the handle; nMap) is skipped, never a read or
+ * write outside a table.  d_slot2map: HOST array of nCams device pointers, N ints each; d_pointFeat, d_refStatic, d_mapPts, d_counts may
+ * be NULL.  CS_ERR_INVALID before any launch: a null handle, list or d_featRef, a null d_slot2map[c], nMap > the handle's maxMap. */
+int cs_merge_constraints_apply_map_dev(cs_merge_constraints* mc, void* hip_stream, int* const* d_slot2map, int* d_pointFeat,
+                                       cs_feat_ref* d_featRef, unsigned char* d_refStatic, int nMap, double* d_mapPts, int applyPoints,
+                                       int* d_counts);
 
 /* CoSLAM::mapPointsClassify (src/app/SL_CoSLAM.cpp:418-520) over the references: from the next call on cs_map_points_classify_dev and
  * cs_pose_update_classify_frame_dev read d_featRef ([nMap][nCams], the table cs_feat_ref_advance_dev keeps: as the END of the previous

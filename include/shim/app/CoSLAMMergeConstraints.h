@@ -14,8 +14,12 @@
 //
 // featMatches is the reference's Matching (num, operator[] -> idx1 / idx2): indices into m_featPoints[maxiCam] / [maxjCam]; they are turned
 // into slots here.  Header-only and synchronous (the solves wait).  false: checkMergeMapPoints said no, or there was nothing to judge; a
-// failed solve throws and leaves m_nMergeInfo = 0.  Applying the merge list (buffers.views) and the solved points (buffers.solvedPts,
-// pointMap) to the map stays with the caller.
+// failed solve throws and leaves m_nMergeInfo = 0.
+//
+//     merger.mergeMapPoints(d_pointFeat, d_featRef, d_refStatic, d_mapPts, true, d_counts);   // behind a true genMergeInfoVer2
+//
+// applies the merge list (mergeMapPoints :468-488, the duplicate marks of :631-634) and the solved points (:665-669) to the LIVE tables:
+// cs_merge_constraints_apply_map_dev over the slot2map tables given to setCamera (they are written), one enqueue, no wait.
 #ifndef COSLAM_MERGE_CONSTRAINTS_H
 #define COSLAM_MERGE_CONSTRAINTS_H
 
@@ -111,6 +115,17 @@ public:
         }
         m_nMergeInfo = n;
         return true;
+    }
+
+    // mergeMapPoints + `fp->mpt = 0` + the write of the solved coordinates into MapPoint::M, on the device; enqueues only.  The verdict is
+    // read on the device: behind anything but CS_MERGE_OK nothing is written.  d_pointFeat / d_refStatic / d_mapPts / d_counts [6] may be 0.
+    void mergeMapPoints(int* d_pointFeat, cs_feat_ref* d_featRef, unsigned char* d_refStatic, double* d_mapPts, bool applyPoints = true,
+                        int* d_counts = 0) {
+        int* s2m[16];
+        for (int c = 0; c < 16; ++c) s2m[c] = c < _nCams ? const_cast<int*>(_cams[c].slot2map) : 0;
+        if (cs_merge_constraints_apply_map_dev(_mc, _stream, s2m, d_pointFeat, d_featRef, d_refStatic, _mapCap, d_mapPts, applyPoints ? 1 : 0,
+                                               d_counts) != CS_OK)
+            fail();
     }
 
 private:
