@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "merge_graph.cpp",
     "merge_apply.hip",
     "merge_constraints.hip",
+    "merge_match.hip",
     "liveview.hip",
     "poseupdate.hip",
     "ncc.hip",

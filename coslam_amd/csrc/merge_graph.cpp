@@ -253,3 +253,66 @@ extern "C" int cs_merge_first_constrain(int nKeyFrames, const int* frames, const
     }
     return CS_OK;
 }
+
+// ---- the choice of the camera pair: MergeCameraGroup::matchMergableCameras' loop (src/app/SL_MergeCameraGroup.cpp:325-414), DESIGN 3.24 ----
+// Restated as it runs: the entries classified into a std::map keyed (gId1, gId2) (group pairs in ascending key order, each pair's entries in
+// list order); nMinNCCMatchNum = 20 per group pair; `featMatches[k].num > nMinNCCMatchNum` reads the global success count k, while
+// `nMinNCCMatchNum = featMatches[i].num` reads the index i inside the group pair's list (an unfilled Matching counts 0); maxk and the pair
+// survive from one group pair to the next.  The reference's `m_mergeInfo[i].valid = false` on a short SURF match writes an entry nothing
+// reads again before the list is rebuilt: not restated.  matched with maxk == -1 is where the reference's run is undefined: status -1.
+#include <map>
+#include <utility>
+extern "C" int cs_merge_match_select(int nInfo, const cs_merge_info* info, const int* surfNum, const unsigned char* ematOk, const int* nccNum,
+                                     const unsigned char* eligible, const int* groupSize, cs_merge_match_choice* out) {
+    if (out) {
+        memset(out, 0xFF, sizeof(*out));   // every field -1
+        out->status = 0;
+    }
+    if (nInfo < 0 || nInfo > 256 || !out || (nInfo > 0 && (!info || !surfNum || !ematOk || !nccNum)) || !groupSize) {
+        cs_set_error("cs_merge_match_select: bad arguments (%d entries of at most 256)", nInfo);
+        return CS_ERR_INVALID;
+    }
+    std::map<std::pair<int, int>, std::vector<int>> byPair;
+    for (int e = 0; e < nInfo; ++e) {
+        const int g1 = info[e].gid1, g2 = info[e].gid2;
+        if (g1 < 0 || g2 >= 16 || g1 >= g2) {   // the reference asserts gId1 < gId2
+            cs_set_error("cs_merge_match_select: entry %d names the groups %d / %d", e, g1, g2);
+            return CS_ERR_INVALID;
+        }
+        byPair[std::make_pair(g1, g2)].push_back(e);
+    }
+    int featNum[512];   // featMatches[].num: k < nInfo <= 256, i < nInfo
+    memset(featNum, 0, sizeof(featNum));
+    bool matched = false;
+    int k = 0;
+    for (const auto& gp : byPair) {
+        int nMinNCCMatchNum = 20;
+        const std::vector<int>& list = gp.second;
+        for (size_t i = 0; i < list.size(); ++i) {
+            const int e = list[i];
+            if (surfNum[e] < 25) continue;
+            if (!ematOk[e]) continue;
+            featNum[k] = nccNum[e];
+            matched = true;
+            if (featNum[k] > nMinNCCMatchNum && (!eligible || eligible[e])) {
+                nMinNCCMatchNum = featNum[i];
+                out->maxk = k, out->entry = e;
+                out->maxiCam = info[e].cam1, out->maxjCam = info[e].cam2;
+                out->maxgId1 = gp.first.first, out->maxgId2 = gp.first.second;
+            }
+            ++k;
+        }
+    }
+    if (!matched) return CS_OK;   // status 0
+    if (out->maxk < 0) {
+        out->status = -1;
+        return CS_OK;
+    }
+    out->status = 1;
+    if (groupSize[out->maxgId1] > groupSize[out->maxgId2]) {
+        out->gid1 = out->maxgId1, out->gid2 = out->maxgId2, out->camid1 = out->maxiCam, out->camid2 = out->maxjCam;
+    } else {
+        out->gid1 = out->maxgId2, out->gid2 = out->maxgId1, out->camid1 = out->maxjCam, out->camid2 = out->maxiCam;
+    }
+    return CS_OK;
+}

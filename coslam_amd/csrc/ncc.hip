@@ -535,6 +535,61 @@ static int ncc_get_blocks_group_impl(int device, void* hip_stream, int nCams, co
     return CS_OK;
 }
 
+// getScaledNCCBlocks (SL_NCCBlock.cpp:152-168 -> getNCCBlock, :58-78): the cutter alone, on the small images the caller GIVES (a key
+// frame's KeyPose::imgSmall) -- nothing is resized.  The cutter reads its image through NcCamSet::scaled when `scaled` is set.
+extern "C" int cs_ncc_get_scaled_blocks_group_dev(int device, void* hip_stream, int nCams, const cs_ncc_cam* cams, int Ws, int Hs, int n,
+                                                  double scale) {
+    if (nCams < 1 || nCams > NC_MAX_CAMS || !cams || Ws <= 0 || Hs <= 0 || n < 0 || !(scale > 0)) {
+        cs_set_error("cs_ncc_get_scaled_blocks_group_dev: bad arguments (1..%d cameras)", NC_MAX_CAMS);
+        return CS_ERR_INVALID;
+    }
+    NcCamSet S;
+    memset(&S, 0, sizeof(S));
+    for (int c = 0; c < nCams; ++c) {
+        const cs_ncc_cam& q = cams[c];
+        if (!q.img || (n && (!q.x || !q.y || !q.blocks || !q.abc))) {
+            cs_set_error("cs_ncc_get_scaled_blocks_group_dev: null pointer in camera %d", c);
+            return CS_ERR_INVALID;
+        }
+        S.img[c] = q.img, S.scaled[c] = const_cast<unsigned char*>(q.img) /* read only */, S.x[c] = q.x, S.y[c] = q.y;
+        S.blocks[c] = q.blocks, S.abc[c] = q.abc, S.valid[c] = nullptr;
+    }
+    if (n == 0) return CS_OK;
+    CS_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(k_ncc_blocks_subpix, dim3((n + 3) / 4, nCams), dim3(256), 0, (hipStream_t)hip_stream, S, Ws, Hs, n, scale, 1);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+// SingleSLAM's small image: cv::resize(img, small, Size((int)(W s), (int)(H s))) -- the destination size is given (truncated), so the
+// interpolation's scales are W / Ws and H / Hs (cv::resize: inv_scale = dsize / ssize), not 1 / s.
+extern "C" int cs_ncc_small_dims(int W, int H, double scale, int* Ws, int* Hs) {
+    if (!Ws || !Hs || W <= 0 || H <= 0 || !(scale > 0)) {
+        cs_set_error("cs_ncc_small_dims: bad arguments");
+        return CS_ERR_INVALID;
+    }
+    *Ws = (int)(W * scale);
+    *Hs = (int)(H * scale);
+    return CS_OK;
+}
+extern "C" int cs_ncc_small_image_dev(int device, void* hip_stream, const unsigned char* d_img, int W, int H, double scale,
+                                      unsigned char* d_small) {
+    int Ws = 0, Hs = 0;
+    if (!d_img || !d_small || cs_ncc_small_dims(W, H, scale, &Ws, &Hs) != CS_OK || Ws < 1 || Hs < 1) {
+        cs_set_error("cs_ncc_small_image_dev: bad arguments (%d x %d, scale %g)", W, H, scale);
+        return CS_ERR_INVALID;
+    }
+    NcCamSet S;
+    memset(&S, 0, sizeof(S));
+    S.img[0] = d_img, S.scaled[0] = d_small;
+    CS_HIP(hipSetDevice(device));
+    const double inv_x = (double)Ws / W, inv_y = (double)Hs / H;   // cv::resize: scale_x = 1. / inv_scale_x
+    hipLaunchKernelGGL(k_resize_linear_u8, dim3((Ws + 63) / 64, (Hs + 3) / 4, 1), dim3(256), 0, (hipStream_t)hip_stream, S, W, H, 1. / inv_x,
+                       1. / inv_y, Ws, Hs);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
 extern "C" int cs_ncc_epi_mat_dev(int device, void* hip_stream, const double F[9], int M, const double* d_x1, const double* d_y1,
                                   const unsigned char* d_blocks1, const double* d_abc1, const int* d_valid1, int N,
                                   const double* d_x2, const double* d_y2, const unsigned char* d_blocks2, const double* d_abc2,

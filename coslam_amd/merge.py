@@ -595,6 +595,44 @@ class MergeCamGroups:
         self.last_merge_frame = cur
         return rep
 
+    def run_from_seeds(self, matcher, match_cams, Ws, Hs, infos, surf_num, emat_ok, jobs, history, tables, groups, key_frames, self_motion,
+                             key_groups, pixelErrVar, epi_max=20.0, ncc_min=0.45, max_disp=150.0, last_release_frame=None, n_max_keyfrm=100,
+                             stream_ptr=None):
+        """mergeCamGroups from the gate's list on: matcher -> counts (the one wait in front of the choice) -> merge_match_select -> run() with the
+        chosen pair and the chosen job's matches handed over as a DEVICE table (never copied through the host).
+        infos: the gate's list [(frame1, cam1, gid1, frame2, cam2, gid2)]; surf_num / emat_ok per entry (the host front: matchSURFPoints' count,
+        computeEMat > 0); jobs: per entry None (skipped by the front) or dict(E, seeds) -- iCam / jCam are the entry's cameras.
+        -> run()'s dict, plus choice (merge_match_select's dict), match_counts [nJobs][4] and job_of_entry; status "no_pair" when nothing
+        was chosen (choice.status 0 or -1): nothing is enqueued behind the matcher then."""
+        import torch
+
+        s = torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        job_of, jl = [-1] * len(infos), []
+        for e, (inf, j) in enumerate(zip(infos, jobs)):
+            if j is None or surf_num[e] < 25 or not emat_ok[e]:
+                continue
+            job_of[e] = len(jl)
+            jl.append(dict(iCam=int(inf[1]), jCam=int(inf[4]), E=j["E"], seeds=j.get("seeds")))
+            if jl[-1]["seeds"] is None:
+                jl[-1].pop("seeds")
+        if jl:
+            matcher.run(match_cams, Ws, Hs, jl, epi_max, ncc_min, max_disp, stream_ptr=s)
+        cnt = matcher.counts(len(jl), stream_ptr=s)
+        ncc = [int(cnt[k][0]) if k >= 0 else 0 for k in job_of]
+        elig = [1 if k >= 0 and cnt[k][1] == 0 else 0 for k in job_of]
+        ok = [1 if (emat_ok[e] and job_of[e] >= 0) else 0 for e in range(len(infos))]
+        rec = _camera_groups_record(groups)
+        choice = merge_match_select(infos, surf_num, ok, ncc, [int(rec.num[g]) for g in range(MAX_CAMS)], elig)
+        if choice["status"] != 1:
+            return dict(status="no_pair", merged=False, choice=choice, match_counts=cnt, job_of_entry=job_of)
+        k = job_of[choice["entry"]]
+        d_matches = torch.as_tensor(_DeviceInt32View(matcher.matches_ptr(k), int(cnt[k][0])), device=torch.device("cuda", self.device))
+        rep = self.run(history, tables, groups, key_frames, self_motion, key_groups,
+                       (choice["maxgId1"], choice["maxgId2"], choice["maxiCam"], choice["maxjCam"]), d_matches, pixelErrVar,
+                       last_release_frame=last_release_frame, n_max_keyfrm=n_max_keyfrm, stream_ptr=s)
+        rep.update(choice=choice, match_counts=cnt, job_of_entry=job_of, matches_ptr=matcher.matches_ptr(k))
+        return rep
+
     def close(self):
         if self.ma is not None:
             self.ma.close()
@@ -608,3 +646,207 @@ class MergeCamGroups:
             self.close()
         except Exception:
             pass
+
+
+MERGE_MATCH_MAX_JOBS = 256
+MERGE_MATCH_PAIRS_OVERFLOW, MERGE_MATCH_MATCHES_OVERFLOW = 1, 2
+
+
+class MergeMatchCam(C.Structure):
+    """== cs_merge_match_cam (include/coslam_hip.h): xy / state / imgSmall device pointers, K a HOST pointer."""
+
+    _fields_ = [("xy", C.c_void_p), ("state", C.c_void_p), ("K", C.c_void_p), ("imgSmall", C.c_void_p), ("imgScale", C.c_double)]
+
+
+class MergeMatchJob(C.Structure):
+    """== cs_merge_match_job."""
+
+    _fields_ = [("iCam", C.c_int), ("jCam", C.c_int), ("E", C.c_double * 9), ("nSeeds", C.c_int), ("seeds", C.c_void_p)]
+
+
+class MergeMatchBuffers(C.Structure):
+    """== cs_merge_match_buffers."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("matches", "scores", "counts", "pairs", "pairCount", "blocks", "abc", "valid")] + \
+               [(n, C.c_int) for n in ("nCams", "N", "maxJobs", "maxSeeds", "pairCap", "maxMatches")]
+
+
+class MergeMatchChoice(C.Structure):
+    """== cs_merge_match_choice."""
+
+    _fields_ = [(n, C.c_int) for n in ("status", "entry", "maxk", "maxiCam", "maxjCam", "maxgId1", "maxgId2", "gid1", "gid2", "camid1", "camid2")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class _DeviceInt32View:
+    """a [rows][2] int32 table in device memory as torch.as_tensor takes it (no copy)"""
+
+    def __init__(self, ptr, rows):
+        self.__cuda_array_interface__ = dict(shape=(int(rows), 2), typestr="<i4", data=(int(ptr), False), version=2, strides=None)
+
+
+def merge_match_fmat(K1, K2, E):
+    """cs_merge_match_fmat (host code): F of matchFeaturePointsNCC = iK1^T E^T iK2"""
+    import numpy as np
+
+    a, b, e = (np.ascontiguousarray(v, dtype=np.float64).reshape(9) for v in (K1, K2, E))
+    F = np.zeros(9)
+    p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+    check(lib().cs_merge_match_fmat(p(a), p(b), p(e), p(F)), "cs_merge_match_fmat")
+    return F
+
+
+def merge_match_select(infos, surf_num, emat_ok, ncc_num, group_size, eligible=None):
+    """cs_merge_match_select (host code): matchMergableCameras' loop over the gate's list.  infos: [(frame1, cam1, gid1, frame2, cam2, gid2)]
+    (MergeCandidates.infos()); per entry the SURF match count, whether computeEMat succeeded, the NCC match count and (optionally) whether
+    the job may be chosen (a flagged job may not); group_size[g] = camGroups[g].num.  -> dict(status, entry, maxk, maxiCam, maxjCam, maxgId1,
+    maxgId2, gid1, gid2, camid1, camid2); status 1: chosen, 0: nothing matched, -1: the reference's undefined run (no pair)."""
+    import numpy as np
+
+    n = len(infos)
+    arr = (MergeInfo * max(n, 1))()
+    for a, t in zip(arr, infos):
+        for (name, _), v in zip(MergeInfo._fields_, t):
+            setattr(a, name, int(v))
+    sn = np.ascontiguousarray(surf_num, dtype=np.int32).reshape(-1)
+    ok = np.ascontiguousarray(np.asarray(emat_ok) != 0, dtype=np.uint8).reshape(-1)
+    nn = np.ascontiguousarray(ncc_num, dtype=np.int32).reshape(-1)
+    assert len(sn) == n and len(ok) == n and len(nn) == n
+    gs = np.zeros(MAX_CAMS, np.int32)
+    gs[:len(group_size)] = np.asarray(group_size, dtype=np.int32)
+    el = None if eligible is None else np.ascontiguousarray(np.asarray(eligible) != 0, dtype=np.uint8).reshape(-1)
+    p = lambda v: C.c_void_p(v.ctypes.data) if v is not None and len(v) else None  # noqa: E731
+    out = MergeMatchChoice()
+    check(lib().cs_merge_match_select(n, arr, p(sn), p(ok), p(nn), p(el), p(gs), C.byref(out)), "cs_merge_match_select")
+    return out.as_dict()
+
+
+class MergeMatcher:
+    """cs_merge_match: MergeCameraGroup::matchFeaturePointsNCC on the device for the candidate camera pairs of a key frame -- blocks from
+    the key frame's small images, the epipolar / NCC candidate lists, the seed-guided greedy one-to-one matching.  The
+    outputs stay in device memory: matches_ptr(k) is what MergeConstraints.assemble / MergeCamGroups.run take as a device table."""
+
+    def __init__(self, n_cams, N, max_jobs, max_seeds, pair_cap, max_matches, device=0):
+        L = lib()
+        L.cs_merge_match_create.restype = C.c_void_p
+        self._L, self.device, self.n_cams, self.N = L, int(device), int(n_cams), int(N)
+        self.max_jobs, self.max_seeds, self.pair_cap, self.max_matches = int(max_jobs), int(max_seeds), int(pair_cap), int(max_matches)
+        self._m = L.cs_merge_match_create(self.device, self.n_cams, self.N, self.max_jobs, self.max_seeds, self.pair_cap, self.max_matches)
+        if not self._m:
+            check(-1, "cs_merge_match_create")
+        self.buf = MergeMatchBuffers()
+        check(L.cs_merge_match_buffers_get(C.c_void_p(self._m), C.byref(self.buf)), "cs_merge_match_buffers_get")
+        self._keep = None
+
+    def _stream(self, stream_ptr):
+        import torch
+
+        return torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+
+    def run(self, cams, Ws, Hs, jobs, epi_max=20.0, ncc_min=0.45, max_disp=150.0, stream_ptr=None):
+        """cs_merge_match_run_dev.  cams: per camera a dict xy, state, imgSmall (device pointers), K (9 doubles, HOST array), imgScale;
+        jobs: [dict(iCam, jCam, E [9], seeds [n][4] = x1, y1, x2, y2)].  The defaults are the reference's call (20.0, 0.45, 150).
+        Enqueues only."""
+        import numpy as np
+
+        vp = C.c_void_p
+        ca = (MergeMatchCam * max(len(cams), 1))()
+        keep = []
+        for a, c in zip(ca, cams):
+            K = np.ascontiguousarray(c["K"], dtype=np.float64).reshape(9)
+            keep.append(K)
+            a.xy, a.state, a.K, a.imgSmall, a.imgScale = int(c["xy"]) or None, int(c["state"]) or None, K.ctypes.data, int(c["imgSmall"]) or None, float(c["imgScale"])
+        ja = (MergeMatchJob * max(len(jobs), 1))()
+        for a, j in zip(ja, jobs):
+            sd = np.ascontiguousarray(np.asarray(j.get("seeds", np.zeros((0, 4))), dtype=np.float64).reshape(-1, 4))
+            keep.append(sd)
+            a.iCam, a.jCam, a.nSeeds, a.seeds = int(j["iCam"]), int(j["jCam"]), len(sd), (sd.ctypes.data if len(sd) else None)
+            a.E[:] = [float(v) for v in np.asarray(j["E"], dtype=np.float64).reshape(9)]
+        if len(cams) != self.n_cams:
+            raise ValueError(f"MergeMatcher.run: {len(cams)} cameras, the handle has {self.n_cams}")
+        check(self._L.cs_merge_match_run_dev(vp(self._m), vp(self._stream(stream_ptr)), ca, int(Ws), int(Hs), len(jobs), ja if len(jobs) else None,
+                                             C.c_double(epi_max), C.c_double(ncc_min), C.c_double(max_disp)), "cs_merge_match_run_dev")
+
+    def from_pairs(self, d_pairs, d_pair_count, d_xy1, d_xy2, seeds=None, max_disp=150.0, stream_ptr=None):
+        """cs_merge_match_from_pairs_dev: the matcher alone.  Per job a device pointer to its cs_ncc_pair records, to its count, to the
+        positions of both cameras (2N doubles each); seeds: per job a host [n][4] array or None.  Enqueues only."""
+        import numpy as np
+
+        vp = C.c_void_p
+        n = len(d_pairs)
+        arr = lambda v: (vp * max(n, 1))(*[vp(int(x)) if x else None for x in v])  # noqa: E731
+        sds = [np.ascontiguousarray(np.asarray(s if s is not None else np.zeros((0, 4)), dtype=np.float64).reshape(-1, 4))
+               for s in (seeds if seeds is not None else [None] * n)]
+        ns = (C.c_int * max(n, 1))(*[len(s) for s in sds])
+        sp = (vp * max(n, 1))(*[vp(s.ctypes.data) if len(s) else None for s in sds])
+        check(self._L.cs_merge_match_from_pairs_dev(vp(self._m), vp(self._stream(stream_ptr)), n, arr(d_pairs), arr(d_pair_count), arr(d_xy1),
+                                                    arr(d_xy2), ns, sp, C.c_double(max_disp)), "cs_merge_match_from_pairs_dev")
+
+    def counts(self, n_jobs, stream_ptr=None):
+        """cs_merge_match_counts: the stage's one host wait -> int32 [n_jobs][4] = matches kept, flags, candidates, rounds"""
+        import numpy as np
+
+        out = np.zeros((max(int(n_jobs), 1), 4), np.int32)
+        check(self._L.cs_merge_match_counts(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), int(n_jobs), C.c_void_p(out.ctypes.data)),
+              "cs_merge_match_counts")
+        return out[:int(n_jobs)]
+
+    def matches_ptr(self, job):
+        """device pointer of job's [maxMatches][2] int32 slot pairs"""
+        return int(self.buf.matches) + 8 * self.max_matches * int(job)
+
+    def _down(self, ptr, n, dtype, stream_ptr=None):
+        import numpy as np
+
+        out = np.zeros(n, dtype)
+        if out.nbytes:
+            check(self._L.cs_merge_match_download(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(ptr),
+                                                  C.c_void_p(out.ctypes.data), C.c_size_t(out.nbytes)), "cs_merge_match_download")
+        return out
+
+    def matches(self, job, count, stream_ptr=None):
+        """-> (int32 [count][2] slot pairs in acceptance order, float64 [count] scores) of one job; waits"""
+        import numpy as np
+
+        m = self._down(self.matches_ptr(job), 2 * int(count), np.int32, stream_ptr).reshape(-1, 2)
+        return m, self._down(int(self.buf.scores) + 8 * self.max_matches * int(job), int(count), np.float64, stream_ptr)
+
+    def blocks(self, stream_ptr=None):
+        """-> (uint8 [nCams][N][128], float64 [nCams][N][4], int32 [nCams][N]) of the last run; waits"""
+        import numpy as np
+
+        n = self.n_cams * self.N
+        return self._down(self.buf.blocks, n * 128, np.uint8, stream_ptr).reshape(self.n_cams, self.N, 128), \
+            self._down(self.buf.abc, n * 4, np.float64, stream_ptr).reshape(self.n_cams, self.N, 4), \
+            self._down(self.buf.valid, n, np.int32, stream_ptr).reshape(self.n_cams, self.N)
+
+    def pairs(self, slot, stream_ptr=None):
+        """the candidate list at batch slot `slot` of the last batch -> (total that passed, records cut to pairCap as a structured array
+        i, j, epi, ncc); the list's order is not defined; waits"""
+        import numpy as np
+
+        dt = np.dtype([("i", np.int32), ("j", np.int32), ("epi", np.float64), ("ncc", np.float64)])
+        total = int(self._down(int(self.buf.pairCount) + 4 * int(slot), 1, np.int32, stream_ptr)[0])
+        return total, self._down(int(self.buf.pairs) + dt.itemsize * self.pair_cap * int(slot), min(total, self.pair_cap), dt, stream_ptr)
+
+    def close(self):
+        if self._m:
+            self._L.cs_merge_match_destroy(C.c_void_p(self._m))
+            self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ncc_small_image_dev(stream_ptr, d_img, W, H, scale, d_small, device=0):
+    """cs_ncc_small_image_dev: SingleSLAM's small image, cv::resize(img, small, Size((int)(W s), (int)(H s))) -> (Ws, Hs); enqueues only"""
+    ws, hs = C.c_int(), C.c_int()
+    check(lib().cs_ncc_small_dims(int(W), int(H), C.c_double(scale), C.byref(ws), C.byref(hs)), "cs_ncc_small_dims")
+    check(lib().cs_ncc_small_image_dev(int(device), C.c_void_p(stream_ptr), C.c_void_p(d_img), int(W), int(H), C.c_double(scale), C.c_void_p(d_small)),
+          "cs_ncc_small_image_dev")
+    return ws.value, hs.value

@@ -1200,6 +1200,114 @@ int cs_merge_constraints_apply_map_dev(cs_merge_constraints* mc, void* hip_strea
                                        cs_feat_ref* d_featRef, unsigned char* d_refStatic, int nMap, double* d_mapPts, int applyPoints,
                                        int* d_counts);
 
+/* ---- the merge matcher: MergeCameraGroup::matchFeaturePointsNCC (src/app/SL_MergeCameraGroup.cpp:262-307) behind storeFeaturePoints
+ * (:179-188), and the choice of the camera pair in matchMergableCameras (:320-421); DESIGN.md 3.24 ----
+ * What stays on the host enters as input: per candidate camera pair (a JOB) the essential matrix E of computeEMat and the positions of
+ * the inlier SURF matches (getMatchedPts(newMatches, surfPts1, surfPts2): seed rows {x1, y1, x2, y2}).  Per camera (host array): xy / state
+ * of the CURRENT key frame in device memory (xy: x[N] then y[N], the hand-back's undistorted pixels; camera c's list is its slots with
+ * state 0 / 1 in slot order -- the device works on slots behind that mask, a match's list index in the reference is the slot's rank), K as
+ * 9 doubles in HOST memory (F is formed on the host), the key frame's small image imgSmall (Ws x Hs bytes, device: KeyPose::setSmallImage)
+ * and imgScale (per camera, as KeyPose holds it: the cutter runs once per distinct value).  All cameras of one call share Ws and Hs.  A live
+ * slot whose position is not finite or beyond 1e6 pixels takes no part (its mask entry is 0).
+ * cs_merge_match_run_dev enqueues on hip_stream, with no host wait in between:
+ *   blocks      getScaledNCCBlocks: cv::getRectSubPix(imgSmall, 11 x 11, (x imgScale, y imgScale)) of EVERY slot, replicated border
+ *               (cs_ncc_get_scaled_blocks_group_dev: one launch for all cameras); valid = state 0 / 1
+ *   F           host: mat33Trans(E, Et); getFMat(iK2, iK1, Et, F) = iK1^T E^T iK2 (cs_merge_match_fmat)
+ *   candidates  getEpiNccMat as a list: cs_ncc_epi_pairs_group_dev (<= 8 jobs a launch) with epiMax / nccMin (the reference: 20.0, 0.45)
+ *   matches     k_merge_match, one workgroup per job: getDisparityMat's guide (maxDisp; the reference: 150; nSeeds == 0: no guide),
+ *               greedyGuidedNCCMatch, the matches in acceptance order (score falling, then slot in iCam rising, then slot in jCam rising).
+ *               No cap below pairCap; the result does not depend on the order of the candidate list.
+ * Jobs beyond maxJobs run in batches of maxJobs on the same stream (the candidate lists are the batch's; the outputs are every job's).
+ * The job tables and seeds are uploaded from staging copies the handle keeps: a call first waits for the stream of the handle's PREVIOUS
+ * call if that left such copies (the one wait in front of the stage; none inside it).
+ * Out, per job k < CS_MERGE_MATCH_MAX_JOBS, in device memory: matches [k][maxMatches][2] SLOT pairs (slot in iCam, slot in jCam: what
+ * cs_merge_constraints_assemble_dev takes as d_matches), scores [k][maxMatches], counts [k][4] = {matches kept, flags, candidates that
+ * passed (may exceed pairCap), rounds of the matcher}.  Flags: CS_MERGE_MATCH_PAIRS_OVERFLOW (the list overflowed pairCap: pairs were
+ * dropped in no fixed order), CS_MERGE_MATCH_MATCHES_OVERFLOW (more than maxMatches matches: the tail was dropped, the head is the
+ * greedy's head).  A flagged job is not eligible for cs_merge_match_select.
+ * Device memory of a handle: maxJobs x pairCap x (sizeof(cs_ncc_pair) + 24) bytes (the lists and the matcher's two packed working
+ * lists) + nCams x N x 180 (blocks 128, abc 32, mask 4, positions 16) + maxJobs x (N x 48 + maxSeeds x 32) + 256 x maxMatches x 16 (outputs).
+ * Scores are the candidates' bits, except that a score of -0.0 is reported as +0.0 (the two share a place in the order).
+ * CS_ERR_INVALID before any launch (cs_last_error text): null handle / table, camera ids outside the rig, iCam == jCam, nSeeds > maxSeeds,
+ * more than CS_MERGE_MATCH_MAX_JOBS jobs; creation: nCams 1..16, N 1..32768 (slot pairs are packed into 16 bits each), maxJobs 1..256,
+ * maxSeeds >= 0, pairCap >= 1, maxMatches >= 1. */
+#define CS_MERGE_MATCH_MAX_JOBS 256
+struct cs_ncc_pair;   /* below: the NCC section */
+struct cs_ncc_cam;
+enum { CS_MERGE_MATCH_PAIRS_OVERFLOW = 1, CS_MERGE_MATCH_MATCHES_OVERFLOW = 2 };
+typedef struct {
+    const double* xy;                 /* device, 2N */
+    const int* state;                 /* device, N */
+    const double* K;                  /* HOST, 9 */
+    const unsigned char* imgSmall;    /* device, Ws x Hs */
+    double imgScale;
+} cs_merge_match_cam;
+typedef struct {
+    int iCam, jCam;
+    double E[9];
+    int nSeeds;
+    const double* seeds;              /* HOST [nSeeds][4] = {x1, y1, x2, y2}; copied by the call */
+} cs_merge_match_job;
+typedef struct {
+    const int* matches;               /* [CS_MERGE_MATCH_MAX_JOBS][maxMatches][2] */
+    const double* scores;             /* [CS_MERGE_MATCH_MAX_JOBS][maxMatches] */
+    const int* counts;                /* [CS_MERGE_MATCH_MAX_JOBS][4] */
+    const struct cs_ncc_pair* pairs;         /* [maxJobs][pairCap]: the candidate lists of the LAST batch (job k of the batch at slot k) */
+    const int* pairCount;             /* [maxJobs] */
+    const unsigned char* blocks;      /* [nCams][N][128] */
+    const double* abc;                /* [nCams][N][4] */
+    const int* valid;                 /* [nCams][N] */
+    int nCams, N, maxJobs, maxSeeds, pairCap, maxMatches;
+} cs_merge_match_buffers;
+typedef struct { int count, flags, candidates, rounds; } cs_merge_match_count;
+typedef struct cs_merge_match cs_merge_match;
+cs_merge_match* cs_merge_match_create(int device, int nCams, int N, int maxJobs, int maxSeeds, int pairCap, int maxMatches);
+void cs_merge_match_destroy(cs_merge_match* mm);
+/* F of matchFeaturePointsNCC from K1, K2 (cameras iCam, jCam) and E; host code; mat33Inv is Gauss-Jordan with partial pivoting.
+ * CS_ERR_INVALID for a singular K. */
+int cs_merge_match_fmat(const double K1[9], const double K2[9], const double E[9], double F[9]);
+int cs_merge_match_run_dev(cs_merge_match* mm, void* hip_stream, const cs_merge_match_cam* cams /* host [nCams] */, int Ws, int Hs,
+                           int nJobs, const cs_merge_match_job* jobs /* host */, double epiMax, double nccMin, double maxDisp);
+/* k_merge_match alone on the caller's candidate lists (device memory; any order; records with a slot outside 0 .. N - 1 or a NaN score are
+ * ignored; a pair listed twice is one candidate): job k reads d_pairs[k] / *d_pairCount[k] (a count above pairCap sets the overflow flag
+ * and pairCap records are read), positions from d_xy1[k] / d_xy2[k] (2N doubles each), seeds as in cs_merge_match_job.  nJobs <= maxJobs. */
+int cs_merge_match_from_pairs_dev(cs_merge_match* mm, void* hip_stream, int nJobs, const struct cs_ncc_pair* const* d_pairs /* host array */,
+                                  const int* const* d_pairCount /* host array */, const double* const* d_xy1 /* host array */,
+                                  const double* const* d_xy2 /* host array */, const int* nSeeds /* host */,
+                                  const double* const* seeds /* host array of host [nSeeds][4] */, double maxDisp);
+/* counts and flags of jobs 0 .. nJobs - 1 in host memory: the stage's ONE host wait */
+int cs_merge_match_counts(cs_merge_match* mm, void* hip_stream, int nJobs, cs_merge_match_count* h_out);
+int cs_merge_match_buffers_get(const cs_merge_match* mm, cs_merge_match_buffers* out);
+/* bytes of one of the handle's device buffers to the host; waits for hip_stream */
+int cs_merge_match_download(cs_merge_match* mm, void* hip_stream, const void* d_src, void* h_dst, size_t bytes);
+/* getScaledNCCBlocks for every camera of a group: cams[c].img is the GIVEN small image (Ws x Hs; nothing is resized, `scaled` is not
+ * used), the block of point p is cut at (x[p] scale, y[p] scale) by the cutter of cs_ncc_get_blocks_group_dev; `valid` is left alone. */
+int cs_ncc_get_scaled_blocks_group_dev(int device, void* hip_stream, int nCams, const struct cs_ncc_cam* cams /* host */, int Ws, int Hs, int n,
+                                       double scale);
+/* The small image of a key frame: SingleSLAM's cv::resize(img, small, Size((int)(W s), (int)(H s))) (src/app/SL_SingleSLAM.cpp:275,
+ * 323-325) [INTER_LINEAR, 8-bit], d_small: (int)(W s) x (int)(H s) bytes (cs_ncc_small_dims).  The destination size is TRUNCATED and the
+ * scales of the interpolation are W / Ws and H / Hs: wherever W s is not an integer this differs from cs_ncc_get_blocks_group_dev's
+ * `Size(), s, s` form (rounded size, scale 1 / s). */
+int cs_ncc_small_dims(int W, int H, double scale, int* Ws, int* Hs);
+int cs_ncc_small_image_dev(int device, void* hip_stream, const unsigned char* d_img, int W, int H, double scale, unsigned char* d_small);
+/* matchMergableCameras' loop (:325-414) over the gate's list, restated as it runs; host code, no device.  info [nInfo]: the gate's
+ * cs_merge_candidates.info; per entry surfNum (matchSURFPoints' count; fewer than 25: skipped), ematOk (computeEMat > 0; 0: skipped, k
+ * not advanced), nccNum (the job's match count; the caller passes 0 for a flagged job, and eligible[e] == 0 -- may be NULL -- keeps
+ * entry e from being chosen though it still advances k and fills its featMatches slot).  The entries are classified by (gid1, gid2) in
+ * ascending key order, nMinNCCMatchNum = 20 is reset per group pair, the comparison reads featMatches[k].num and the new threshold is
+ * taken from featMatches[i].num (i: the index inside the group pair's list, k: the global count of successes; an unfilled Matching
+ * counts 0).  groupSize [16]: camGroups[g].num.  Out: cs_merge_match_choice; status 1: a pair was chosen; 0: nothing matched (numMatched
+ * 0); -1: matched but no pair above the threshold -- the reference then indexes camGroups[-1] and featMatches[-1] (undefined;
+ * DESIGN.md 8.2): no pair is returned. */
+typedef struct {
+    int status;                       /* 1 / 0 / -1 as above */
+    int entry;                        /* index into info[] of the chosen entry, -1 */
+    int maxk, maxiCam, maxjCam, maxgId1, maxgId2;
+    int gid1, gid2, camid1, camid2;   /* m_gid1 / m_gid2 / m_camid1 / m_camid2: the larger group first (:400-414) */
+} cs_merge_match_choice;
+int cs_merge_match_select(int nInfo, const cs_merge_info* info, const int* surfNum, const unsigned char* ematOk, const int* nccNum,
+                          const unsigned char* eligible, const int* groupSize, cs_merge_match_choice* out);
+
 /* CoSLAM::mapPointsClassify (src/app/SL_CoSLAM.cpp:418-520) over the references: from the next call on cs_map_points_classify_dev and
  * cs_pose_update_classify_frame_dev read d_featRef ([nMap][nCams], the table cs_feat_ref_advance_dev keeps: as the END of the previous
  * frame left it, or already at this frame) next to d_pointFeat (this frame's features): a camera that lost the point still gives
