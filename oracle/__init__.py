@@ -734,14 +734,21 @@ def _dd(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-def intracam_estimate(K, R0, t0, npts, prevErrs, Ms, ms, tau):
-    """okp_intracam_estimate -> (ok, R[3,3], t[3], opt)"""
+def intracam_estimate(K, R0, t0, npts, prevErrs, Ms, ms, tau, opt=None):
+    """okp_intracam_estimate -> (ok, R[3,3], t[3], opt).  opt: the options to start from (any record with PoseOption's 96-byte
+    layout, e.g. coslam_amd.IntraCamPoseOption; it is copied, not written to); None = IntraCamPoseOption()'s defaults.
+    With maxIterRW == 0 the reference never writes R_opt / t_opt; the output buffers are handed over holding R0 / t0, so that case
+    returns the start pose (every other case overwrites them in its first LM step)."""
     L = lib()
     K, R0, t0, Ms, ms = _dd(K).ravel(), _dd(R0).ravel(), _dd(t0).ravel(), _dd(Ms).ravel(), _dd(ms).ravel()
     pe = None if prevErrs is None else _dd(prevErrs).ravel()
-    R, t = np.zeros(9), np.zeros(3)
+    R, t = R0.copy(), t0.copy()
     o = PoseOption()
-    L.okp_option_default(C.byref(o))
+    if opt is None:
+        L.okp_option_default(C.byref(o))
+    else:
+        assert C.sizeof(opt) == C.sizeof(PoseOption)
+        C.memmove(C.byref(o), C.byref(opt), C.sizeof(PoseOption))
     ok = L.okp_intracam_estimate(_p(K), _p(R0), _p(t0), int(npts), None if pe is None else _p(pe), _p(Ms), _p(ms),
                                  C.c_double(tau), _p(R), _p(t), C.byref(o))
     return bool(ok), R.reshape(3, 3), t, o

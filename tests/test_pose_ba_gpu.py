@@ -8,31 +8,16 @@ import pytest
 
 import coslam_amd
 import oracle
-from coslam_amd.synth import Scene, make_ba_problem, rodrigues
+from coslam_amd.synth import Scene, make_ba_problem
+from tests import pose_cases
+from tests.pose_cases import pose_problem
 
 pytestmark = pytest.mark.gpu
 
 
-def pose_problem(seed, npts=192, noise=0.5, n_out=10, frame=3):
-    rng = np.random.default_rng(seed)
-    sc = Scene(1, 640, 480, 3000, seed=100 + seed)
-    R, t = sc.pose(0, frame)
-    uv, vis = sc.project(0, frame)
-    idx = np.nonzero(vis)[0][:npts]
-    Ms = np.ascontiguousarray(sc.points[idx])
-    ms = uv[idx] + noise * rng.standard_normal((len(idx), 2))
-    ms[:n_out] += 30 * rng.standard_normal((n_out, 2))
-    R0 = R @ rodrigues(0.01 * rng.standard_normal(3))
-    t0 = t + 0.03 * rng.standard_normal(3)
-    return sc.K, R0, t0, Ms, np.ascontiguousarray(ms), R, t
-
-
-@pytest.mark.parametrize("seed,npts", [(0, 192), (1, 192), (2, 64), (3, 7), (4, 1000), (5, 5000)])
-def test_intracam_matches_oracle(hip, seed, npts):
-    K, R0, t0, Ms, ms, Rgt, tgt = pose_problem(seed, npts, n_out=min(10, npts // 4))
-    n = len(Ms)
-    ok_g, R_g, t_g, o_g = coslam_amd.intraCamEstimate(K, R0, t0, n, None, Ms, ms, 10.0)
-    ok_o, R_o, t_o, o_o = oracle.intracam_estimate(K, R0, t0, n, None, Ms, ms, 10.0)
+def _check_intracam(res_g, res_o):
+    ok_g, R_g, t_g, o_g = res_g
+    ok_o, R_o, t_o, o_o = res_o
     assert ok_g == ok_o
     assert np.max(np.abs(R_g - R_o)) < 1e-6 and np.max(np.abs(t_g - t_o)) < 1e-6
     if o_g.nIterRW == o_o.nIterRW and o_g.nIterLM == o_o.nIterLM:
@@ -41,6 +26,33 @@ def test_intracam_matches_oracle(hip, seed, npts):
         assert np.max(np.abs(R_g - R_o)) < 1e-8 and np.max(np.abs(t_g - t_o)) < 1e-7
         assert abs(o_g.err - o_o.err) <= 1e-8 * max(1.0, abs(o_o.err))
     assert np.allclose(R_g @ R_g.T, np.eye(3), atol=1e-9)
+
+
+# (seed, npts); from 0 on: the sizes at which the host entry takes another path -- no point at all, one wave | four waves (64 | 65),
+# the second trip of the pass over the points (256 | 257), weights in LDS | in global scratch (4096 | 4097)
+@pytest.mark.parametrize("seed,npts", [(0, 192), (1, 192), (2, 64), (3, 7), (4, 1000), (5, 5000)] +
+                         [(c["seed"], c["npts"]) for c in pose_cases.HOST_CASES if c["npts"] in (0, 65, 256, 257, 4096, 4097)])
+def test_intracam_matches_oracle(hip, seed, npts):
+    K, R0, t0, Ms, ms, Rgt, tgt = pose_problem(seed, npts, n_out=min(10, npts // 4))
+    n = len(Ms)
+    assert n == npts
+    if npts in (4097, 5000):
+        assert len(Ms) > 4096          # the weights do not fit LDS: the global scratch block
+    _check_intracam(coslam_amd.intraCamEstimate(K, R0, t0, n, None, Ms, ms, 10.0), oracle.intracam_estimate(K, R0, t0, n, None, Ms, ms, 10.0))
+
+
+def test_intracam_staging_block_grows_and_is_reused(hip):
+    """5000 -> 100 -> 6000 -> 100 points on one thread: the staging block of the host entry is allocated, reused for a smaller problem,
+    replaced by a larger one and reused again; every answer is the oracle's, and the two small ones are the same bytes."""
+    small = []
+    for seed, npts in ((5, 5000), (7, 100), (6, 6000), (7, 100)):
+        K, R0, t0, Ms, ms, _, _ = pose_problem(seed, npts)
+        assert len(Ms) == npts
+        res = coslam_amd.intraCamEstimate(K, R0, t0, npts, None, Ms, ms, 10.0)
+        _check_intracam(res, oracle.intracam_estimate(K, R0, t0, npts, None, Ms, ms, 10.0))
+        if npts == 100:
+            small.append((res[0], res[1].tobytes(), res[2].tobytes(), bytes(res[3])))
+    assert small[0] == small[1]
 
 
 def test_intracam_with_prev_errors_and_failure_modes(hip):
@@ -53,6 +65,15 @@ def test_intracam_with_prev_errors_and_failure_modes(hip):
     K, R0, t0, Ms, ms, Rgt, tgt = pose_problem(9, 150, noise=0.0, n_out=0)
     ok, R, t, _ = coslam_amd.intraCamEstimate(K, R0, t0, 150, None, Ms, ms, 10.0)
     assert ok and np.max(np.abs(R - Rgt)) < 1e-6 and np.max(np.abs(t - tgt)) < 1e-5
+    # a failing solve: one not-a-number measurement among valid ones -> every LM step rejected until lambda passes 1e18, ok false,
+    # retTypeLM -1 and the start pose back, bit for bit -- as the oracle has it
+    K, R0, t0, Ms, ms = pose_cases.failing(*pose_cases.build(pose_cases.FAIL_CASE))[:5]
+    ok_g, R_g, t_g, o_g = coslam_amd.intraCamEstimate(K, R0, t0, len(Ms), None, Ms, ms, 10.0)
+    ok_o, R_o, t_o, o_o = oracle.intracam_estimate(K, R0, t0, len(Ms), None, Ms, ms, 10.0)
+    assert not ok_o and o_o.retTypeLM == -1
+    assert not ok_g and o_g.retTypeLM == -1 and (o_g.nIterLM, o_g.nIterRW) == (o_o.nIterLM, o_o.nIterRW) == (21, 0)
+    assert R_g.tobytes() == np.ascontiguousarray(R0).tobytes() == R_o.tobytes() and t_g.tobytes() == np.ascontiguousarray(t0).tobytes() == t_o.tobytes()
+    assert np.isnan(o_g.err) and np.isnan(o_o.err) and o_g.lambda_ == o_o.lambda_ > 1e18
 
 
 def ba_inputs(**kw):
