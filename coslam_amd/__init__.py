@@ -37,7 +37,7 @@ from .posegraph import PoseGraphs, after_ba_function, after_ba_record, posegraph
 from .results import ExportCam, LoopExportCam, export_results_v1, loop_export_results  # noqa: F401,E402
 from .grouping import (CameraGroups, GroupingCam, camera_grouping_dev, camera_grouping_scratch_bytes, grouping_cams,  # noqa: F401,E402
                        view_overlap_costs_dev)
-from .merge import (MergeApply, MergeCamGroups, MergeConstraints, MergeMatcher, MergePoseCorrection, merge_first_constrain,  # noqa: F401,E402
+from .merge import (MergeApply, MergeCamGroups, MergeConstraints, MergeFront, MergeMatcher, MergePoseCorrection, merge_first_constrain,  # noqa: F401,E402
                     merge_keygraph_plan, merge_match_fmat, merge_match_select, merge_matched_groups, ncc_small_image_dev,
                     recompute_map_points_keyfrms_dev)
 from .liveview import LiveHeader, LiveView, MapCounts, map_counts_dev, map_counts_scratch_bytes  # noqa: F401,E402

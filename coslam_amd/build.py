@@ -30,6 +30,7 @@ HIP_SOURCES = [
     "merge_apply.hip",
     "merge_constraints.hip",
     "merge_match.hip",
+    "merge_front.hip",
     "liveview.hip",
     "poseupdate.hip",
     "ncc.hip",

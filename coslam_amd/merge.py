@@ -633,6 +633,25 @@ class MergeCamGroups:
         rep.update(choice=choice, match_counts=cnt, job_of_entry=job_of, matches_ptr=matcher.matches_ptr(k))
         return rep
 
+    def run_from_descriptors(self, front, front_cams, matcher, match_cams, Ws, Hs, infos, history, tables, groups, key_frames, self_motion,
+                             key_groups, pixelErrVar, ratio=0.8, max_dist=0.6, n_ransac=200, max_epi_err=2.0, min_inlier_num=15, seed=0,
+                             epi_max=20.0, ncc_min=0.45, max_disp=150.0, last_release_frame=None, n_max_keyfrm=100, stream_ptr=None):
+        """mergeCamGroups from the gate's list and the key frames' key points + descriptors: MergeFront.run over every entry's camera pair
+        (matchSURFPoints, computeEMat, getMatchedPts; DESIGN 3.25), then run_from_seeds with what it returned.  front: a MergeFront;
+        front_cams: per camera dict(pts, desc: device pointers, n, K).  E and the seeds pass through the front's one read-back (the matcher's
+        job table takes them from host memory).  -> run_from_seeds' dict, plus front (MergeFront.run's list)."""
+        import torch
+
+        s = torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        got = front.run(front_cams, [(int(inf[1]), int(inf[4])) for inf in infos], ratio, max_dist, n_ransac, max_epi_err, min_inlier_num, seed,
+                        stream_ptr=s)
+        rep = self.run_from_seeds(matcher, match_cams, Ws, Hs, infos, [g["surf_num"] for g in got], [g["emat_ok"] for g in got],
+                                  [dict(E=g["E"], seeds=g["seeds"]) for g in got], history, tables, groups, key_frames, self_motion,
+                                  key_groups, pixelErrVar, epi_max=epi_max, ncc_min=ncc_min, max_disp=max_disp,
+                                  last_release_frame=last_release_frame, n_max_keyfrm=n_max_keyfrm, stream_ptr=s)
+        rep["front"] = got
+        return rep
+
     def close(self):
         if self.ma is not None:
             self.ma.close()
@@ -850,3 +869,186 @@ def ncc_small_image_dev(stream_ptr, d_img, W, H, scale, d_small, device=0):
     check(lib().cs_ncc_small_image_dev(int(device), C.c_void_p(stream_ptr), C.c_void_p(d_img), int(W), int(H), C.c_double(scale), C.c_void_p(d_small)),
           "cs_ncc_small_image_dev")
     return ws.value, hs.value
+
+
+MERGE_FRONT_MAX_JOBS = 256
+MERGE_FRONT_TOO_FEW, MERGE_FRONT_NO_MODEL = 1, 2
+
+
+class MergeFrontCam(C.Structure):
+    """== cs_merge_front_cam (include/coslam_hip.h): pts / desc device pointers, K a HOST pointer."""
+
+    _fields_ = [("pts", C.c_void_p), ("desc", C.c_void_p), ("K", C.c_void_p), ("n", C.c_int)]
+
+
+class MergeFrontJob(C.Structure):
+    """== cs_merge_front_job."""
+
+    _fields_ = [("iCam", C.c_int), ("jCam", C.c_int)]
+
+
+class MergeFrontResult(C.Structure):
+    """== cs_merge_front_result."""
+
+    _fields_ = [(n, C.c_int) for n in ("surfNum", "ematOk", "inlierNum", "rounds", "bestHyp", "flags")] + [("E", C.c_double * 9), ("epiErr", C.c_double)]
+
+
+class MergeFrontBuffers(C.Structure):
+    """== cs_merge_front_buffers."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("matches", "dist", "count", "inlierFlag", "seeds", "newMatches", "results", "hypSample", "hypCount",
+                                          "hypE", "pix", "valid")] + [(n, C.c_int) for n in ("nCams", "maxPts", "dimDesc", "maxJobs", "maxHyp")]
+
+
+class MergeFront:
+    """cs_merge_front: the front of matchMergableCameras on the device -- matchSurf over the descriptors of every candidate camera pair, the
+    RANSAC of estimateEMat with its local refit, the inliers' seed rows.  From key points + descriptors to what MergeMatcher.run
+    and merge_match_select take per job: E, seeds, surf_num, emat_ok."""
+
+    def __init__(self, n_cams, max_pts, dim_desc, max_jobs, max_hyp, device=0):
+        L = lib()
+        L.cs_merge_front_create.restype = C.c_void_p
+        self._L, self.device, self.n_cams, self.max_pts, self.dim = L, int(device), int(n_cams), int(max_pts), int(dim_desc)
+        self.max_jobs, self.max_hyp = int(max_jobs), int(max_hyp)
+        self._m = L.cs_merge_front_create(self.device, self.n_cams, self.max_pts, self.dim, self.max_jobs, self.max_hyp)
+        if not self._m:
+            check(-1, "cs_merge_front_create")
+        self.buf = MergeFrontBuffers()
+        check(L.cs_merge_front_buffers_get(C.c_void_p(self._m), C.byref(self.buf)), "cs_merge_front_buffers_get")
+
+    def _stream(self, stream_ptr):
+        import torch
+
+        return torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+
+    def _tables(self, cams, pairs):
+        import numpy as np
+
+        if len(cams) != self.n_cams:
+            raise ValueError(f"MergeFront: {len(cams)} cameras, the handle has {self.n_cams}")
+        ca, keep = (MergeFrontCam * max(len(cams), 1))(), []
+        for a, c in zip(ca, cams):
+            K = np.ascontiguousarray(c["K"], dtype=np.float64).reshape(9)
+            keep.append(K)
+            a.pts, a.desc, a.K, a.n = int(c["pts"]) or None, int(c.get("desc") or 0) or None, K.ctypes.data, int(c["n"])
+        ja = (MergeFrontJob * max(len(pairs), 1))()
+        for a, (i, j) in zip(ja, pairs):
+            a.iCam, a.jCam = int(i), int(j)
+        return ca, ja, keep
+
+    def enqueue(self, cams, pairs, ratio=0.8, max_dist=0.6, n_ransac=200, max_epi_err=2.0, min_inlier_num=15, seed=0, stream_ptr=None):
+        """cs_merge_front_run_dev.  cams: per camera a dict pts [n][2] f64, desc [n][dim] f32 (device pointers), n, K (9 doubles, HOST array);
+        pairs: [(iCam, jCam)].  The defaults are the reference's call (0.8, 0.6; 200, 2.0, 15).  Enqueues only."""
+        vp = C.c_void_p
+        ca, ja, _keep = self._tables(cams, pairs)
+        check(self._L.cs_merge_front_run_dev(vp(self._m), vp(self._stream(stream_ptr)), ca, len(pairs), ja if len(pairs) else None,
+                                             C.c_double(ratio), C.c_double(max_dist), int(n_ransac), C.c_double(max_epi_err),
+                                             int(min_inlier_num), C.c_ulonglong(int(seed))), "cs_merge_front_run_dev")
+
+    def match(self, cams, pairs, ratio=0.8, max_dist=0.6, stream_ptr=None):
+        """cs_merge_front_match_dev: the descriptor stage alone.  Enqueues only."""
+        vp = C.c_void_p
+        ca, ja, _keep = self._tables(cams, pairs)
+        check(self._L.cs_merge_front_match_dev(vp(self._m), vp(self._stream(stream_ptr)), ca, len(pairs), ja if len(pairs) else None,
+                                               C.c_double(ratio), C.c_double(max_dist)), "cs_merge_front_match_dev")
+
+    def from_matches(self, cams, pairs, matches, n_ransac=200, max_epi_err=2.0, min_inlier_num=15, seed=0, stream_ptr=None):
+        """cs_merge_front_from_matches_dev: the RANSAC stage alone (computeEMat's shape); matches: per job a host int [n][2].  Enqueues only."""
+        import numpy as np
+
+        vp = C.c_void_p
+        ca, ja, _keep = self._tables(cams, pairs)
+        ms = [np.ascontiguousarray(np.asarray(m, dtype=np.int32).reshape(-1, 2)) for m in matches]
+        n = len(pairs)
+        if len(ms) != n:
+            raise ValueError("MergeFront.from_matches: one match list per job")
+        mp = (vp * max(n, 1))(*[vp(m.ctypes.data) if len(m) else None for m in ms])
+        nm = (C.c_int * max(n, 1))(*[len(m) for m in ms])
+        check(self._L.cs_merge_front_from_matches_dev(vp(self._m), vp(self._stream(stream_ptr)), ca, n, ja if n else None, mp, nm, int(n_ransac),
+                                                      C.c_double(max_epi_err), int(min_inlier_num), C.c_ulonglong(int(seed))),
+              "cs_merge_front_from_matches_dev")
+
+    def results(self, n_jobs, stream_ptr=None):
+        """cs_merge_front_results: the stage's one host wait -> [dict(surf_num, emat_ok, inlier_num, rounds, best_hyp, flags, E [9], epi_err)]"""
+        import numpy as np
+
+        arr = (MergeFrontResult * max(int(n_jobs), 1))()
+        check(self._L.cs_merge_front_results(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), int(n_jobs), arr), "cs_merge_front_results")
+        return [dict(surf_num=int(r.surfNum), emat_ok=int(r.ematOk), inlier_num=int(r.inlierNum), rounds=int(r.rounds), best_hyp=int(r.bestHyp),
+                     flags=int(r.flags), E=np.array(list(r.E)), epi_err=float(r.epiErr)) for r in arr[:int(n_jobs)]]
+
+    def run(self, cams, pairs, ratio=0.8, max_dist=0.6, n_ransac=200, max_epi_err=2.0, min_inlier_num=15, seed=0, stream_ptr=None):
+        """enqueue + results + the seed rows of every job -> per job what MergeCamGroups.run_from_seeds takes: dict(E, seeds [inlier_num][4],
+        surf_num, emat_ok) (plus the rest of the result record)"""
+        self.enqueue(cams, pairs, ratio, max_dist, n_ransac, max_epi_err, min_inlier_num, seed, stream_ptr)
+        import numpy as np
+
+        out = self.results(len(pairs), stream_ptr)
+        rows = self._down(self.buf.seeds, 4 * self.max_pts * len(pairs), np.float64, stream_ptr).reshape(len(pairs), self.max_pts, 4)
+        for k, r in enumerate(out):      # (one download for every job's rows)
+            r["seeds"] = np.ascontiguousarray(rows[k, :r["inlier_num"]])
+        return out
+
+    def _down(self, ptr, n, dtype, stream_ptr=None):
+        import numpy as np
+
+        out = np.zeros(n, dtype)
+        if out.nbytes:
+            check(self._L.cs_merge_front_download(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(ptr),
+                                                  C.c_void_p(out.ctypes.data), C.c_size_t(out.nbytes)), "cs_merge_front_download")
+        return out
+
+    def counts(self, n_jobs, stream_ptr=None):
+        """matchSurf's count of jobs 0 .. n_jobs - 1; waits"""
+        import numpy as np
+
+        return self._down(self.buf.count, int(n_jobs), np.int32, stream_ptr)
+
+    def matches(self, job, count, stream_ptr=None):
+        """-> (int32 [count][2] in ascending i, float32 [count] distances) of one job; waits"""
+        import numpy as np
+
+        return self._down(int(self.buf.matches) + 8 * self.max_pts * int(job), 2 * int(count), np.int32, stream_ptr).reshape(-1, 2), \
+            self._down(int(self.buf.dist) + 4 * self.max_pts * int(job), int(count), np.float32, stream_ptr)
+
+    def inlier_flags(self, job, count, stream_ptr=None):
+        import numpy as np
+
+        return self._down(int(self.buf.inlierFlag) + self.max_pts * int(job), int(count), np.uint8, stream_ptr)
+
+    def seeds(self, job, count, stream_ptr=None):
+        """-> float64 [count][4] rows {x1, y1, x2, y2} of the inliers in match order; waits"""
+        import numpy as np
+
+        return self._down(int(self.buf.seeds) + 32 * self.max_pts * int(job), 4 * int(count), np.float64, stream_ptr).reshape(-1, 4)
+
+    def new_matches(self, job, count, stream_ptr=None):
+        import numpy as np
+
+        return self._down(int(self.buf.newMatches) + 8 * self.max_pts * int(job), 2 * int(count), np.int32, stream_ptr).reshape(-1, 2)
+
+    def hypotheses(self, slot, n_hyp, stream_ptr=None):
+        """the hypotheses at batch slot `slot` of the last batch -> (int32 [n_hyp][8] samples, int32 [n_hyp] counts, float64 [n_hyp][9]); waits"""
+        import numpy as np
+
+        b, h = self.max_hyp * int(slot), int(n_hyp)
+        return self._down(int(self.buf.hypSample) + 32 * b, 8 * h, np.int32, stream_ptr).reshape(-1, 8), \
+            self._down(int(self.buf.hypCount) + 4 * b, h, np.int32, stream_ptr), \
+            self._down(int(self.buf.hypE) + 72 * b, 9 * h, np.float64, stream_ptr).reshape(-1, 9)
+
+    def point_rows(self, slot, count, stream_ptr=None):
+        """the rows {x1, y1, x2, y2} of every match at batch slot `slot`; waits"""
+        import numpy as np
+
+        return self._down(int(self.buf.pix) + 32 * self.max_pts * int(slot), 4 * int(count), np.float64, stream_ptr).reshape(-1, 4)
+
+    def close(self):
+        if self._m:
+            self._L.cs_merge_front_destroy(C.c_void_p(self._m))
+            self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

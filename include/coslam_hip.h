@@ -1308,6 +1308,81 @@ typedef struct {
 int cs_merge_match_select(int nInfo, const cs_merge_info* info, const int* surfNum, const unsigned char* ematOk, const int* nccNum,
                           const unsigned char* eligible, const int* groupSize, cs_merge_match_choice* out);
 
+/* ---- the merge front: matchSURFPoints -> computeEMat -> getMatchedPts of matchMergableCameras (src/app/SL_MergeCameraGroup.cpp:360-378);
+ * DESIGN.md 3.25 ----
+ * From per-camera key points + descriptors (SURF detection stays outside) to what cs_merge_match_run_dev and cs_merge_match_select take per
+ * candidate camera pair (a JOB): E, the seed rows, surfNum, ematOk.  matchSurf / estimateEMat / evaluateEMat are un-vendored: OUR definitions,
+ * DESIGN.md 5.1 (restated in numpy by tests/mergefront_ref.py).  Per camera (host array): pts n x 2 doubles {x, y} and desc n x dimDesc
+ * floats in DEVICE memory, n, K as 9 doubles in HOST memory (iK is formed on the host by cs_merge_match_fmat's mat33Inv).
+ * cs_merge_front_run_dev enqueues on hip_stream, with no host wait in between:
+ *   valid       a point takes part iff its key point is finite and within 1e6 px and its descriptor is finite
+ *   matchSurf   (ratio, maxDist; the reference: 0.8, 0.6) brute force in f32, direct differences; nearest j (the lowest of equals) and the
+ *               second-nearest distance; accepted iff d1 < maxDist && d1 < ratio d2; one-to-one by an integer minimum of {f32 bits of d1, i}
+ *               per column; matches in ascending i
+ *   estimateEMat (nRansac, maxEpiErr, minInlierNum; the reference: 200, 2.0, 15) hypotheses from a counter-based generator (seed, job k,
+ *               hypothesis h, draw), the normalised eight-point solve in f64, evaluateEMat's count of every hypothesis over all matches,
+ *               the best by one integer maximum of {count, ~h}, at most 4 rounds of refit over all inliers (kept iff the count did not fall)
+ *   seeds       getMatchedPts of the inliers (newMatches), rows {x1, y1, x2, y2}
+ * Jobs beyond maxJobs run in batches of maxJobs on the same stream; job k's generator stream does not depend on the batching.  The job
+ * tables are uploaded from staging copies the handle keeps: a call first waits for the stream of the handle's PREVIOUS call if that left
+ * such copies (the one wait in front of the stage; none inside it).  Results are the same bits from run to run.
+ * Out, per job k < CS_MERGE_FRONT_MAX_JOBS, in device memory: matches [k][maxPts][2] (point of iCam, point of jCam), dist [k][maxPts] (f32),
+ * count [k], inlierFlag [k][maxPts], seeds [k][maxPts][4], newMatches [k][maxPts][2], results [k].  Of the LAST batch, per batch slot:
+ * hypSample [slot][maxHyp][8] (all -1: the draws ran out), hypCount [slot][maxHyp], hypE [slot][maxHyp][9] (0: no model), pix
+ * [slot][maxPts][4] (the point rows of every match).  Flags: CS_MERGE_FRONT_TOO_FEW (fewer than 8 matches: ematOk 0, nothing solved),
+ * CS_MERGE_FRONT_NO_MODEL (no hypothesis has an inlier).
+ * CS_ERR_INVALID before any launch (cs_last_error text): null handle / table, camera ids outside the rig, iCam == jCam, n > maxPts,
+ * nRansac < 1 or > maxHyp, a singular K, more than CS_MERGE_FRONT_MAX_JOBS jobs (cs_merge_front_from_matches_dev: more than maxJobs);
+ * creation: nCams 1..16, maxPts 1..32768, dimDesc 1..128, maxJobs 1..256, maxHyp 1..65536. */
+#define CS_MERGE_FRONT_MAX_JOBS 256
+enum { CS_MERGE_FRONT_TOO_FEW = 1, CS_MERGE_FRONT_NO_MODEL = 2 };
+typedef struct {
+    const double* pts;                /* device, [n][2] */
+    const float* desc;                /* device, [n][dimDesc] */
+    const double* K;                  /* HOST, 9 */
+    int n;
+} cs_merge_front_cam;
+typedef struct { int iCam, jCam; } cs_merge_front_job;
+typedef struct {
+    int surfNum, ematOk, inlierNum, rounds /* refit rounds kept */, bestHyp /* -1: none */, flags;
+    double E[9];
+    double epiErr;                    /* mean error of the inliers */
+} cs_merge_front_result;
+typedef struct {
+    const int* matches;               /* [CS_MERGE_FRONT_MAX_JOBS][maxPts][2] */
+    const float* dist;                /* [CS_MERGE_FRONT_MAX_JOBS][maxPts] */
+    const int* count;                 /* [CS_MERGE_FRONT_MAX_JOBS] */
+    const unsigned char* inlierFlag;  /* [CS_MERGE_FRONT_MAX_JOBS][maxPts] */
+    const double* seeds;              /* [CS_MERGE_FRONT_MAX_JOBS][maxPts][4] */
+    const int* newMatches;            /* [CS_MERGE_FRONT_MAX_JOBS][maxPts][2] */
+    const cs_merge_front_result* results;  /* [CS_MERGE_FRONT_MAX_JOBS] */
+    const int* hypSample;             /* [maxJobs][maxHyp][8]: the LAST batch (job k of the batch at slot k) */
+    const int* hypCount;              /* [maxJobs][maxHyp] */
+    const double* hypE;               /* [maxJobs][maxHyp][9] */
+    const double* pix;                /* [maxJobs][maxPts][4] */
+    const int* valid;                 /* [nCams][maxPts] */
+    int nCams, maxPts, dimDesc, maxJobs, maxHyp;
+} cs_merge_front_buffers;
+typedef struct cs_merge_front cs_merge_front;
+cs_merge_front* cs_merge_front_create(int device, int nCams, int maxPts, int dimDesc, int maxJobs, int maxHyp);
+void cs_merge_front_destroy(cs_merge_front* mf);
+int cs_merge_front_run_dev(cs_merge_front* mf, void* hip_stream, const cs_merge_front_cam* cams /* host [nCams] */, int nJobs,
+                           const cs_merge_front_job* jobs /* host */, double ratio, double maxDist, int nRansac, double maxEpiErr,
+                           int minInlierNum, unsigned long long seed);
+/* the descriptor stage alone: matches, dist, count (and the point rows) of every job */
+int cs_merge_front_match_dev(cs_merge_front* mf, void* hip_stream, const cs_merge_front_cam* cams /* host [nCams] */, int nJobs,
+                             const cs_merge_front_job* jobs /* host */, double ratio, double maxDist);
+/* the RANSAC stage alone on the caller's match lists (computeEMat's shape): matches[k] HOST [nMatches[k]][2] point indices, copied by the
+ * call; desc may be NULL; a match that names a point outside its camera takes no part (its point row is NaN).  nJobs <= maxJobs. */
+int cs_merge_front_from_matches_dev(cs_merge_front* mf, void* hip_stream, const cs_merge_front_cam* cams /* host [nCams] */, int nJobs,
+                                    const cs_merge_front_job* jobs /* host */, const int* const* matches /* host array */,
+                                    const int* nMatches /* host */, int nRansac, double maxEpiErr, int minInlierNum, unsigned long long seed);
+/* the result records of jobs 0 .. nJobs - 1 in host memory: the stage's ONE host wait */
+int cs_merge_front_results(cs_merge_front* mf, void* hip_stream, int nJobs, cs_merge_front_result* h_out);
+int cs_merge_front_buffers_get(const cs_merge_front* mf, cs_merge_front_buffers* out);
+/* bytes of one of the handle's device buffers to the host; waits for hip_stream */
+int cs_merge_front_download(cs_merge_front* mf, void* hip_stream, const void* d_src, void* h_dst, size_t bytes);
+
 /* CoSLAM::mapPointsClassify (src/app/SL_CoSLAM.cpp:418-520) over the references: from the next call on cs_map_points_classify_dev and
  * cs_pose_update_classify_frame_dev read d_featRef ([nMap][nCams], the table cs_feat_ref_advance_dev keeps: as the END of the previous
  * frame left it, or already at this frame) next to d_pointFeat (this frame's features): a camera that lost the point still gives
