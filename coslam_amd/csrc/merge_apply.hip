@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "cs_common.h"
+#include "dev_arena.h"
 #include "project_dev.h"
 #include "triangulate_dev.h"
 #include "history_view.h"
@@ -356,22 +357,20 @@ extern "C" cs_merge_apply* cs_merge_apply_create(int device, int nCams, int nKey
         return nullptr;
     }
     const size_t nk = nNodes, ek = nEdges > 0 ? nEdges : 1, nc = a->nChainNodes, ec = a->nChainEdges > 0 ? a->nChainEdges : 1;
-    const size_t nD = 12 * nk * 2 + 12 * ek + ek + 12 * nc * 2 + 12 * ec;
-    const size_t nI = nk + ek + 2 + nKey;
-    if (hipMalloc((void**)&a->dev, 8 * nD + 4 * nI) != hipSuccess) {
+    size_t bytes;
+    const bool ok = cs_arena_alloc(device, a->dev, bytes, [&](CsArena& ar) {
+        ar.take(a->kR, 9 * nk), ar.take(a->kT, 3 * nk), ar.take(a->knR, 9 * nk), ar.take(a->knT, 3 * nk);
+        ar.take(a->keR, 9 * ek), ar.take(a->keT, 3 * ek), ar.take(a->keS, ek);
+        ar.take(a->cR, 9 * nc), ar.take(a->cT, 3 * nc), ar.take(a->cnR, 9 * nc), ar.take(a->cnT, 3 * nc);
+        ar.take(a->ceR, 9 * ec), ar.take(a->ceT, 3 * ec);
+        ar.take(a->keyNode, nk), ar.take(a->conRow, ek), ar.take(a->guard, 2), ar.take(a->keyFrames, nKey);
+    });
+    if (!ok) {
         cs_set_error("%s: hipMalloc failed", who);
         cs_merge_apply_destroy(a);
         return nullptr;
     }
-    double* d = (double*)a->dev;
-    a->kR = d, d += 9 * nk, a->kT = d, d += 3 * nk, a->knR = d, d += 9 * nk, a->knT = d, d += 3 * nk;
-    a->keR = d, d += 9 * ek, a->keT = d, d += 3 * ek, a->keS = d, d += ek;
-    a->cR = d, d += 9 * nc, a->cT = d, d += 3 * nc, a->cnR = d, d += 9 * nc, a->cnT = d, d += 3 * nc;
-    a->ceR = d, d += 9 * ec, a->ceT = d, d += 3 * ec;
-    int* q = (int*)d;
-    a->keyNode = q, q += nk, a->conRow = q, q += ek, a->guard = q, q += 2, a->keyFrames = q;
-    if (hipMemset(a->dev, 0, 8 * nD + 4 * nI) != hipSuccess ||
-        hipMemcpy(a->keyNode, keyNode.data(), 4 * nk, hipMemcpyHostToDevice) != hipSuccess ||
+    if (hipMemcpy(a->keyNode, keyNode.data(), 4 * nk, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(a->keyFrames, keyFrames, 4 * (size_t)nKey, hipMemcpyHostToDevice) != hipSuccess ||
         (!conRow.empty() && hipMemcpy(a->conRow, conRow.data(), 4 * conRow.size(), hipMemcpyHostToDevice) != hipSuccess)) {
         cs_set_error("%s: upload failed", who);

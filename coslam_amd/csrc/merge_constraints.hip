@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "cs_common.h"
+#include "dev_arena.h"
 #include "history_view.h"
 
 struct cs_merge_constraints {
@@ -27,11 +28,11 @@ struct cs_merge_constraints {
     int *slotView, *candKey, *candRank, *candPt, *unm;
     unsigned* isM1;
     int* matches;   // [maxMatches][2]: cs_merge_constraints_assemble's copy of a host list
+    CsStage stage;  // ... and the host side of that copy
     // cs_merge_constraints_apply_map_dev: winner tables (all -1 between calls) and the rows gathered from the pre-call table
     int *winSlot, *winRow, *winPt;   // [nCams][N], [maxMap][nCams], [maxMap]
     int4* gRef;                      // [maxViews]
     unsigned char* gStat;            // [maxViews]
-    std::vector<int> hMatches;
     // the two solves (:646-647): the problem on the host, the existing robust BA's workspace, both results
     cs_ba* ba;
     int solved;   // 0: no solve since the last assembly, 1: both solves succeeded, -1: a solve failed
@@ -576,9 +577,22 @@ __global__ __launch_bounds__(MC_T) void k_merge_apply_map(MmArgs A) {
     if (tid < 6 && A.counts) A.counts[tid] += s_cnt[tid];
 }
 
-size_t mc_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
+
+// the device block: the exported problem and lists, the assembly's work tables, the solve's results, the map update's tables
+static void mc_layout(cs_merge_constraints* mc, CsArena& ar) {
+    const size_t nM = mc->maxMatches, nP = mc->maxPoints, nO = mc->maxObs, nV = mc->maxViews, nS = (size_t)MC_MAX_CAMS * mc->N;
+    cs_merge_constraints_buffers& B = mc->b;
+    ar.take(B.header, 1), ar.take(B.views, nV), ar.take(B.Ks, 32 * 9), ar.take(B.Rs, 32 * 9), ar.take(B.Ts, 32 * 3), ar.take(B.pts, nP * 3);
+    ar.take(B.pointMap, nP), ar.take(B.obsPtr, nP + 1), ar.take(B.obsCam, nO), ar.take(B.obsXY, nO * 2);
+    ar.take(B.info, MC_MAX_INFO), ar.take(B.infoValid, MC_MAX_INFO), ar.take(B.infoR, MC_MAX_INFO * 9), ar.take(B.infoT, MC_MAX_INFO * 3);
+    ar.take(mc->trk, nM), ar.take(mc->slotView, nS), ar.take(mc->candKey, nS), ar.take(mc->candRank, nS), ar.take(mc->candPt, nS);
+    ar.take(mc->unm, 20 * nM), ar.take(mc->isM1, ((size_t)mc->maxMap + 31) / 32);
+    ar.take(B.solvedRs, 32 * 9), ar.take(B.solvedTs, 32 * 3), ar.take(B.solvedPts, nP * 3), ar.take(B.outlier, nO);
+    ar.take(mc->matches, nM * 2);
+    ar.take(mc->winSlot, (size_t)mc->nCams * mc->N), ar.take(mc->winRow, (size_t)mc->maxMap * mc->nCams), ar.take(mc->winPt, mc->maxMap);
+    ar.take(mc->gRef, nV), ar.take(mc->gStat, nV);
+}
 
 extern "C" cs_merge_constraints* cs_merge_constraints_create(int device, int nCams, int N, int maxMatches, int maxMap) {
     if (nCams < 1 || nCams > MC_MAX_CAMS || N < 1 || maxMatches < 1 || maxMap < 1 || maxMatches > (1 << 20) / 21) {
@@ -588,35 +602,16 @@ extern "C" cs_merge_constraints* cs_merge_constraints_create(int device, int nCa
     cs_merge_constraints* mc = new cs_merge_constraints();
     mc->device = device, mc->nCams = nCams, mc->N = N, mc->maxMatches = maxMatches, mc->maxMap = maxMap;
     mc->maxPoints = 21 * maxMatches, mc->maxObs = 32 * mc->maxPoints, mc->maxViews = 32 * maxMatches;
-    const size_t nP = mc->maxPoints, nO = mc->maxObs, nV = mc->maxViews, nS = (size_t)MC_MAX_CAMS * N;
-    const size_t sizes[] = {sizeof(cs_merge_constraints_header), nV * sizeof(cs_merge_view), 32 * 9 * 8, 32 * 9 * 8, 32 * 3 * 8, nP * 24, nP * 4, (nP + 1) * 4,
-                            nO * 4, nO * 16, MC_MAX_INFO * sizeof(cs_merge_info), MC_MAX_INFO, MC_MAX_INFO * 72, MC_MAX_INFO * 24,
-                            (size_t)maxMatches * sizeof(int4), nS * 4, nS * 4, nS * 4, nS * 4, 20 * (size_t)maxMatches * 4, ((size_t)maxMap + 31) / 32 * 4,
-                            32 * 9 * 8, 32 * 3 * 8, nP * 24, nO * 4, (size_t)maxMatches * 8,
-                            (size_t)nCams * N * 4, (size_t)maxMap * nCams * 4, (size_t)maxMap * 4, nV * sizeof(int4), nV};
-    size_t off[sizeof(sizes) / sizeof(sizes[0]) + 1] = {0};
-    for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) off[i + 1] = off[i] + mc_align(sizes[i]);
-    const size_t total = off[sizeof(sizes) / sizeof(sizes[0])];
-    if (hipSetDevice(device) != hipSuccess || hipMalloc((void**)&mc->base, total) != hipSuccess || hipMemset(mc->base, 0, total) != hipSuccess) {
-        cs_set_error("cs_merge_constraints_create: %zu bytes of device memory: %s", total, hipGetErrorString(hipGetLastError()));
+    if (!cs_arena_alloc(device, mc->base, mc->bytes, [mc](CsArena& ar) { mc_layout(mc, ar); })) {
+        cs_set_error("cs_merge_constraints_create: %zu bytes of device memory: %s", mc->bytes, hipGetErrorString(hipGetLastError()));
         delete mc;
         return nullptr;
     }
-    mc->bytes = total;
-    char* b = mc->base;
     cs_merge_constraints_buffers& B = mc->b;
-    B.header = (cs_merge_constraints_header*)(b + off[0]), B.views = (cs_merge_view*)(b + off[1]);
-    B.Ks = (double*)(b + off[2]), B.Rs = (double*)(b + off[3]), B.Ts = (double*)(b + off[4]), B.pts = (double*)(b + off[5]);
-    B.pointMap = (int*)(b + off[6]), B.obsPtr = (int*)(b + off[7]), B.obsCam = (int*)(b + off[8]), B.obsXY = (double*)(b + off[9]);
-    B.info = (cs_merge_info*)(b + off[10]), B.infoValid = (unsigned char*)(b + off[11]), B.infoR = (double*)(b + off[12]), B.infoT = (double*)(b + off[13]);
     B.maxPoints = mc->maxPoints, B.maxObs = mc->maxObs, B.maxViews = mc->maxViews, B.maxInfo = MC_MAX_INFO;
-    mc->trk = (int4*)(b + off[14]), mc->slotView = (int*)(b + off[15]), mc->candKey = (int*)(b + off[16]), mc->candRank = (int*)(b + off[17]);
-    mc->candPt = (int*)(b + off[18]), mc->unm = (int*)(b + off[19]), mc->isM1 = (unsigned*)(b + off[20]);
-    B.solvedRs = (double*)(b + off[21]), B.solvedTs = (double*)(b + off[22]), B.solvedPts = (double*)(b + off[23]), B.outlier = (int*)(b + off[24]);
-    mc->matches = (int*)(b + off[25]);
-    mc->winSlot = (int*)(b + off[26]), mc->winRow = (int*)(b + off[27]), mc->winPt = (int*)(b + off[28]);
-    mc->gRef = (int4*)(b + off[29]), mc->gStat = (unsigned char*)(b + off[30]);
-    if (hipMemset(mc->winSlot, 0xFF, off[29] - off[26]) != hipSuccess) {   // the three winner tables: -1 once, every call restores what it named
+    // the three winner tables: -1 once, every call restores what it named
+    if (hipMemset(mc->winSlot, 0xFF, 4 * (size_t)nCams * N) != hipSuccess || hipMemset(mc->winRow, 0xFF, 4 * (size_t)maxMap * nCams) != hipSuccess ||
+        hipMemset(mc->winPt, 0xFF, 4 * (size_t)maxMap) != hipSuccess) {
         cs_set_error("cs_merge_constraints_create: %s", hipGetErrorString(hipGetLastError()));
         (void)hipFree(mc->base);
         delete mc;
@@ -629,7 +624,11 @@ extern "C" cs_merge_constraints* cs_merge_constraints_create(int device, int nCa
 extern "C" void cs_merge_constraints_destroy(cs_merge_constraints* mc) {
     if (!mc) return;
     if (mc->ba) cs_ba_destroy(mc->ba);
-    if (mc->base) (void)hipFree(mc->base);
+    if (mc->base) {
+        (void)hipSetDevice(mc->device);
+        mc->stage.drain();   // (the upload of the last assembly may still read its staging copy)
+        (void)hipFree(mc->base);
+    }
     delete mc;
 }
 
@@ -698,9 +697,9 @@ extern "C" int cs_merge_constraints_assemble(cs_merge_constraints* mc, const cs_
     }
     if (nMatches > 0) {
         CS_HIP(hipSetDevice(mc->device));
-        CS_HIP(hipStreamSynchronize((hipStream_t)hip_stream));   // (an earlier launch may still read the table; the staging copy is the handle's)
-        mc->hMatches.assign(h_matches, h_matches + 2 * (size_t)nMatches);
-        CS_HIP(hipMemcpyAsync(mc->matches, mc->hMatches.data(), 8 * (size_t)nMatches, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
+        int rc = mc->stage.begin((hipStream_t)hip_stream);
+        if (rc == CS_OK) rc = mc->stage.upload((hipStream_t)hip_stream, mc->matches, h_matches, 8 * (size_t)nMatches);
+        if (rc != CS_OK) return rc;
     }
     return cs_merge_constraints_assemble_dev(mc, h, hip_stream, cams, d_featRef, nMap, d_mapPts, d_groups, gId1, gId2, maxiCam, maxjCam, f1, f2,
                                              mc->matches, nMatches);
@@ -743,15 +742,8 @@ extern "C" int cs_merge_constraints_header_get(cs_merge_constraints* mc, void* h
 }
 
 extern "C" int cs_merge_constraints_download(cs_merge_constraints* mc, void* hip_stream, const void* d_src, void* h_dst, size_t bytes) {
-    const char* s = (const char*)d_src;
-    if (!mc || !d_src || !h_dst || s < mc->base || bytes > mc->bytes || s + bytes > mc->base + mc->bytes) {
-        cs_set_error("cs_merge_constraints_download: the range is not inside the handle's buffers");
-        return CS_ERR_INVALID;
-    }
-    CS_HIP(hipSetDevice(mc->device));
-    CS_HIP(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-    CS_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
-    return CS_OK;
+    return cs_arena_download("cs_merge_constraints_download", mc ? mc->device : 0, mc ? mc->base : nullptr, mc ? mc->bytes : 0, hip_stream, d_src,
+                             h_dst, bytes);
 }
 
 // ---- the two solves of :646-647: bundleAdjustRobust(1, ..., 1, ..., 800, 1, 100), then (..., 30, 5, 30) from the first one's result.

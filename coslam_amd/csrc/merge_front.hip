@@ -22,6 +22,8 @@
 #include <vector>
 
 #include "cs_common.h"
+#include "dev_arena.h"
+#include "host33.h"
 
 #pragma clang fp contract(off)
 
@@ -605,8 +607,6 @@ __global__ __launch_bounds__(MF_T) void k_mf_refit(MfArgs A) {
     }
 }
 
-inline size_t mf_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 struct cs_merge_front {
@@ -617,9 +617,19 @@ struct cs_merge_front {
     int* valid;      // [nCams][maxPts]
     MfJob* jobs;     // [maxJobs]
     MfArgs args;     // the tables (jobs and the call's parameters are set per launch)
-    std::vector<std::vector<char>> stage;   // the host side of the uploads a call enqueued, alive until the next call has waited
-    hipStream_t stageStream;                // ... for the stream they were enqueued on
+    CsStage stage;
 };
+
+// the device block: per camera, per batch slot, per hypothesis of a slot, per job
+static void mf_layout(cs_merge_front* mf, CsArena& ar) {
+    const size_t nS = (size_t)mf->maxJobs * mf->maxPts, nH = (size_t)mf->maxJobs * mf->maxHyp, nJ = CS_MERGE_FRONT_MAX_JOBS, nO = nJ * mf->maxPts;
+    MfArgs& A = mf->args;
+    ar.take(mf->valid, (size_t)mf->nCams * mf->maxPts), ar.take(mf->jobs, mf->maxJobs);
+    ar.take(A.rowJ, nS), ar.take(A.rowD, nS), ar.take(A.colBest, nS), ar.take(A.pix, nS * 4), ar.take(A.nrm, nS * 4), ar.take(A.flagTmp, nS);
+    ar.take(A.hypSample, nH * 8), ar.take(A.hypCount, nH), ar.take(A.hypE, nH * 9), ar.take(A.best, mf->maxJobs);
+    ar.take(A.matches, nO * 2), ar.take(A.dist, nO), ar.take(A.count, nJ), ar.take(A.inlierFlag, nO), ar.take(A.seeds, nO * 4);
+    ar.take(A.newMatches, nO * 2), ar.take(A.results, nJ);
+}
 
 extern "C" cs_merge_front* cs_merge_front_create(int device, int nCams, int maxPts, int dimDesc, int maxJobs, int maxHyp) {
     if (nCams < 1 || nCams > MF_MAX_CAMS || maxPts < 1 || maxPts > MF_MAX_PTS || dimDesc < 1 || dimDesc > MF_MAX_DIM || maxJobs < 1 ||
@@ -630,31 +640,13 @@ extern "C" cs_merge_front* cs_merge_front_create(int device, int nCams, int maxP
     }
     cs_merge_front* mf = new cs_merge_front();
     mf->device = device, mf->nCams = nCams, mf->maxPts = maxPts, mf->dim = dimDesc, mf->maxJobs = maxJobs, mf->maxHyp = maxHyp;
-    const size_t nS = (size_t)maxJobs * maxPts, nH = (size_t)maxJobs * maxHyp, nO = (size_t)CS_MERGE_FRONT_MAX_JOBS * maxPts;
-    const size_t sizes[] = {(size_t)nCams * maxPts * 4, (size_t)maxJobs * sizeof(MfJob),                   // 0 valid, jobs
-                            nS * 4, nS * 4, nS * 8, nS * 32, nS * 32, nS,                                   // 2 rowJ rowD colBest pix nrm flagTmp
-                            nH * 32, nH * 4, nH * 72, (size_t)maxJobs * 8,                                  // 8 hypSample hypCount hypE best
-                            nO * 8, nO * 4, (size_t)CS_MERGE_FRONT_MAX_JOBS * 4, nO, nO * 32, nO * 8,       // 12 matches dist count inlierFlag seeds newMatches
-                            (size_t)CS_MERGE_FRONT_MAX_JOBS * sizeof(cs_merge_front_result)};               // 18 results
-    constexpr int NS = sizeof(sizes) / sizeof(sizes[0]);
-    size_t off[NS + 1] = {0};
-    for (int i = 0; i < NS; ++i) off[i + 1] = off[i] + mf_align(sizes[i]);
-    const size_t total = off[NS];
-    if (hipSetDevice(device) != hipSuccess || hipMalloc((void**)&mf->base, total) != hipSuccess || hipMemset(mf->base, 0, total) != hipSuccess) {
-        cs_set_error("cs_merge_front_create: %zu bytes of device memory: %s", total, hipGetErrorString(hipGetLastError()));
+    MfArgs& A = mf->args;
+    memset(&A, 0, sizeof(A));
+    if (!cs_arena_alloc(device, mf->base, mf->bytes, [mf](CsArena& ar) { mf_layout(mf, ar); })) {
+        cs_set_error("cs_merge_front_create: %zu bytes of device memory: %s", mf->bytes, hipGetErrorString(hipGetLastError()));
         delete mf;
         return nullptr;
     }
-    mf->bytes = total, mf->stageStream = nullptr;
-    char* b = mf->base;
-    MfArgs& A = mf->args;
-    memset(&A, 0, sizeof(A));
-    mf->valid = (int*)(b + off[0]), mf->jobs = (MfJob*)(b + off[1]);
-    A.rowJ = (int*)(b + off[2]), A.rowD = (float*)(b + off[3]), A.colBest = (mf_u64*)(b + off[4]), A.pix = (double*)(b + off[5]);
-    A.nrm = (double*)(b + off[6]), A.flagTmp = (unsigned char*)(b + off[7]);
-    A.hypSample = (int*)(b + off[8]), A.hypCount = (int*)(b + off[9]), A.hypE = (double*)(b + off[10]), A.best = (mf_u64*)(b + off[11]);
-    A.matches = (int*)(b + off[12]), A.dist = (float*)(b + off[13]), A.count = (int*)(b + off[14]), A.inlierFlag = (unsigned char*)(b + off[15]);
-    A.seeds = (double*)(b + off[16]), A.newMatches = (int*)(b + off[17]), A.results = (cs_merge_front_result*)(b + off[18]);
     A.maxPts = maxPts, A.dim = dimDesc, A.maxHyp = maxHyp;
     cs_merge_front_buffers& B = mf->b;
     B.matches = A.matches, B.dist = A.dist, B.count = A.count, B.inlierFlag = A.inlierFlag, B.seeds = A.seeds, B.newMatches = A.newMatches;
@@ -667,7 +659,7 @@ extern "C" void cs_merge_front_destroy(cs_merge_front* mf) {
     if (!mf) return;
     if (mf->base) {
         (void)hipSetDevice(mf->device);
-        (void)hipDeviceSynchronize();   // (an upload of the last call may still read mf->stage)
+        mf->stage.drain();   // (an upload of the last call may still read its staging copy)
         (void)hipFree(mf->base);
     }
     delete mf;
@@ -699,7 +691,6 @@ int mf_check(const char* who, cs_merge_front* mf, const cs_merge_front_cam* cams
         return CS_ERR_INVALID;
     }
     double iK[MF_MAX_CAMS][9];
-    static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     for (int c = 0; c < mf->nCams; ++c) {
         if (cams[c].n < 0 || cams[c].n > mf->maxPts) {
             cs_set_error("%s: camera %d: %d points, the handle holds %d", who, c, cams[c].n, mf->maxPts);
@@ -709,8 +700,7 @@ int mf_check(const char* who, cs_merge_front* mf, const cs_merge_front_cam* cams
             cs_set_error("%s: camera %d: null pts / desc / K", who, c);
             return CS_ERR_INVALID;
         }
-        // mat33Inv is cs_merge_match_fmat's: with K1 = E = I its F = I^T I^T iK2 is iK2 itself (products with 0 and 1 only)
-        if (cs_merge_match_fmat(I3, cams[c].K, I3, iK[c]) != CS_OK) {
+        if (!cs_host_inv33(cams[c].K, iK[c])) {
             cs_set_error("%s: camera %d: singular K", who, c);
             return CS_ERR_INVALID;
         }
@@ -729,24 +719,6 @@ int mf_check(const char* who, cs_merge_front* mf, const cs_merge_front_cam* cams
         J.n1 = cams[a].n, J.n2 = cams[b].n, J.out = k;
         memcpy(J.iK1, iK[a], sizeof(J.iK1)), memcpy(J.iK2, iK[b], sizeof(J.iK2));
     }
-    return CS_OK;
-}
-
-int mf_begin(cs_merge_front* mf, hipStream_t s) {
-    CS_HIP(hipSetDevice(mf->device));
-    if (!mf->stage.empty()) {   // an upload of the previous call may still read its staging copy: wait for THAT call's stream
-        CS_HIP(hipStreamSynchronize(mf->stageStream));
-        mf->stage.clear();
-    }
-    mf->stageStream = s;
-    return CS_OK;
-}
-
-int mf_upload(cs_merge_front* mf, hipStream_t s, void* d_dst, const void* h_src, size_t bytes) {
-    if (!bytes) return CS_OK;
-    mf->stage.emplace_back(bytes);
-    memcpy(mf->stage.back().data(), h_src, bytes);
-    CS_HIP(hipMemcpyAsync(d_dst, mf->stage.back().data(), bytes, hipMemcpyHostToDevice, s));
     return CS_OK;
 }
 
@@ -801,11 +773,12 @@ int mf_run(const char* who, cs_merge_front* mf, void* hip_stream, const cs_merge
     int rc = mf_check(who, mf, cams, nJobs, jobs, CS_MERGE_FRONT_MAX_JOBS, true, ransac ? &P : nullptr, all);
     if (rc != CS_OK || nJobs == 0) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
-    if ((rc = mf_begin(mf, s)) != CS_OK || (rc = mf_valid(mf, s, cams)) != CS_OK) return rc;
+    CS_HIP(hipSetDevice(mf->device));
+    if ((rc = mf->stage.begin(s)) != CS_OK || (rc = mf_valid(mf, s, cams)) != CS_OK) return rc;
     const MfArgs A = mf_args(mf, P);
     for (int k0 = 0; k0 < nJobs; k0 += mf->maxJobs) {   // a batch: the work tables are the batch's, the outputs are every job's
         const int nb = nJobs - k0 < mf->maxJobs ? nJobs - k0 : mf->maxJobs;
-        if ((rc = mf_upload(mf, s, mf->jobs, all.data() + k0, sizeof(MfJob) * (size_t)nb)) != CS_OK) return rc;
+        if ((rc = mf->stage.upload(s, mf->jobs, all.data() + k0, sizeof(MfJob) * (size_t)nb)) != CS_OK) return rc;
         if ((rc = mf_match_batch(mf, s, nb, all.data() + k0, A)) != CS_OK) return rc;
         if (ransac && (rc = mf_ransac_batch(mf, s, nb, A)) != CS_OK) return rc;
     }
@@ -849,12 +822,13 @@ extern "C" int cs_merge_front_from_matches_dev(cs_merge_front* mf, void* hip_str
     }
     if (nJobs == 0) return CS_OK;
     hipStream_t s = (hipStream_t)hip_stream;
-    if ((rc = mf_begin(mf, s)) != CS_OK) return rc;
+    CS_HIP(hipSetDevice(mf->device));
+    if ((rc = mf->stage.begin(s)) != CS_OK) return rc;
     const MfArgs A = mf_args(mf, P);
-    if ((rc = mf_upload(mf, s, mf->jobs, all.data(), sizeof(MfJob) * (size_t)nJobs)) != CS_OK) return rc;
-    if ((rc = mf_upload(mf, s, A.count, nMatches, sizeof(int) * (size_t)nJobs)) != CS_OK) return rc;
+    if ((rc = mf->stage.upload(s, mf->jobs, all.data(), sizeof(MfJob) * (size_t)nJobs)) != CS_OK) return rc;
+    if ((rc = mf->stage.upload(s, A.count, nMatches, sizeof(int) * (size_t)nJobs)) != CS_OK) return rc;
     for (int k = 0; k < nJobs; ++k)
-        if ((rc = mf_upload(mf, s, A.matches + 2 * (size_t)k * mf->maxPts, matches[k], 8 * (size_t)nMatches[k])) != CS_OK) return rc;
+        if ((rc = mf->stage.upload(s, A.matches + 2 * (size_t)k * mf->maxPts, matches[k], 8 * (size_t)nMatches[k])) != CS_OK) return rc;
     if (nMax > 0) {
         hipLaunchKernelGGL(k_mf_gather, dim3((nMax + MF_T - 1) / MF_T, nJobs), dim3(MF_T), 0, s, A);
         CS_CHECK_LAUNCH();
@@ -884,13 +858,6 @@ extern "C" int cs_merge_front_buffers_get(const cs_merge_front* mf, cs_merge_fro
 }
 
 extern "C" int cs_merge_front_download(cs_merge_front* mf, void* hip_stream, const void* d_src, void* h_dst, size_t bytes) {
-    const char* p = (const char*)d_src;
-    if (!mf || !h_dst || !p || p < mf->base || bytes > mf->bytes || p + bytes > mf->base + mf->bytes) {
-        cs_set_error("cs_merge_front_download: the range is not inside the handle's buffers");
-        return CS_ERR_INVALID;
-    }
-    CS_HIP(hipSetDevice(mf->device));
-    CS_HIP(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-    CS_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
-    return CS_OK;
+    return cs_arena_download("cs_merge_front_download", mf ? mf->device : 0, mf ? mf->base : nullptr, mf ? mf->bytes : 0, hip_stream, d_src, h_dst,
+                             bytes);
 }

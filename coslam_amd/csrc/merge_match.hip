@@ -28,6 +28,8 @@
 #include <vector>
 
 #include "cs_common.h"
+#include "dev_arena.h"
+#include "host33.h"
 
 #pragma clang fp contract(off)
 
@@ -274,38 +276,6 @@ __global__ __launch_bounds__(256) void k_mm_prep(MmPrepArgs A) {
     A.valid[(size_t)c * A.N + i] = ok ? 1 : 0;
 }
 
-inline size_t mm_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// mat33Inv is un-vendored: the library's definition is Gauss-Jordan elimination with partial pivoting on [K | I], the one the reference
-// drivers are linked with (so that F agrees with them to the bit)
-bool mm_inv33(const double* K, double* iK) {
-    double M[3][6];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) M[i][j] = K[3 * i + j], M[i][3 + j] = i == j ? 1.0 : 0.0;
-    for (int c = 0; c < 3; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < 3; ++r)
-            if (fabs(M[r][c]) > fabs(M[piv][c])) piv = r;
-        if (piv != c)
-            for (int j = 0; j < 6; ++j) {
-                const double t = M[c][j];
-                M[c][j] = M[piv][j], M[piv][j] = t;
-            }
-        const double d = M[c][c];
-        if (!(d != 0) || d != d) return false;
-        for (int j = 0; j < 6; ++j) M[c][j] /= d;
-        for (int r = 0; r < 3; ++r) {
-            if (r == c) continue;
-            const double f = M[r][c];
-            if (f == 0.0) continue;
-            for (int j = 0; j < 6; ++j) M[r][j] -= f * M[c][j];
-        }
-    }
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) iK[3 * i + j] = M[i][3 + j];
-    return true;
-}
-
 }  // namespace
 
 struct cs_merge_match {
@@ -317,13 +287,26 @@ struct cs_merge_match {
     double* seeds;   // [maxJobs][maxSeeds][4]
     MmJob* jobs;     // [maxJobs]
     MmArgs args;     // the tables (jobs / maxDisp are set per launch)
-    std::vector<std::vector<char>> stage;   // the host side of the uploads a call enqueued, alive until the next call has waited
-    hipStream_t stageStream;                // ... for the stream they were enqueued on
+    CsStage stage;
 };
+
+// the device block: per camera slot, the candidate lists, the matcher's work tables per batch slot, per job
+static void mm_layout(cs_merge_match* mm, CsArena& ar) {
+    const size_t nS = (size_t)mm->nCams * mm->N, nJ = mm->maxJobs, nL = nJ * 2 * (size_t)mm->pairCap, nT = nJ * mm->N, nO = CS_MERGE_MATCH_MAX_JOBS;
+    cs_merge_match_buffers& B = mm->b;
+    MmArgs& A = mm->args;
+    ar.take(B.blocks, nS * 128), ar.take(B.abc, nS * 4), ar.take(B.valid, nS), ar.take(mm->xs, nS * 2);
+    ar.take(B.pairs, nJ * mm->pairCap), ar.take(B.pairCount, nJ);
+    ar.take(A.liveKey, nL), ar.take(A.liveIJ, nL);
+    ar.take(A.rowBest, nT), ar.take(A.colBest, nT), ar.take(A.winKey, nT);
+    ar.take(A.rowTie, nT), ar.take(A.colTie, nT), ar.take(A.rowMatch, nT), ar.take(A.colMatch, nT), ar.take(A.rowSeed, nT), ar.take(A.winIJ, nT);
+    ar.take(mm->seeds, nJ * (size_t)(mm->maxSeeds > 0 ? mm->maxSeeds : 1) * 4), ar.take(mm->jobs, nJ);
+    ar.take(A.matches, nO * mm->maxMatches * 2), ar.take(A.scores, nO * mm->maxMatches), ar.take(A.counts, nO * 4);
+}
 
 extern "C" int cs_merge_match_fmat(const double K1[9], const double K2[9], const double E[9], double F[9]) {
     double iK1[9], iK2[9], T[9];
-    if (!K1 || !K2 || !E || !F || !mm_inv33(K1, iK1) || !mm_inv33(K2, iK2)) {
+    if (!K1 || !K2 || !E || !F || !cs_host_inv33(K1, iK1) || !cs_host_inv33(K2, iK2)) {
         cs_set_error("cs_merge_match_fmat: null argument or singular K");
         return CS_ERR_INVALID;
     }
@@ -348,35 +331,14 @@ extern "C" cs_merge_match* cs_merge_match_create(int device, int nCams, int N, i
     }
     cs_merge_match* mm = new cs_merge_match();
     mm->device = device, mm->nCams = nCams, mm->N = N, mm->maxJobs = maxJobs, mm->maxSeeds = maxSeeds, mm->pairCap = pairCap, mm->maxMatches = maxMatches;
-    const size_t nS = (size_t)nCams * N, nJ = maxJobs, nL = nJ * 2 * (size_t)pairCap, nT = nJ * N, nO = CS_MERGE_MATCH_MAX_JOBS;
-    const size_t sizes[] = {nS * 128, nS * 32, nS * 4, nS * 16,                                   // 0 blocks, abc, valid, xs
-                            nJ * pairCap * sizeof(cs_ncc_pair), nJ * 4,                             // 4 pairs, pairCount
-                            nL * 8, nL * 4,                                                         // 6 liveKey, liveIJ
-                            nT * 8, nT * 8, nT * 8, nT * 4, nT * 4, nT * 4, nT * 4, nT * 4, nT * 4, // 8 rowBest colBest winKey | rowTie colTie rowMatch colMatch rowSeed | winIJ
-                            nJ * (size_t)(maxSeeds > 0 ? maxSeeds : 1) * 32, nJ * sizeof(MmJob),    // 17 seeds, jobs
-                            nO * maxMatches * 8, nO * maxMatches * 8, nO * 16};                     // 19 matches, scores, counts
-    constexpr int NS = sizeof(sizes) / sizeof(sizes[0]);
-    size_t off[NS + 1] = {0};
-    for (int i = 0; i < NS; ++i) off[i + 1] = off[i] + mm_align(sizes[i]);
-    const size_t total = off[NS];
-    if (hipSetDevice(device) != hipSuccess || hipMalloc((void**)&mm->base, total) != hipSuccess || hipMemset(mm->base, 0, total) != hipSuccess) {
-        cs_set_error("cs_merge_match_create: %zu bytes of device memory: %s", total, hipGetErrorString(hipGetLastError()));
+    cs_merge_match_buffers& B = mm->b;
+    MmArgs& A = mm->args;
+    memset(&A, 0, sizeof(A));
+    if (!cs_arena_alloc(device, mm->base, mm->bytes, [mm](CsArena& ar) { mm_layout(mm, ar); })) {
+        cs_set_error("cs_merge_match_create: %zu bytes of device memory: %s", mm->bytes, hipGetErrorString(hipGetLastError()));
         delete mm;
         return nullptr;
     }
-    mm->bytes = total, mm->stageStream = nullptr;
-    char* b = mm->base;
-    cs_merge_match_buffers& B = mm->b;
-    B.blocks = (unsigned char*)(b + off[0]), B.abc = (double*)(b + off[1]), B.valid = (int*)(b + off[2]), mm->xs = (double*)(b + off[3]);
-    B.pairs = (cs_ncc_pair*)(b + off[4]), B.pairCount = (int*)(b + off[5]);
-    MmArgs& A = mm->args;
-    memset(&A, 0, sizeof(A));
-    A.liveKey = (mm_u64*)(b + off[6]), A.liveIJ = (unsigned*)(b + off[7]);
-    A.rowBest = (mm_u64*)(b + off[8]), A.colBest = (mm_u64*)(b + off[9]), A.winKey = (mm_u64*)(b + off[10]);
-    A.rowTie = (int*)(b + off[11]), A.colTie = (int*)(b + off[12]), A.rowMatch = (int*)(b + off[13]), A.colMatch = (int*)(b + off[14]);
-    A.rowSeed = (int*)(b + off[15]), A.winIJ = (unsigned*)(b + off[16]);
-    mm->seeds = (double*)(b + off[17]), mm->jobs = (MmJob*)(b + off[18]);
-    A.matches = (int*)(b + off[19]), A.scores = (double*)(b + off[20]), A.counts = (int*)(b + off[21]);
     A.N = N, A.pairCap = pairCap, A.maxMatches = maxMatches;
     B.matches = A.matches, B.scores = A.scores, B.counts = A.counts;
     B.nCams = nCams, B.N = N, B.maxJobs = maxJobs, B.maxSeeds = maxSeeds, B.pairCap = pairCap, B.maxMatches = maxMatches;
@@ -387,7 +349,7 @@ extern "C" void cs_merge_match_destroy(cs_merge_match* mm) {
     if (!mm) return;
     if (mm->base) {
         (void)hipSetDevice(mm->device);
-        (void)hipDeviceSynchronize();   // (an upload of the last call may still read mm->stage)
+        mm->stage.drain();   // (an upload of the last call may still read its staging copy)
         (void)hipFree(mm->base);
     }
     delete mm;
@@ -396,15 +358,13 @@ extern "C" void cs_merge_match_destroy(cs_merge_match* mm) {
 // the jobs' table and seeds of one batch to the device, then the matcher: nb workgroups
 static int mm_launch(cs_merge_match* mm, hipStream_t s, int nb, const MmJob* jobs, const int* nSeeds, const double* const* seeds, double maxDisp) {
     const size_t seedBytes = (size_t)(mm->maxSeeds > 0 ? mm->maxSeeds : 1) * 32;
-    mm->stage.emplace_back(sizeof(MmJob) * (size_t)nb);
-    memcpy(mm->stage.back().data(), jobs, sizeof(MmJob) * (size_t)nb);
-    CS_HIP(hipMemcpyAsync(mm->jobs, mm->stage.back().data(), sizeof(MmJob) * (size_t)nb, hipMemcpyHostToDevice, s));
+    int rc = mm->stage.upload(s, mm->jobs, jobs, sizeof(MmJob) * (size_t)nb);
+    if (rc != CS_OK) return rc;
     size_t need = 0;
     for (int k = 0; k < nb; ++k)
         if (nSeeds[k] > 0) need = (size_t)(k + 1) * seedBytes;
     if (need) {
-        mm->stage.emplace_back(need);
-        char* h = mm->stage.back().data();
+        char* h = mm->stage.block(need);
         memset(h, 0, need);
         for (int k = 0; k < nb; ++k)
             if (nSeeds[k] > 0) memcpy(h + k * seedBytes, seeds[k], (size_t)nSeeds[k] * 32);
@@ -414,16 +374,6 @@ static int mm_launch(cs_merge_match* mm, hipStream_t s, int nb, const MmJob* job
     A.jobs = mm->jobs, A.maxDisp = maxDisp;
     hipLaunchKernelGGL(k_merge_match, dim3(nb), dim3(MM_T), 0, s, A);
     CS_CHECK_LAUNCH();
-    return CS_OK;
-}
-
-static int mm_begin(cs_merge_match* mm, hipStream_t s) {
-    CS_HIP(hipSetDevice(mm->device));
-    if (!mm->stage.empty()) {   // an upload of the previous call may still read its staging copy: wait for THAT call's stream
-        CS_HIP(hipStreamSynchronize(mm->stageStream));
-        mm->stage.clear();
-    }
-    mm->stageStream = s;
     return CS_OK;
 }
 
@@ -448,7 +398,8 @@ extern "C" int cs_merge_match_from_pairs_dev(cs_merge_match* mm, void* hip_strea
     }
     if (nJobs == 0) return CS_OK;
     hipStream_t s = (hipStream_t)hip_stream;
-    int rc = mm_begin(mm, s);
+    CS_HIP(hipSetDevice(mm->device));
+    int rc = mm->stage.begin(s);
     if (rc != CS_OK) return rc;
     return mm_launch(mm, s, nJobs, jobs.data(), ns.data(), seeds, maxDisp);
 }
@@ -490,7 +441,8 @@ extern "C" int cs_merge_match_run_dev(cs_merge_match* mm, void* hip_stream, cons
         pj[k].pairs = (cs_ncc_pair*)mm->b.pairs + (size_t)slot * mm->pairCap, pj[k].count = (int*)mm->b.pairCount + slot;
     }
     hipStream_t s = (hipStream_t)hip_stream;
-    int rc = mm_begin(mm, s);
+    CS_HIP(hipSetDevice(mm->device));
+    int rc = mm->stage.begin(s);
     if (rc != CS_OK) return rc;
     P.xs = mm->xs, P.valid = (int*)mm->b.valid, P.N = N;
     hipLaunchKernelGGL(k_mm_prep, dim3((N + 255) / 256, nC), dim3(256), 0, s, P);
@@ -548,13 +500,6 @@ extern "C" int cs_merge_match_buffers_get(const cs_merge_match* mm, cs_merge_mat
 }
 
 extern "C" int cs_merge_match_download(cs_merge_match* mm, void* hip_stream, const void* d_src, void* h_dst, size_t bytes) {
-    const char* p = (const char*)d_src;
-    if (!mm || !h_dst || !p || p < mm->base || bytes > mm->bytes || p + bytes > mm->base + mm->bytes) {
-        cs_set_error("cs_merge_match_download: the range is not inside the handle's buffers");
-        return CS_ERR_INVALID;
-    }
-    CS_HIP(hipSetDevice(mm->device));
-    CS_HIP(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-    CS_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
-    return CS_OK;
+    return cs_arena_download("cs_merge_match_download", mm ? mm->device : 0, mm ? mm->base : nullptr, mm ? mm->bytes : 0, hip_stream, d_src, h_dst,
+                             bytes);
 }

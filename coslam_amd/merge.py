@@ -225,20 +225,68 @@ def recompute_map_points_keyfrms_dev(history, stream_ptr, cams, d_featRef, nMap,
                                                     vp(d_counts), vp(d_guard)), "cs_recompute_map_points_keyfrms_dev")
 
 
-class MergeApply:
+def _stream(device, stream_ptr):
+    """the stream a call goes to: the caller's, or torch's current stream of the device"""
+    import torch
+
+    return torch.cuda.current_stream(device).cuda_stream if stream_ptr is None else stream_ptr
+
+
+class _MergeHandle:
+    """What the handle classes below share: the library `_L`, the handle `_m` of the C type `_prefix`, its device."""
+
+    _prefix = None    # "cs_merge_front", ...: <prefix>_create / _destroy / _buffers_get / _download
+    _Buffers = None   # the ctypes mirror of <prefix>_buffers where the handle exports its buffers (-> self.buf)
+    _m = None
+
+    def _create(self, device, *args):
+        self._L, self.device = lib(), int(device)
+        fn = getattr(self._L, self._prefix + "_create")
+        fn.restype = C.c_void_p
+        self._m = fn(self.device, *args)
+        if not self._m:
+            check(-1, self._prefix + "_create")
+        if self._Buffers is not None:
+            self.buf = self._Buffers()
+            check(getattr(self._L, self._prefix + "_buffers_get")(C.c_void_p(self._m), C.byref(self.buf)), self._prefix + "_buffers_get")
+
+    def _stream(self, stream_ptr):
+        return _stream(self.device, stream_ptr)
+
+    def _down(self, ptr, n, dtype, stream_ptr=None):
+        import numpy as np
+
+        out = np.zeros(n, dtype)
+        if out.nbytes:
+            check(getattr(self._L, self._prefix + "_download")(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(ptr),
+                                                               C.c_void_p(out.ctypes.data), C.c_size_t(out.nbytes)), self._prefix + "_download")
+        return out
+
+    def close(self):
+        if self._m:
+            getattr(self._L, self._prefix + "_destroy")(C.c_void_p(self._m))
+            self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MergeApply(_MergeHandle):
     """cs_merge_apply: a merge's pose correction fed from and written to a TrackHistory, and the map behind it -- from "valid MergeInfo {R, t}
     exist" to "history and map are the merged ones" on one stream, no host wait.  plan: merge_keygraph_plan's dict (node_kf counted over ALL
     key frames given to the plan); key_frames: the frame numbers of those key frames, oldest first, the current key frame last; n_cams: the
     history's cameras (every one gets its chain, also those outside the plan).  MergePoseCorrection is the host-fed form of the same solve."""
 
+    _prefix = "cs_merge_apply"
+
     def __init__(self, plan, key_frames, n_cams, device=0):
         import numpy as np
         import torch
 
-        L = lib()
-        L.cs_merge_apply_create.restype = C.c_void_p
-        L.cs_merge_apply_guard.restype = C.c_void_p
-        self._L, self.device, self.n_cams = L, int(device), int(n_cams)
+        self.n_cams = int(n_cams)
         fx = int(plan["fixed_kf"]) if "fixed_kf" in plan else int(np.min(plan["node_kf"]))
         self.key_frames = np.ascontiguousarray(np.asarray(key_frames, dtype=np.int32)[fx:])
         node_kf = np.ascontiguousarray(np.asarray(plan["node_kf"], dtype=np.int32) - fx)
@@ -248,10 +296,9 @@ class MergeApply:
         sid = np.ascontiguousarray(plan["scale_id"], dtype=np.int32)
         self.n_edges, self.n_constraint = len(id1), int((sid >= 0).sum())
         p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
-        self._a = L.cs_merge_apply_create(self.device, self.n_cams, len(self.key_frames), p(self.key_frames), len(node_kf), p(node_kf), p(node_cam),
-                                          p(fixed), len(id1), p(id1), p(id2), p(sid))
-        if not self._a:
-            check(-1, "cs_merge_apply_create")
+        self._create(device, self.n_cams, len(self.key_frames), p(self.key_frames), len(node_kf), p(node_kf), p(node_cam), p(fixed), len(id1), p(id1),
+                     p(id2), p(sid))
+        self._L.cs_merge_apply_guard.restype = C.c_void_p
         dev = torch.device("cuda", self.device)
         self._torch = torch
         self.d_edgeS = torch.zeros(max(self.n_edges, 1), dtype=torch.float64, device=dev)
@@ -261,7 +308,7 @@ class MergeApply:
     @property
     def guard_ptr(self):
         """device pointer of the guard word (1 when the last run's solves failed)"""
-        return int(self._L.cs_merge_apply_guard(C.c_void_p(self._a)) or 0)
+        return int(self._L.cs_merge_apply_guard(C.c_void_p(self._m)) or 0)
 
     def run(self, history, info_R, info_T, stream_ptr=None):
         """cs_merge_apply_run_dev: info_R [nConstraint][9] / info_T [nConstraint][3] = MergeInfo::R / t of the constraint edges in edge order
@@ -272,43 +319,28 @@ class MergeApply:
         dT = torch.as_tensor(info_T, dtype=torch.float64).reshape(-1, 3).to(dev).contiguous()
         assert dR.shape[0] == self.n_constraint and dT.shape[0] == self.n_constraint
         self._keep = (dR, dT)
-        s = torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
         vp = C.c_void_p
-        check(self._L.cs_merge_apply_run_dev(vp(self._a), vp(history._h), vp(s), vp(dR.data_ptr()), vp(dT.data_ptr()), vp(self.d_edgeS.data_ptr())),
+        check(self._L.cs_merge_apply_run_dev(vp(self._m), vp(history._h), vp(self._stream(stream_ptr)), vp(dR.data_ptr()), vp(dT.data_ptr()), vp(self.d_edgeS.data_ptr())),
               "cs_merge_apply_run_dev")
 
     def run_dev(self, history, d_infoR, d_infoT, stream_ptr=None):
         """cs_merge_apply_run_dev with MergeInfo::R / t given as DEVICE POINTERS ([nConstraint][9] / [3] doubles in edge order), e.g.
         MergeConstraints.buf.infoR / infoT as cs_merge_info_dev left them.  Enqueues only."""
-        s = self._torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
         vp = C.c_void_p
-        check(self._L.cs_merge_apply_run_dev(vp(self._a), vp(history._h), vp(s), vp(d_infoR), vp(d_infoT), vp(self.d_edgeS.data_ptr())),
+        check(self._L.cs_merge_apply_run_dev(vp(self._m), vp(history._h), vp(self._stream(stream_ptr)), vp(d_infoR), vp(d_infoT), vp(self.d_edgeS.data_ptr())),
               "cs_merge_apply_run_dev")
 
     def recompute(self, history, cams, d_featRef, nMap, d_mapCount, d_firstFrame, d_lastFrame, d_mapFlags, d_mapPts, d_mapCov, f_start,
                   pixelErrVar, updateCov=True, d_counts=None, stream_ptr=None):
         """MergeCameraGroup::recomputeMapPoints behind run(), guarded by its solves: f_end = the current key frame; the caller forms
         f_start = max(fixed frame, last release frame) as CoSLAM::mergeCamGroups does (reference src/app/SL_CoSLAM.cpp:1430-1434)."""
-        s = self._torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
-        recompute_map_points_keyfrms_dev(history, s, cams, d_featRef, nMap, d_mapCount, d_firstFrame, d_lastFrame, d_mapFlags, f_start,
+        recompute_map_points_keyfrms_dev(history, self._stream(stream_ptr), cams, d_featRef, nMap, d_mapCount, d_firstFrame, d_lastFrame, d_mapFlags, f_start,
                                          int(self.key_frames[-1]), self.d_key_frames.data_ptr(), len(self.key_frames), d_mapPts, d_mapCov,
                                          pixelErrVar, updateCov, d_counts, self.guard_ptr)
 
     def status(self, stream_ptr=None):
         """cs_merge_apply_status: waits; raises CoslamHipError (CS_ERR_NUMERIC) naming the failed graph"""
-        s = self._torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
-        check(self._L.cs_merge_apply_status(C.c_void_p(self._a), C.c_void_p(s)), "cs_merge_apply_status")
-
-    def close(self):
-        if self._a:
-            self._L.cs_merge_apply_destroy(C.c_void_p(self._a))
-            self._a = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        check(self._L.cs_merge_apply_status(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr))), "cs_merge_apply_status")
 
 
 def merge_first_constrain(frames, self_motion, cam_ids):
@@ -348,26 +380,17 @@ class MergeConstraintsBuffers(C.Structure):
                [(n, C.c_void_p) for n in ("solvedRs", "solvedTs", "solvedPts", "outlier")]
 
 
-class MergeConstraints:
+class MergeConstraints(_MergeHandle):
     """cs_merge_constraints: MergeCameraGroup::genMergeInfoVer2 on the device, from the matched features of two cameras to the merge's
     bundle-adjustment problem (assemble) and from a set of poses to the MergeInfo {R, t} list (info).  The buffers stay in device memory
     (d_info_R / d_info_T are what MergeApply.run takes); problem() / views() / infos() download them for a host-side caller."""
 
+    _prefix, _Buffers = "cs_merge_constraints", MergeConstraintsBuffers
+
     def __init__(self, n_cams, N, max_matches, max_map, device=0):
-        L = lib()
-        L.cs_merge_constraints_create.restype = C.c_void_p
-        self._L, self.device, self.n_cams, self.N = L, int(device), int(n_cams), int(N)
-        self._m = L.cs_merge_constraints_create(self.device, self.n_cams, self.N, int(max_matches), int(max_map))
-        if not self._m:
-            check(-1, "cs_merge_constraints_create")
-        self.buf = MergeConstraintsBuffers()
-        check(L.cs_merge_constraints_buffers_get(C.c_void_p(self._m), C.byref(self.buf)), "cs_merge_constraints_buffers_get")
+        self.n_cams, self.N = int(n_cams), int(N)
+        self._create(device, self.n_cams, self.N, int(max_matches), int(max_map))
         self._keep = None
-
-    def _stream(self, stream_ptr):
-        import torch
-
-        return torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
 
     def assemble(self, history, cams, d_featRef, nMap, d_mapPts, d_groups, gId1, gId2, maxiCam, maxjCam, f1, f2, matches, stream_ptr=None):
         """cs_merge_constraints_assemble_dev.  cams: a merge_cams() array or a list of dicts of device pointers (xy, state, slot2map, K of the
@@ -446,15 +469,6 @@ class MergeConstraints:
               "cs_merge_constraints_header_get")
         return h
 
-    def _down(self, ptr, n, dtype, stream_ptr=None):
-        import numpy as np
-
-        out = np.zeros(n, dtype)
-        if out.nbytes:
-            check(self._L.cs_merge_constraints_download(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(ptr),
-                                                        C.c_void_p(out.ctypes.data), C.c_size_t(out.nbytes)), "cs_merge_constraints_download")
-        return out
-
     def problem(self, stream_ptr=None):
         """-> dict(header, Ks, Rs, Ts, pts, pointMap, obs_ptr, obs_cam, obs_xy) as numpy, cut to the header's counts"""
         import numpy as np
@@ -482,17 +496,6 @@ class MergeConstraints:
         valid = self._down(b.infoValid, h.nInfo, np.uint8).astype(np.int32).reshape(-1, 1)
         return np.concatenate([ints, valid], axis=1), self._down(b.infoR, 9 * h.nInfo, np.float64).reshape(-1, 9), \
             self._down(b.infoT, 3 * h.nInfo, np.float64).reshape(-1, 3)
-
-    def close(self):
-        if self._m:
-            self._L.cs_merge_constraints_destroy(C.c_void_p(self._m))
-            self._m = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 MERGE_HOLD_OFF = 130   # CoSLAM::mergeCamGroups: `curFrame < m_lastFrmGroupMerge + 130` (reference src/app/SL_CoSLAM.cpp:1381)
@@ -538,7 +541,7 @@ class MergeCamGroups:
                    groups=None, group_id=None, merged_gid=-1, record=None, error=None)
         if cur < self.last_merge_frame + MERGE_HOLD_OFF:
             return rep
-        s = torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        s = _stream(self.device, stream_ptr)
         dev = torch.device("cuda", self.device)
         gId1, gId2, iCam, jCam = (int(v) for v in pair)
         rec = _camera_groups_record(groups)
@@ -606,7 +609,7 @@ class MergeCamGroups:
         was chosen (choice.status 0 or -1): nothing is enqueued behind the matcher then."""
         import torch
 
-        s = torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        s = _stream(self.device, stream_ptr)
         job_of, jl = [-1] * len(infos), []
         for e, (inf, j) in enumerate(zip(infos, jobs)):
             if j is None or surf_num[e] < 25 or not emat_ok[e]:
@@ -642,7 +645,7 @@ class MergeCamGroups:
         job table takes them from host memory).  -> run_from_seeds' dict, plus front (MergeFront.run's list)."""
         import torch
 
-        s = torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        s = _stream(self.device, stream_ptr)
         got = front.run(front_cams, [(int(inf[1]), int(inf[4])) for inf in infos], ratio, max_dist, n_ransac, max_epi_err, min_inlier_num, seed,
                         stream_ptr=s)
         rep = self.run_from_seeds(matcher, match_cams, Ws, Hs, infos, [g["surf_num"] for g in got], [g["emat_ok"] for g in got],
@@ -742,27 +745,18 @@ def merge_match_select(infos, surf_num, emat_ok, ncc_num, group_size, eligible=N
     return out.as_dict()
 
 
-class MergeMatcher:
+class MergeMatcher(_MergeHandle):
     """cs_merge_match: MergeCameraGroup::matchFeaturePointsNCC on the device for the candidate camera pairs of a key frame -- blocks from
     the key frame's small images, the epipolar / NCC candidate lists, the seed-guided greedy one-to-one matching.  The
     outputs stay in device memory: matches_ptr(k) is what MergeConstraints.assemble / MergeCamGroups.run take as a device table."""
 
+    _prefix, _Buffers = "cs_merge_match", MergeMatchBuffers
+
     def __init__(self, n_cams, N, max_jobs, max_seeds, pair_cap, max_matches, device=0):
-        L = lib()
-        L.cs_merge_match_create.restype = C.c_void_p
-        self._L, self.device, self.n_cams, self.N = L, int(device), int(n_cams), int(N)
+        self.n_cams, self.N = int(n_cams), int(N)
         self.max_jobs, self.max_seeds, self.pair_cap, self.max_matches = int(max_jobs), int(max_seeds), int(pair_cap), int(max_matches)
-        self._m = L.cs_merge_match_create(self.device, self.n_cams, self.N, self.max_jobs, self.max_seeds, self.pair_cap, self.max_matches)
-        if not self._m:
-            check(-1, "cs_merge_match_create")
-        self.buf = MergeMatchBuffers()
-        check(L.cs_merge_match_buffers_get(C.c_void_p(self._m), C.byref(self.buf)), "cs_merge_match_buffers_get")
+        self._create(device, self.n_cams, self.N, self.max_jobs, self.max_seeds, self.pair_cap, self.max_matches)
         self._keep = None
-
-    def _stream(self, stream_ptr):
-        import torch
-
-        return torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
 
     def run(self, cams, Ws, Hs, jobs, epi_max=20.0, ncc_min=0.45, max_disp=150.0, stream_ptr=None):
         """cs_merge_match_run_dev.  cams: per camera a dict xy, state, imgSmall (device pointers), K (9 doubles, HOST array), imgScale;
@@ -816,15 +810,6 @@ class MergeMatcher:
         """device pointer of job's [maxMatches][2] int32 slot pairs"""
         return int(self.buf.matches) + 8 * self.max_matches * int(job)
 
-    def _down(self, ptr, n, dtype, stream_ptr=None):
-        import numpy as np
-
-        out = np.zeros(n, dtype)
-        if out.nbytes:
-            check(self._L.cs_merge_match_download(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(ptr),
-                                                  C.c_void_p(out.ctypes.data), C.c_size_t(out.nbytes)), "cs_merge_match_download")
-        return out
-
     def matches(self, job, count, stream_ptr=None):
         """-> (int32 [count][2] slot pairs in acceptance order, float64 [count] scores) of one job; waits"""
         import numpy as np
@@ -849,17 +834,6 @@ class MergeMatcher:
         dt = np.dtype([("i", np.int32), ("j", np.int32), ("epi", np.float64), ("ncc", np.float64)])
         total = int(self._down(int(self.buf.pairCount) + 4 * int(slot), 1, np.int32, stream_ptr)[0])
         return total, self._down(int(self.buf.pairs) + dt.itemsize * self.pair_cap * int(slot), min(total, self.pair_cap), dt, stream_ptr)
-
-    def close(self):
-        if self._m:
-            self._L.cs_merge_match_destroy(C.c_void_p(self._m))
-            self._m = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def ncc_small_image_dev(stream_ptr, d_img, W, H, scale, d_small, device=0):
@@ -900,26 +874,16 @@ class MergeFrontBuffers(C.Structure):
                                           "hypE", "pix", "valid")] + [(n, C.c_int) for n in ("nCams", "maxPts", "dimDesc", "maxJobs", "maxHyp")]
 
 
-class MergeFront:
+class MergeFront(_MergeHandle):
     """cs_merge_front: the front of matchMergableCameras on the device -- matchSurf over the descriptors of every candidate camera pair, the
     RANSAC of estimateEMat with its local refit, the inliers' seed rows.  From key points + descriptors to what MergeMatcher.run
     and merge_match_select take per job: E, seeds, surf_num, emat_ok."""
 
+    _prefix, _Buffers = "cs_merge_front", MergeFrontBuffers
+
     def __init__(self, n_cams, max_pts, dim_desc, max_jobs, max_hyp, device=0):
-        L = lib()
-        L.cs_merge_front_create.restype = C.c_void_p
-        self._L, self.device, self.n_cams, self.max_pts, self.dim = L, int(device), int(n_cams), int(max_pts), int(dim_desc)
-        self.max_jobs, self.max_hyp = int(max_jobs), int(max_hyp)
-        self._m = L.cs_merge_front_create(self.device, self.n_cams, self.max_pts, self.dim, self.max_jobs, self.max_hyp)
-        if not self._m:
-            check(-1, "cs_merge_front_create")
-        self.buf = MergeFrontBuffers()
-        check(L.cs_merge_front_buffers_get(C.c_void_p(self._m), C.byref(self.buf)), "cs_merge_front_buffers_get")
-
-    def _stream(self, stream_ptr):
-        import torch
-
-        return torch.cuda.current_stream(self.device).cuda_stream if stream_ptr is None else stream_ptr
+        self.n_cams, self.max_pts, self.dim, self.max_jobs, self.max_hyp = int(n_cams), int(max_pts), int(dim_desc), int(max_jobs), int(max_hyp)
+        self._create(device, self.n_cams, self.max_pts, self.dim, self.max_jobs, self.max_hyp)
 
     def _tables(self, cams, pairs):
         import numpy as np
@@ -989,15 +953,6 @@ class MergeFront:
             r["seeds"] = np.ascontiguousarray(rows[k, :r["inlier_num"]])
         return out
 
-    def _down(self, ptr, n, dtype, stream_ptr=None):
-        import numpy as np
-
-        out = np.zeros(n, dtype)
-        if out.nbytes:
-            check(self._L.cs_merge_front_download(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(ptr),
-                                                  C.c_void_p(out.ctypes.data), C.c_size_t(out.nbytes)), "cs_merge_front_download")
-        return out
-
     def counts(self, n_jobs, stream_ptr=None):
         """matchSurf's count of jobs 0 .. n_jobs - 1; waits"""
         import numpy as np
@@ -1041,14 +996,3 @@ class MergeFront:
         import numpy as np
 
         return self._down(int(self.buf.pix) + 32 * self.max_pts * int(slot), 4 * int(count), np.float64, stream_ptr).reshape(-1, 4)
-
-    def close(self):
-        if self._m:
-            self._L.cs_merge_front_destroy(C.c_void_p(self._m))
-            self._m = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -53,6 +53,15 @@ def test_refusals_that_need_no_device():
     lib.cs_merge_front_destroy(z)
 
 
+def test_device_arena_and_range_test_on_the_host(tmp_path):
+    """tests/cxx/dev_arena_test.cpp: the merge handles' layout arena (two passes, 256-byte alignment, declared order, empty arrays) and the
+    range test behind every cs_merge_*_download (both ends, a pointer below the base, byte counts that would wrap) -- no HIP, no device"""
+    exe = str(tmp_path / "dev_arena_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cxx", "dev_arena_test.cpp"), "-o", exe])
+    got = subprocess.run([exe], capture_output=True, text=True)
+    assert got.returncode == 0 and got.stdout.strip() == "dev_arena ok", got.stdout + got.stderr
+
+
 def test_no_device_means_loud_failure():
     if coslam_amd.lib().cs_device_count() > 0:
         pytest.skip("a GPU is visible here")
