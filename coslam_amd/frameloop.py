@@ -270,8 +270,6 @@ class FrameLoop:
         if cfg.klt_cus > 0 or cfg.pose_cus > 0:
             # CU-partitioned streams (cs_stream_create_cu_range = hipExtStreamCreateWithCUMask): VERDICT r04 item 3
             L_ = coslam_amd.lib()
-            L_.cs_stream_create_cu_range.restype = C.c_void_p
-            L_.cs_stream_create_cu_range.argtypes = [C.c_int, C.c_int, C.c_int]
             if cfg.klt_cus > 0:
                 h_ = L_.cs_stream_create_cu_range(device, 0, int(cfg.klt_cus))
                 if not h_:
@@ -563,10 +561,8 @@ class FrameLoop:
     def _allgather(self, send, recv, nbytes):
         """one all-gather on the pose stream: the library's communicator, else torch.distributed's"""
         if self.native is not None:
-            L, vp = coslam_amd.lib(), C.c_void_p
-            L.cs_comm_allgather_dev.argtypes = [vp, vp, vp, vp, C.c_size_t]
-            check(L.cs_comm_allgather_dev(self.native.exchange_comm, vp(self.pose_s.cuda_stream), vp(send.data_ptr()), vp(recv.data_ptr()),
-                                          nbytes), "cs_comm_allgather_dev")
+            check(coslam_amd.lib().cs_comm_allgather_dev(self.native.exchange_comm, self.pose_s.cuda_stream, send.data_ptr(), recv.data_ptr(),
+                                                         nbytes), "cs_comm_allgather_dev")
         else:
             import torch.distributed as dist
 
@@ -1246,14 +1242,14 @@ class FrameLoop:
         """the own cameras' columns of the current-static pass's candidate tables to every rank (18 KB per camera: latency-bound, ONE
         collective), so that every rank takes the same registration decisions on its replica"""
         NA, nc, P = self.cfg.n_cams, self.nc, self.cfg.p_reg   # P: rows of a record = the list's cap
-        L, vp, ps, o = coslam_amd.lib(), C.c_void_p, self.pose_s.cuda_stream, self.reg_out
+        L, ps, o = coslam_amd.lib(), self.pose_s.cuda_stream, self.reg_out
         send, recv = self._cand
-        check(L.cs_register_candidates_pack_list_dev(self.device, vp(ps), P, NA, self.c0, nc, vp(self.d_curlist.data_ptr()), vp(o["slot"].data_ptr()),
-                                                     vp(o["flags"].data_ptr()), vp(self.d_mergeable.data_ptr()), vp(send.data_ptr())),
+        check(L.cs_register_candidates_pack_list_dev(self.device, ps, P, NA, self.c0, nc, self.d_curlist.data_ptr(), o["slot"].data_ptr(),
+                                                     o["flags"].data_ptr(), self.d_mergeable.data_ptr(), send.data_ptr()),
               "cs_register_candidates_pack_list_dev")
         self._allgather(send, recv, send.numel() * 4)
-        check(L.cs_register_candidates_unpack_list_dev(self.device, vp(ps), P, NA, nc, self.rank, vp(self.d_curlist.data_ptr()), vp(recv.data_ptr()),
-                                                       vp(o["slot"].data_ptr()), vp(o["flags"].data_ptr()), vp(self.d_mergeable.data_ptr())),
+        check(L.cs_register_candidates_unpack_list_dev(self.device, ps, P, NA, nc, self.rank, self.d_curlist.data_ptr(), recv.data_ptr(),
+                                                       o["slot"].data_ptr(), o["flags"].data_ptr(), self.d_mergeable.data_ptr()),
               "cs_register_candidates_unpack_list_dev")
 
     # ---------------------------------------------------------------------------------------------------------------

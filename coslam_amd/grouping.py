@@ -9,14 +9,14 @@ MAX_CAMS = 16
 
 
 class GroupingCam(C.Structure):
-    """== cs_grouping_cam (include/coslam_hip.h)."""
-
+    _c_type_ = "cs_grouping_cam"
     _fields_ = [("xy", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p)]
 
 
 class CameraGroups(C.Structure):
-    """== cs_camera_groups (include/coslam_hip.h): CameraGroup m_groups[] / m_groupNum / m_groupId[]."""
+    """CameraGroup m_groups[] / m_groupNum / m_groupId[]."""
 
+    _c_type_ = "cs_camera_groups"
     _fields_ = [("groupNum", C.c_int), ("num", C.c_int * MAX_CAMS), ("camIds", (C.c_int * MAX_CAMS) * MAX_CAMS), ("groupId", C.c_int * MAX_CAMS)]
 
     def groups(self):
@@ -42,18 +42,14 @@ def grouping_cams(cams):
 
 def camera_grouping_scratch_bytes(nCams, N):
     """bytes of device scratch of the two entries: zero it once before the first call, every call leaves it zeroed"""
-    fn = lib().cs_camera_grouping_scratch_bytes
-    fn.restype = C.c_size_t
-    return int(fn(int(nCams), int(N)))
+    return lib().cs_camera_grouping_scratch_bytes(int(nCams), int(N))
 
 
 def _common(stream_ptr, cams, N, nMap, d_mapCount, d_pointFeat, d_mapFlags, d_list, d_listCount, W, H, minOverlapNum, minOverlapAreaRatio, d_vcosts,
             d_nShare, d_hullArea, d_scratch, device):
-    vp = C.c_void_p
     arr = grouping_cams(cams)
-    return (int(device), vp(stream_ptr), len(arr), arr if len(arr) else None, int(N), int(nMap), vp(d_mapCount), vp(d_pointFeat), vp(d_mapFlags),
-            vp(d_list), vp(d_listCount), int(W), int(H), int(minOverlapNum), C.c_double(minOverlapAreaRatio), vp(d_vcosts), vp(d_nShare),
-            vp(d_hullArea), vp(d_scratch))
+    return (int(device), stream_ptr, len(arr), arr if len(arr) else None, int(N), int(nMap), d_mapCount, d_pointFeat, d_mapFlags, d_list, d_listCount,
+            int(W), int(H), int(minOverlapNum), minOverlapAreaRatio, d_vcosts, d_nShare, d_hullArea, d_scratch)
 
 
 def view_overlap_costs_dev(stream_ptr, cams, N, nMap, d_mapCount, d_pointFeat, d_mapFlags, W, H, d_vcosts, d_nShare, d_scratch, minOverlapNum=0,
@@ -72,5 +68,5 @@ def camera_grouping_dev(stream_ptr, cams, N, nMap, d_mapCount, d_pointFeat, d_ma
     in device memory)."""
     check(lib().cs_camera_grouping_dev(*_common(stream_ptr, cams, N, nMap, d_mapCount, d_pointFeat, d_mapFlags, d_list, d_listCount, W, H,
                                                 minOverlapNum, minOverlapAreaRatio, d_vcosts, d_nShare, d_hullArea, d_scratch, device),
-                                       C.c_double(initCamTranslation), C.c_double(maxDistRatio), C.c_void_p(d_groups)),
+                                       initCamTranslation, maxDistRatio, d_groups),
           "cs_camera_grouping_dev")

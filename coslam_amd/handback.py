@@ -8,8 +8,9 @@ from .pose import IntraCamPoseOption  # noqa: F401  (layout of the `opt` record)
 
 
 class HandbackCam(C.Structure):
-    """== cs_handback_cam (include/coslam_hip.h): device pointers of one camera."""
+    """Device pointers of one camera."""
 
+    _c_type_ = "cs_handback_cam"
     _fields_ = [(n, C.c_void_p) for n in ("dest", "K", "kud", "mapPts", "isStatic", "slot2map", "trackSpan", "xy", "state",
                                           "selBlk", "Ms", "ms", "sel", "npts", "opt", "pointFeat")] + \
                [("pointFeatStride", C.c_int), ("nPointFeat", C.c_int)]
@@ -30,5 +31,5 @@ def handback_dev(stream_ptr, cams, N, W, H, nColBlk=16, nRowBlk=12, ptsStride=19
     """cams: a list of dicts (see handback_cams) or the array handback_cams returned;
     frame: GPUKLT::m_frame of this call (the tracks' frame spans are kept in trackSpan)."""
     arr = cams if isinstance(cams, C.Array) else handback_cams(cams)
-    check(lib().cs_klt_handback_dev(int(device), C.c_void_p(stream_ptr), len(arr), arr, int(N), int(W), int(H),
-                                    int(nColBlk), int(nRowBlk), int(ptsStride), int(frame)), "cs_klt_handback_dev")
+    check(lib().cs_klt_handback_dev(int(device), stream_ptr, len(arr), arr, int(N), int(W), int(H), int(nColBlk), int(nRowBlk), int(ptsStride),
+                                    int(frame)), "cs_klt_handback_dev")

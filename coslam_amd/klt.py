@@ -10,14 +10,15 @@ import numpy as np
 
 from ._lib import CoslamHipError, check, lib
 
-# == KLT_TrackedFeature, v3d_gpuklt.h:166-176
+# KLT_TrackedFeature, v3d_gpuklt.h:166-176
 KLT_TrackedFeature = np.dtype([("status", "<i4"), ("pos", "<f4", (2,)), ("gain", "<f4"), ("fed", "<i4")])
-assert KLT_TrackedFeature.itemsize == 20
+C_RECORD_TYPES = {"KLT_TrackedFeature": "cs_klt_feature"}   # the numpy record types of this module -> their C types (tests/test_abi.py)
 
 
 class KLT_SequenceTrackerConfig(C.Structure):
-    """== KLT_SequenceTrackerConfig, v3d_gpuklt.h:180-199 (defaults identical)."""
+    """KLT_SequenceTrackerConfig, v3d_gpuklt.h:180-199 (defaults identical)."""
 
+    _c_type_ = "cs_klt_config"
     _fields_ = [
         ("nIterations", C.c_int),
         ("nLevels", C.c_int),
@@ -75,13 +76,10 @@ class KLT_SequenceTracker:
 
     def __init__(self, config, device=0, tap_mode=0):
         self._L = lib()
-        self._L.cs_klt_create.restype = C.c_void_p
-        self._L.cs_klt_create.argtypes = [C.POINTER(KLT_SequenceTrackerConfig), C.c_int, C.c_int]
         self.config = config
         self._h = self._L.cs_klt_create(C.byref(config), int(device), int(tap_mode))
         if not self._h:
             raise CoslamHipError("cs_klt_create: " + self._L.cs_last_error().decode())
-        self._h = C.c_void_p(self._h)
         self.N = 0
 
     # -- lifetime
@@ -97,7 +95,6 @@ class KLT_SequenceTracker:
 
     def close(self):
         if self._h:
-            self._L.cs_klt_destroy.argtypes = [C.c_void_p]
             self._L.cs_klt_destroy(self._h)
             self._h = None
 
@@ -109,13 +106,13 @@ class KLT_SequenceTracker:
 
     # -- setters, v3d_gpuklt.h:219-240
     def setBorderMargin(self, m):
-        check(self._L.cs_klt_set_border_margin(self._h, C.c_float(m)))
+        check(self._L.cs_klt_set_border_margin(self._h, m))
 
     def setConvergenceThreshold(self, t):
-        check(self._L.cs_klt_set_convergence_threshold(self._h, C.c_float(t)))
+        check(self._L.cs_klt_set_convergence_threshold(self._h, t))
 
     def setSSD_Threshold(self, t):
-        check(self._L.cs_klt_set_ssd_threshold(self._h, C.c_float(t)))
+        check(self._L.cs_klt_set_ssd_threshold(self._h, t))
 
     # -- reference-shaped host calls: return (count, dest[N])
     def _dest(self):
@@ -125,64 +122,59 @@ class KLT_SequenceTracker:
         img = _u8(image, self.W, self.H)
         dest, n = self._dest(), C.c_int(0)
         if present is None:
-            check(self._L.cs_klt_detect(self._h, img.ctypes.data_as(C.c_void_p), C.byref(n),
-                                        dest.ctypes.data_as(C.c_void_p)), "cs_klt_detect")
+            check(self._L.cs_klt_detect(self._h, img.ctypes.data, C.byref(n), dest.ctypes.data), "cs_klt_detect")
         else:
             p = np.ascontiguousarray(present, dtype=np.float32).reshape(-1, 3)
-            check(self._L.cs_klt_detect_present(self._h, img.ctypes.data_as(C.c_void_p), C.byref(n),
-                                                dest.ctypes.data_as(C.c_void_p), p.shape[0],
-                                                p.ctypes.data_as(C.c_void_p)), "cs_klt_detect_present")
+            check(self._L.cs_klt_detect_present(self._h, img.ctypes.data, C.byref(n), dest.ctypes.data, p.shape[0],
+                                                p.ctypes.data), "cs_klt_detect_present")
         return n.value, dest
 
     def redetect(self, image):
         img = _u8(image, self.W, self.H)
         dest, n = self._dest(), C.c_int(0)
-        check(self._L.cs_klt_redetect(self._h, img.ctypes.data_as(C.c_void_p), C.byref(n),
-                                      dest.ctypes.data_as(C.c_void_p)), "cs_klt_redetect")
+        check(self._L.cs_klt_redetect(self._h, img.ctypes.data, C.byref(n), dest.ctypes.data), "cs_klt_redetect")
         return n.value, dest
 
     def track(self, image):
         img = _u8(image, self.W, self.H)
         dest, n = self._dest(), C.c_int(0)
-        check(self._L.cs_klt_track(self._h, img.ctypes.data_as(C.c_void_p), C.byref(n),
-                                   dest.ctypes.data_as(C.c_void_p)), "cs_klt_track")
+        check(self._L.cs_klt_track(self._h, img.ctypes.data, C.byref(n), dest.ctypes.data), "cs_klt_track")
         return n.value, dest
 
     def feedExternFeaturePoints(self, featPts):
         p = np.ascontiguousarray(featPts, dtype=np.float32).reshape(-1, 3)
         ids = np.full(max(p.shape[0], 1), -1, dtype=np.int32)
         n = C.c_int(0)
-        check(self._L.cs_klt_feed(self._h, p.shape[0], p.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
-                                  C.byref(n)), "cs_klt_feed")
+        check(self._L.cs_klt_feed(self._h, p.shape[0], p.ctypes.data, ids.ctypes.data, C.byref(n)), "cs_klt_feed")
         return n.value, ids[: n.value].copy()
 
     def feed_dev(self, npts, d_featPts, d_trackIds, d_nFed):
         """feedExternFeaturePoints with the list, the slots and the count in device memory (asynchronous on the tracker's stream)"""
-        check(self._L.cs_klt_feed_dev(self._h, int(npts), C.c_void_p(d_featPts), C.c_void_p(d_trackIds), C.c_void_p(d_nFed)), "cs_klt_feed_dev")
+        check(self._L.cs_klt_feed_dev(self._h, int(npts), d_featPts, d_trackIds, d_nFed), "cs_klt_feed_dev")
 
     def advanceFrame(self):
         check(self._L.cs_klt_advance(self._h), "cs_klt_advance")
 
     # -- device-resident calls (pointers are ints: torch tensor .data_ptr())
     def set_stream(self, stream_ptr):
-        check(self._L.cs_klt_set_stream(self._h, C.c_void_p(stream_ptr)), "cs_klt_set_stream")
+        check(self._L.cs_klt_set_stream(self._h, stream_ptr), "cs_klt_set_stream")
 
     def detect_dev(self, d_image, d_dest, d_counts):
-        check(self._L.cs_klt_detect_dev(self._h, C.c_void_p(d_image), C.c_void_p(d_dest), C.c_void_p(d_counts)),
+        check(self._L.cs_klt_detect_dev(self._h, d_image, d_dest, d_counts),
               "cs_klt_detect_dev")
 
     def redetect_dev(self, d_image, d_dest, d_counts):
-        check(self._L.cs_klt_redetect_dev(self._h, C.c_void_p(d_image), C.c_void_p(d_dest), C.c_void_p(d_counts)),
+        check(self._L.cs_klt_redetect_dev(self._h, d_image, d_dest, d_counts),
               "cs_klt_redetect_dev")
 
     def track_dev(self, d_image, d_dest, d_counts):
-        check(self._L.cs_klt_track_dev(self._h, C.c_void_p(d_image), C.c_void_p(d_dest), C.c_void_p(d_counts)),
+        check(self._L.cs_klt_track_dev(self._h, d_image, d_dest, d_counts),
               "cs_klt_track_dev")
 
     def prefetch_dev(self, d_image_next):
         """Call BEFORE this frame's redetect_dev/detect_dev: its detector tail also builds the next frame's pyramid +
         cornerness map (cs_klt_prefetch_dev)."""
-        check(self._L.cs_klt_prefetch_dev(self._h, C.c_void_p(d_image_next)), "cs_klt_prefetch_dev")
+        check(self._L.cs_klt_prefetch_dev(self._h, d_image_next), "cs_klt_prefetch_dev")
 
     def enable_graphs(self, on=True):
         check(self._L.cs_klt_enable_graphs(self._h, 1 if on else 0), "cs_klt_enable_graphs")
@@ -201,19 +193,19 @@ class KLT_SequenceTracker:
     def debug_probe(self, on=True, read=False):
         """diagnostic: per-slot cycle counters of the persistent gain tracker (uint64[N, 8])"""
         out = np.zeros((self.N, 8), dtype=np.uint64) if read else None
-        check(self._L.cs_klt_debug_probe(self._h, 1 if on else 0, out.ctypes.data_as(C.c_void_p) if read else None),
+        check(self._L.cs_klt_debug_probe(self._h, 1 if on else 0, out.ctypes.data if read else None),
               "cs_klt_debug_probe")
         return out
 
     def redetect_async(self, image):
         """cs_klt_redetect_async_h: upload + redetect + read-back enqueued, returns at once (GPUKLT::next, first half)"""
         img = _u8(image, self.W, self.H)
-        check(self._L.cs_klt_redetect_async_h(self._h, img.ctypes.data_as(C.c_void_p)), "cs_klt_redetect_async_h")
+        check(self._L.cs_klt_redetect_async_h(self._h, img.ctypes.data), "cs_klt_redetect_async_h")
 
     def fetch(self):
         """cs_klt_fetch: blocks until the outstanding frame's results are on the host -> (count, dest[])"""
         dest, n = self._dest(), C.c_int(0)
-        check(self._L.cs_klt_fetch(self._h, C.byref(n), dest.ctypes.data_as(C.c_void_p)), "cs_klt_fetch")
+        check(self._L.cs_klt_fetch(self._h, C.byref(n), dest.ctypes.data), "cs_klt_fetch")
         return n.value, dest
 
     def set_cu_count(self, n_cus):
@@ -230,7 +222,6 @@ class KLT_SequenceTracker:
 
     # -- introspection for parity tests
     def pyramid_texels(self):
-        self._L.cs_klt_pyramid_texels.restype = C.c_size_t
         return int(self._L.cs_klt_pyramid_texels(self._h))
 
     def level_view(self, pyr, level):
@@ -240,22 +231,22 @@ class KLT_SequenceTracker:
 
     def read_pyramid(self, which=1):
         out = np.zeros(self.pyramid_texels() * 4, dtype=np.uint16)
-        check(self._L.cs_klt_read_pyramid(self._h, which, out.ctypes.data_as(C.c_void_p)), "cs_klt_read_pyramid")
+        check(self._L.cs_klt_read_pyramid(self._h, which, out.ctypes.data), "cs_klt_read_pyramid")
         return out
 
     def read_cornerness(self):
         out = np.zeros((self.H, self.W), dtype=np.float32)
-        check(self._L.cs_klt_read_cornerness(self._h, out.ctypes.data_as(C.c_void_p)), "cs_klt_read_cornerness")
+        check(self._L.cs_klt_read_cornerness(self._h, out.ctypes.data), "cs_klt_read_cornerness")
         return out
 
     def read_features(self):
         out = np.zeros((self.N, 3), dtype=np.float32)
-        check(self._L.cs_klt_read_features(self._h, out.ctypes.data_as(C.c_void_p)), "cs_klt_read_features")
+        check(self._L.cs_klt_read_features(self._h, out.ctypes.data), "cs_klt_read_features")
         return out
 
     def build_pyramid(self, image):
         img = _u8(image, self.W, self.H)
-        check(self._L.cs_klt_build_pyramid(self._h, img.ctypes.data_as(C.c_void_p)), "cs_klt_build_pyramid")
+        check(self._L.cs_klt_build_pyramid(self._h, img.ctypes.data), "cs_klt_build_pyramid")
 
 
 class KLT_TrackerGroup:
@@ -268,17 +259,14 @@ class KLT_TrackerGroup:
         self.trackers = list(trackers)
         n = len(self.trackers)
         arr = (C.c_void_p * n)(*[t._h for t in self.trackers])
-        self._L.cs_klt_group_create.restype = C.c_void_p
-        self._L.cs_klt_group_create.argtypes = [C.c_void_p, C.c_int]
         h = self._L.cs_klt_group_create(arr, n)
         if not h:
             raise CoslamHipError("cs_klt_group_create: " + self._L.cs_last_error().decode())
-        self._h = C.c_void_p(h)
+        self._h = h
         self.n = n
 
     def close(self):
         if self._h:
-            self._L.cs_klt_group_destroy.argtypes = [C.c_void_p]
             self._L.cs_klt_group_destroy(self._h)
             self._h = None
 
@@ -294,7 +282,7 @@ class KLT_TrackerGroup:
         return (C.c_void_p * self.n)(*[int(p) for p in ptrs])
 
     def set_stream(self, stream_ptr):
-        check(self._L.cs_klt_group_set_stream(self._h, C.c_void_p(stream_ptr)), "cs_klt_group_set_stream")
+        check(self._L.cs_klt_group_set_stream(self._h, stream_ptr), "cs_klt_group_set_stream")
 
     def detect_dev(self, d_images, d_dests, d_counts):
         check(self._L.cs_klt_group_detect_dev(self._h, self._ptrs(d_images), self._ptrs(d_dests), self._ptrs(d_counts)),

@@ -11,8 +11,9 @@ from .grouping import MAX_CAMS, CameraGroups
 
 
 class MapCounts(C.Structure):
-    """== cs_map_counts: m_nStatic, m_nDynamic, m_nStaticFeat[], m_nDynamicFeat[]."""
+    """m_nStatic, m_nDynamic, m_nStaticFeat[], m_nDynamicFeat[]."""
 
+    _c_type_ = "cs_map_counts"
     _fields_ = [("nStatic", C.c_int), ("nDynamic", C.c_int), ("nStaticFeat", C.c_int * MAX_CAMS), ("nDynamicFeat", C.c_int * MAX_CAMS)]
 
     def as_dict(self, nCams=MAX_CAMS):
@@ -21,51 +22,26 @@ class MapCounts(C.Structure):
 
 
 class LiveHeader(C.Structure):
-    """== cs_live_header."""
-
+    _c_type_ = "cs_live_header"
     _fields_ = [("frame", C.c_int), ("mapCount", C.c_int), ("nCur", C.c_int), ("nDyn", C.c_int), ("curOverflow", C.c_int),
                 ("dynOverflow", C.c_int), ("nCams", C.c_int), ("every", C.c_int), ("counts", MapCounts), ("R", (C.c_double * 9) * MAX_CAMS),
                 ("t", (C.c_double * 3) * MAX_CAMS), ("groups", CameraGroups), ("curOverflowTotal", C.c_int),
                 ("dynOverflowTotal", C.c_int), ("reserved", C.c_int)]
 
 
-# == cs_live_point / cs_live_dyn (32 bytes each)
 LIVE_POINT_DTYPE = np.dtype([("M", "<f8", 3), ("id", "<i4"), ("camMask", "<u2"), ("flags", "u1"), ("numVisCam", "u1")])
 LIVE_DYN_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("id", "<i4"), ("reserved", "<i4")])
-assert LIVE_POINT_DTYPE.itemsize == 32 and LIVE_DYN_DTYPE.itemsize == 32
-
-
-def _protos():
-    L = lib()
-    if getattr(L, "_liveview_protos", False):
-        return L
-    vp, ci = C.c_void_p, C.c_int
-    L.cs_liveview_create.restype = vp
-    L.cs_liveview_create.argtypes = [ci] * 7
-    L.cs_liveview_destroy.restype = None
-    L.cs_liveview_destroy.argtypes = [vp]
-    L.cs_liveview_frame_dev.argtypes = [vp, vp, ci, ci] + [vp] * 7
-    L.cs_liveview_newest.argtypes = [vp]
-    L.cs_liveview_fetch.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(vp)]
-    L.cs_liveview_rings.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
-    L.cs_liveview_dyn_fetch.argtypes = [vp, vp, ci, ci, vp, C.POINTER(ci), C.POINTER(ci)]
-    L.cs_liveview_trails_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp]
-    L.cs_liveview_trails.argtypes = [vp, vp, ci, ci, C.POINTER(ci), vp, vp, vp]
-    L.cs_map_counts_scratch_bytes.restype = C.c_size_t
-    L.cs_map_counts_scratch_bytes.argtypes = []
-    L.cs_map_counts_dev.argtypes = [ci, vp, ci, ci, vp, vp, vp, vp, vp]
-    L._liveview_protos = True
-    return L
+C_RECORD_TYPES = {"LIVE_POINT_DTYPE": "cs_live_point", "LIVE_DYN_DTYPE": "cs_live_dyn"}   # numpy record types -> their C types (tests/test_abi.py)
 
 
 def map_counts_scratch_bytes():
     """bytes of device scratch of map_counts_dev: zero it once before the first call, every call leaves it zeroed"""
-    return int(_protos().cs_map_counts_scratch_bytes())
+    return int(lib().cs_map_counts_scratch_bytes())
 
 
 def map_counts_dev(stream_ptr, nCams, nMap, d_mapCount, d_pointFeat, d_mapFlags, d_counts, d_scratch, device=0):
     """cs_map_counts_dev: getNumDynamicStaticPoints alone into d_counts (a MapCounts in device memory); one launch, no wait."""
-    check(_protos().cs_map_counts_dev(int(device), stream_ptr, int(nCams), int(nMap), d_mapCount, d_pointFeat, d_mapFlags, d_counts, d_scratch),
+    check(lib().cs_map_counts_dev(int(device), stream_ptr, int(nCams), int(nMap), d_mapCount, d_pointFeat, d_mapFlags, d_counts, d_scratch),
           "cs_map_counts_dev")
 
 
@@ -74,7 +50,7 @@ class LiveView:
     COPIES of a published frame's header and records; trails() is getDynTracks over the device ring."""
 
     def __init__(self, nCams, cur_cap, dyn_cap, depth=4, trail_depth=150, every=1, device=0):
-        L = _protos()
+        L = lib()
         self.nCams, self.cur_cap, self.dyn_cap, self.depth, self.trail_depth, self.every = nCams, cur_cap, dyn_cap, depth, trail_depth, every
         self.h = L.cs_liveview_create(int(device), int(nCams), int(cur_cap), int(dyn_cap), int(depth), int(trail_depth), int(every))
         if not self.h:
@@ -82,7 +58,7 @@ class LiveView:
 
     def close(self):
         if self.h:
-            _protos().cs_liveview_destroy(self.h)
+            lib().cs_liveview_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -92,17 +68,17 @@ class LiveView:
             pass
 
     def frame_dev(self, stream_ptr, frame, nMap, d_mapCount, d_pointFeat, d_mapFlags, d_mapPts, d_R, d_t, d_groups=None):
-        check(_protos().cs_liveview_frame_dev(self.h, stream_ptr, int(frame), int(nMap), d_mapCount, d_pointFeat, d_mapFlags, d_mapPts, d_R,
-                                              d_t, d_groups), "cs_liveview_frame_dev")
+        check(lib().cs_liveview_frame_dev(self.h, stream_ptr, int(frame), int(nMap), d_mapCount, d_pointFeat, d_mapFlags, d_mapPts, d_R, d_t,
+                                          d_groups), "cs_liveview_frame_dev")
 
     def newest(self):
         """the newest published frame that has landed on the host, or -1 (never waits)"""
-        return int(_protos().cs_liveview_newest(self.h))
+        return int(lib().cs_liveview_newest(self.h))
 
     def fetch(self, frame):
         """(LiveHeader, records) as VIEWS of the pinned ring: valid until `depth` more snapshots have been published"""
         hp, pp = C.c_void_p(), C.c_void_p()
-        check(_protos().cs_liveview_fetch(self.h, int(frame), C.byref(hp), C.byref(pp)), "cs_liveview_fetch")
+        check(lib().cs_liveview_fetch(self.h, int(frame), C.byref(hp), C.byref(pp)), "cs_liveview_fetch")
         hdr = LiveHeader.from_address(hp.value)
         n = max(0, min(int(hdr.nCur), self.cur_cap))
         buf = (C.c_char * (32 * self.cur_cap)).from_address(pp.value)
@@ -126,7 +102,7 @@ class LiveView:
     def rings(self):
         """dict(h_ring, slot_bytes, d_entries, d_counts, d_frames): addresses of the pinned ring and of the device ring of dynamic lists"""
         a, b, c, d, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
-        check(_protos().cs_liveview_rings(self.h, C.byref(a), C.byref(n), C.byref(b), C.byref(c), C.byref(d)), "cs_liveview_rings")
+        check(lib().cs_liveview_rings(self.h, C.byref(a), C.byref(n), C.byref(b), C.byref(c), C.byref(d)), "cs_liveview_rings")
         return dict(h_ring=a.value, slot_bytes=int(n.value), d_entries=b.value, d_counts=c.value, d_frames=d.value)
 
     def ring_bytes(self):
@@ -138,12 +114,12 @@ class LiveView:
         """(frame, entries as LIVE_DYN_DTYPE) of the dynamic list `frames_back` calls before the newest (waits for the stream)"""
         n, f = C.c_int(0), C.c_int(-1)
         out = np.zeros(self.dyn_cap, dtype=LIVE_DYN_DTYPE)
-        check(_protos().cs_liveview_dyn_fetch(self.h, stream_ptr, int(frames_back), self.dyn_cap, out.ctypes.data, C.byref(n), C.byref(f)),
+        check(lib().cs_liveview_dyn_fetch(self.h, stream_ptr, int(frames_back), self.dyn_cap, out.ctypes.data, C.byref(n), C.byref(f)),
               "cs_liveview_dyn_fetch")
         return int(f.value), out[:max(0, min(int(n.value), self.dyn_cap))].copy()
 
     def trails_dev(self, stream_ptr, trj_len, d_nTrails, d_trailId, d_trailLen, d_trailPts):
-        check(_protos().cs_liveview_trails_dev(self.h, stream_ptr, int(trj_len), d_nTrails, d_trailId, d_trailLen, d_trailPts),
+        check(lib().cs_liveview_trails_dev(self.h, stream_ptr, int(trj_len), d_nTrails, d_trailId, d_trailLen, d_trailPts),
               "cs_liveview_trails_dev")
 
     def trails(self, stream_ptr, trj_len, max_trails=None):
@@ -152,7 +128,7 @@ class LiveView:
         n = C.c_int(0)
         ids, lens = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
         pts = np.zeros((max(cap, 1), max(int(trj_len), 1), 3), np.float64)
-        check(_protos().cs_liveview_trails(self.h, stream_ptr, int(trj_len), cap, C.byref(n), ids.ctypes.data, lens.ctypes.data, pts.ctypes.data),
+        check(lib().cs_liveview_trails(self.h, stream_ptr, int(trj_len), cap, C.byref(n), ids.ctypes.data, lens.ctypes.data, pts.ctypes.data),
               "cs_liveview_trails")
         k = min(int(n.value), cap)
         return [(int(ids[q]), pts[q, :int(lens[q])].copy()) for q in range(k)]

@@ -10,14 +10,14 @@ MAX_INFO = 256
 
 
 class MergeCam(C.Structure):
-    """== cs_merge_cam (include/coslam_hip.h)."""
-
+    _c_type_ = "cs_merge_cam"
     _fields_ = [("xy", C.c_void_p), ("state", C.c_void_p), ("slot2map", C.c_void_p), ("K", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p)]
 
 
 class MergeInfo(C.Structure):
-    """== cs_merge_info: MergeInfo::set(frame1, cam1, gid1, frame2, cam2, gid2)."""
+    """MergeInfo::set(frame1, cam1, gid1, frame2, cam2, gid2)."""
 
+    _c_type_ = "cs_merge_info"
     _fields_ = [(n, C.c_int) for n in ("frame1", "cam1", "gid1", "frame2", "cam2", "gid2")]
 
     def as_tuple(self):
@@ -25,8 +25,7 @@ class MergeInfo(C.Structure):
 
 
 class MergeCandidates(C.Structure):
-    """== cs_merge_candidates (include/coslam_hip.h)."""
-
+    _c_type_ = "cs_merge_candidates"
     _fields_ = [("frame", C.c_int), ("groupNum", C.c_int), ("nMergeInfo", C.c_int), ("reserved", C.c_int), ("info", MergeInfo * MAX_INFO),
                 ("nFeat", C.c_int * MAX_CAMS), ("nInCam", (C.c_int * MAX_CAMS) * MAX_CAMS), ("inNum", (C.c_int * MAX_CAMS) * MAX_CAMS),
                 ("fromTo", (C.c_ubyte * MAX_CAMS) * MAX_CAMS), ("camDist", (C.c_double * MAX_CAMS) * MAX_CAMS)]
@@ -61,9 +60,7 @@ def merge_cams(cams):
 
 def merge_check_scratch_bytes(nCams, N):
     """bytes of device scratch: zero it once before the first call, every call leaves it zeroed"""
-    fn = lib().cs_merge_check_scratch_bytes
-    fn.restype = C.c_size_t
-    return int(fn(int(nCams), int(N)))
+    return lib().cs_merge_check_scratch_bytes(int(nCams), int(N))
 
 
 def merge_check_dev(stream_ptr, cams, N, nMap, d_mapCount, d_mapPts, d_mapFlags, W, H, d_groups, frame, d_out, d_scratch, minInNum=10,
@@ -71,11 +68,10 @@ def merge_check_dev(stream_ptr, cams, N, nMap, d_mapCount, d_mapPts, d_mapFlags,
     """cs_merge_check_dev: checkPossibleMergable(minInNum, minInAreaRatio, maxCamDist) over the record d_groups (a CameraGroups in device
     memory) into d_out (a MergeCandidates in device memory).  cams: a merge_cams() array or a list of dicts.  The defaults are the
     reference's call (10, 0.5, Param::maxDistRatio = 6.0 taken as a distance)."""
-    vp = C.c_void_p
     arr = merge_cams(cams)
-    check(lib().cs_merge_check_dev(int(device), vp(stream_ptr), len(arr), arr if len(arr) else None, int(N), int(nMap), vp(d_mapCount), vp(d_mapPts),
-                                   vp(d_mapFlags), int(W), int(H), vp(d_groups), int(frame), int(minInNum), C.c_double(minInAreaRatio),
-                                   C.c_double(maxCamDist), 1 if allPairs else 0, vp(d_out), vp(d_scratch)),
+    check(lib().cs_merge_check_dev(int(device), stream_ptr, len(arr), arr if len(arr) else None, int(N), int(nMap), d_mapCount, d_mapPts, d_mapFlags,
+                                   int(W), int(H), d_groups, int(frame), int(minInNum), minInAreaRatio, maxCamDist, 1 if allPairs else 0, d_out,
+                                   d_scratch),
           "cs_merge_check_dev")
 
 
@@ -110,7 +106,7 @@ def merge_keygraph_plan(frames, groups, cam_ids, first_constrain, camid1, camid2
     node_kf, node_cam, fixed = np.zeros(n_cap, np.int32), np.zeros(n_cap, np.int32), np.zeros(n_cap, np.uint8)
     id1, id2, sid = np.zeros(e_cap, np.int32), np.zeros(e_cap, np.int32), np.zeros(e_cap, np.int32)
     fx, nn, ne, nc = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+    p = lambda v: v.ctypes.data  # noqa: E731
     check(lib().cs_merge_keygraph_plan(nk, p(fr), recs, len(ids), p(ids), int(first_constrain), int(camid1), int(camid2), len(inf), p(inf),
                                        int(n_max_keyfrm), C.byref(fx), n_cap, C.byref(nn), p(node_kf), p(node_cam), p(fixed), e_cap, C.byref(ne),
                                        p(id1), p(id2), p(sid), C.byref(nc)), "cs_merge_keygraph_plan")
@@ -205,8 +201,8 @@ def merge_matched_groups(groups, gid1, gid2, camid1, camid2):
     a, b = np.ascontiguousarray(gid1, dtype=np.int32).reshape(-1), np.ascontiguousarray(gid2, dtype=np.int32).reshape(-1)
     assert len(a) == len(b)
     gid, mg = np.zeros(MAX_CAMS, np.int32), C.c_int(-1)
-    p = lambda v: C.c_void_p(v.ctypes.data) if len(v) else None  # noqa: E731
-    check(lib().cs_merge_matched_groups(C.byref(rec), len(a), p(a), p(b), int(camid1), int(camid2), C.c_void_p(gid.ctypes.data), C.byref(mg)),
+    p = lambda v: v.ctypes.data if len(v) else None  # noqa: E731
+    check(lib().cs_merge_matched_groups(C.byref(rec), len(a), p(a), p(b), int(camid1), int(camid2), gid.ctypes.data, C.byref(mg)),
           "cs_merge_matched_groups")
     return dict(record=rec, groups=rec.groups(), group_id=gid, merged_gid=mg.value)
 
@@ -218,11 +214,9 @@ def recompute_map_points_keyfrms_dev(history, stream_ptr, cams, d_featRef, nMap,
     place, one launch.  history: a TrackHistory; cams: K, iK per camera; d_keyFrames: ascending int32 frame numbers in device memory."""
     from .poseupdate import poseupdate_cams
 
-    vp = C.c_void_p
-    check(lib().cs_recompute_map_points_keyfrms_dev(vp(history._h), vp(stream_ptr), poseupdate_cams(cams), vp(d_featRef), int(nMap), vp(d_mapCount),
-                                                    vp(d_firstFrame), vp(d_lastFrame), vp(d_mapFlags), int(f_start), int(f_end), vp(d_keyFrames),
-                                                    int(nKey), vp(d_mapPts), vp(d_mapCov), C.c_double(pixelErrVar), 1 if updateCov else 0,
-                                                    vp(d_counts), vp(d_guard)), "cs_recompute_map_points_keyfrms_dev")
+    check(lib().cs_recompute_map_points_keyfrms_dev(history._h, stream_ptr, poseupdate_cams(cams), d_featRef, int(nMap), d_mapCount, d_firstFrame,
+                                                    d_lastFrame, d_mapFlags, int(f_start), int(f_end), d_keyFrames, int(nKey), d_mapPts, d_mapCov,
+                                                    pixelErrVar, 1 if updateCov else 0, d_counts, d_guard), "cs_recompute_map_points_keyfrms_dev")
 
 
 def _stream(device, stream_ptr):
@@ -241,14 +235,12 @@ class _MergeHandle:
 
     def _create(self, device, *args):
         self._L, self.device = lib(), int(device)
-        fn = getattr(self._L, self._prefix + "_create")
-        fn.restype = C.c_void_p
-        self._m = fn(self.device, *args)
+        self._m = getattr(self._L, self._prefix + "_create")(self.device, *args)
         if not self._m:
             check(-1, self._prefix + "_create")
         if self._Buffers is not None:
             self.buf = self._Buffers()
-            check(getattr(self._L, self._prefix + "_buffers_get")(C.c_void_p(self._m), C.byref(self.buf)), self._prefix + "_buffers_get")
+            check(getattr(self._L, self._prefix + "_buffers_get")(self._m, C.byref(self.buf)), self._prefix + "_buffers_get")
 
     def _stream(self, stream_ptr):
         return _stream(self.device, stream_ptr)
@@ -258,13 +250,13 @@ class _MergeHandle:
 
         out = np.zeros(n, dtype)
         if out.nbytes:
-            check(getattr(self._L, self._prefix + "_download")(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(ptr),
-                                                               C.c_void_p(out.ctypes.data), C.c_size_t(out.nbytes)), self._prefix + "_download")
+            check(getattr(self._L, self._prefix + "_download")(self._m, self._stream(stream_ptr), ptr, out.ctypes.data, out.nbytes),
+                  self._prefix + "_download")
         return out
 
     def close(self):
         if self._m:
-            getattr(self._L, self._prefix + "_destroy")(C.c_void_p(self._m))
+            getattr(self._L, self._prefix + "_destroy")(self._m)
             self._m = None
 
     def __del__(self):
@@ -295,10 +287,9 @@ class MergeApply(_MergeHandle):
         id1, id2 = np.ascontiguousarray(plan["id1"], dtype=np.int32), np.ascontiguousarray(plan["id2"], dtype=np.int32)
         sid = np.ascontiguousarray(plan["scale_id"], dtype=np.int32)
         self.n_edges, self.n_constraint = len(id1), int((sid >= 0).sum())
-        p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+        p = lambda v: v.ctypes.data  # noqa: E731
         self._create(device, self.n_cams, len(self.key_frames), p(self.key_frames), len(node_kf), p(node_kf), p(node_cam), p(fixed), len(id1), p(id1),
                      p(id2), p(sid))
-        self._L.cs_merge_apply_guard.restype = C.c_void_p
         dev = torch.device("cuda", self.device)
         self._torch = torch
         self.d_edgeS = torch.zeros(max(self.n_edges, 1), dtype=torch.float64, device=dev)
@@ -308,7 +299,7 @@ class MergeApply(_MergeHandle):
     @property
     def guard_ptr(self):
         """device pointer of the guard word (1 when the last run's solves failed)"""
-        return int(self._L.cs_merge_apply_guard(C.c_void_p(self._m)) or 0)
+        return int(self._L.cs_merge_apply_guard(self._m) or 0)
 
     def run(self, history, info_R, info_T, stream_ptr=None):
         """cs_merge_apply_run_dev: info_R [nConstraint][9] / info_T [nConstraint][3] = MergeInfo::R / t of the constraint edges in edge order
@@ -319,15 +310,13 @@ class MergeApply(_MergeHandle):
         dT = torch.as_tensor(info_T, dtype=torch.float64).reshape(-1, 3).to(dev).contiguous()
         assert dR.shape[0] == self.n_constraint and dT.shape[0] == self.n_constraint
         self._keep = (dR, dT)
-        vp = C.c_void_p
-        check(self._L.cs_merge_apply_run_dev(vp(self._m), vp(history._h), vp(self._stream(stream_ptr)), vp(dR.data_ptr()), vp(dT.data_ptr()), vp(self.d_edgeS.data_ptr())),
+        check(self._L.cs_merge_apply_run_dev(self._m, history._h, self._stream(stream_ptr), dR.data_ptr(), dT.data_ptr(), self.d_edgeS.data_ptr()),
               "cs_merge_apply_run_dev")
 
     def run_dev(self, history, d_infoR, d_infoT, stream_ptr=None):
         """cs_merge_apply_run_dev with MergeInfo::R / t given as DEVICE POINTERS ([nConstraint][9] / [3] doubles in edge order), e.g.
         MergeConstraints.buf.infoR / infoT as cs_merge_info_dev left them.  Enqueues only."""
-        vp = C.c_void_p
-        check(self._L.cs_merge_apply_run_dev(vp(self._m), vp(history._h), vp(self._stream(stream_ptr)), vp(d_infoR), vp(d_infoT), vp(self.d_edgeS.data_ptr())),
+        check(self._L.cs_merge_apply_run_dev(self._m, history._h, self._stream(stream_ptr), d_infoR, d_infoT, self.d_edgeS.data_ptr()),
               "cs_merge_apply_run_dev")
 
     def recompute(self, history, cams, d_featRef, nMap, d_mapCount, d_firstFrame, d_lastFrame, d_mapFlags, d_mapPts, d_mapCov, f_start,
@@ -340,7 +329,7 @@ class MergeApply(_MergeHandle):
 
     def status(self, stream_ptr=None):
         """cs_merge_apply_status: waits; raises CoslamHipError (CS_ERR_NUMERIC) naming the failed graph"""
-        check(self._L.cs_merge_apply_status(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr))), "cs_merge_apply_status")
+        check(self._L.cs_merge_apply_status(self._m, self._stream(stream_ptr)), "cs_merge_apply_status")
 
 
 def merge_first_constrain(frames, self_motion, cam_ids):
@@ -355,7 +344,7 @@ def merge_first_constrain(frames, self_motion, cam_ids):
     ids = np.ascontiguousarray(cam_ids, dtype=np.int32)
     of, oc = np.zeros(2 * max(len(ids), 1), np.int32), np.zeros(2 * max(len(ids), 1), np.int32)
     fc = C.c_int(-1)
-    p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+    p = lambda v: v.ctypes.data  # noqa: E731
     check(lib().cs_merge_first_constrain(len(fr), p(fr), p(sm), sm.shape[1], len(ids), p(ids), C.byref(fc), p(of), p(oc)), "cs_merge_first_constrain")
     return fc.value, [(int(f), int(c)) for f, c in zip(of[:2 * len(ids)], oc[:2 * len(ids)])]
 
@@ -365,16 +354,14 @@ MERGE_VIEW_FROM_M2, MERGE_VIEW_DETACHED, MERGE_VIEW_PREV, MERGE_VIEW_PREV_DETACH
 
 
 class MergeConstraintsHeader(C.Structure):
-    """== cs_merge_constraints_header (include/coslam_hip.h)."""
-
+    _c_type_ = "cs_merge_constraints_header"
     _fields_ = [(n, C.c_int) for n in ("verdict", "nPose", "P", "nObs", "nMergedTracks", "nUnmerged", "nPrevViews", "skippedMatches", "nMergeViews",
                                        "f1", "f2", "nCamIds")] + [("camIds", C.c_int * MAX_CAMS), ("nInfo", C.c_int), ("reserved", C.c_int),
                                                                   ("avgErr", C.c_double)]
 
 
 class MergeConstraintsBuffers(C.Structure):
-    """== cs_merge_constraints_buffers (include/coslam_hip.h)."""
-
+    _c_type_ = "cs_merge_constraints_buffers"
     _fields_ = [(n, C.c_void_p) for n in ("header", "views", "Ks", "Rs", "Ts", "pts", "pointMap", "obsPtr", "obsCam", "obsXY", "info", "infoValid",
                                           "infoR", "infoT")] + [(n, C.c_int) for n in ("maxPoints", "maxObs", "maxViews", "maxInfo")] + \
                [(n, C.c_void_p) for n in ("solvedRs", "solvedTs", "solvedPts", "outlier")]
@@ -400,30 +387,28 @@ class MergeConstraints(_MergeHandle):
         import numpy as np
         import torch
 
-        vp = C.c_void_p
         arr = merge_cams(cams)
-        head = (vp(self._m), vp(history._h), vp(self._stream(stream_ptr)), arr, vp(d_featRef), int(nMap), vp(d_mapPts), vp(d_groups), int(gId1),
-                int(gId2), int(maxiCam), int(maxjCam), int(f1), int(f2))
+        head = (self._m, history._h, self._stream(stream_ptr), arr, d_featRef, int(nMap), d_mapPts, d_groups, int(gId1), int(gId2), int(maxiCam),
+                int(maxjCam), int(f1), int(f2))
         if isinstance(matches, torch.Tensor) and matches.is_cuda:
             dm = matches.to(torch.int32).reshape(-1, 2).contiguous()
             self._keep = dm
-            check(self._L.cs_merge_constraints_assemble_dev(*head, vp(dm.data_ptr()) if dm.shape[0] else None, int(dm.shape[0])),
+            check(self._L.cs_merge_constraints_assemble_dev(*head, dm.data_ptr() if dm.shape[0] else None, int(dm.shape[0])),
                   "cs_merge_constraints_assemble_dev")
         else:
             hm = np.ascontiguousarray(np.asarray(matches, dtype=np.int32).reshape(-1, 2))
-            check(self._L.cs_merge_constraints_assemble(*head, vp(hm.ctypes.data) if len(hm) else None, len(hm)), "cs_merge_constraints_assemble")
+            check(self._L.cs_merge_constraints_assemble(*head, hm.ctypes.data if len(hm) else None, len(hm)), "cs_merge_constraints_assemble")
 
     def info(self, d_groups, gId1, gId2, d_Rs=None, d_Ts=None, stream_ptr=None):
         """cs_merge_info_dev from the poses d_Rs / d_Ts (device pointers, [nPose][9] / [3] in the assembled order; default: the assembled,
         unsolved poses).  Enqueues only."""
-        vp = C.c_void_p
-        check(self._L.cs_merge_info_dev(vp(self._m), vp(self._stream(stream_ptr)), vp(d_groups), int(gId1), int(gId2),
-                                        vp(self.buf.Rs if d_Rs is None else d_Rs), vp(self.buf.Ts if d_Ts is None else d_Ts)), "cs_merge_info_dev")
+        check(self._L.cs_merge_info_dev(self._m, self._stream(stream_ptr), d_groups, int(gId1), int(gId2), self.buf.Rs if d_Rs is None else d_Rs,
+                                        self.buf.Ts if d_Ts is None else d_Ts), "cs_merge_info_dev")
 
     def solve(self, stream_ptr=None):
         """cs_merge_constraints_solve: the two solves of :646-647 on the assembled problem (the existing robust BA, fed the problem read
         back to the host); waits.  Nothing is solved behind a verdict other than MERGE_OK; a failed solve raises CoslamHipError."""
-        check(self._L.cs_merge_constraints_solve(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr))), "cs_merge_constraints_solve")
+        check(self._L.cs_merge_constraints_solve(self._m, self._stream(stream_ptr)), "cs_merge_constraints_solve")
 
     def solution(self, which):
         """-> dict(Rs, Ts, pts, outlier, stats) of solve `which` (0: maxErr 800, 1 x 100; 1: maxErr 30, 5 x 30) of the last solve()"""
@@ -434,15 +419,15 @@ class MergeConstraints(_MergeHandle):
         h = self.header()
         Rs, Ts, pts = np.zeros((h.nPose, 9)), np.zeros((h.nPose, 3)), np.zeros((h.P, 3))
         out, st = np.zeros(max(h.nObs, 1), np.int32), BAStats()
-        p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
-        check(self._L.cs_merge_constraints_solution(C.c_void_p(self._m), int(which), p(Rs), p(Ts), p(pts), p(out), C.byref(st)),
+        p = lambda v: v.ctypes.data  # noqa: E731
+        check(self._L.cs_merge_constraints_solution(self._m, int(which), p(Rs), p(Ts), p(pts), p(out), C.byref(st)),
               "cs_merge_constraints_solution")
         return dict(Rs=Rs, Ts=Ts, pts=pts, outlier=out[:h.nObs], stats=st)
 
     def info_solved(self, d_groups, gId1, gId2, stream_ptr=None):
         """cs_merge_constraints_info_dev: the MergeInfo list from the SOLVED poses; nInfo = 0 behind a rejected verdict, a failed solve or
         no solve at all.  Enqueues only."""
-        check(self._L.cs_merge_constraints_info_dev(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.c_void_p(d_groups), int(gId1),
+        check(self._L.cs_merge_constraints_info_dev(self._m, self._stream(stream_ptr), d_groups, int(gId1),
                                                     int(gId2)), "cs_merge_constraints_info_dev")
 
     def apply_map(self, d_slot2map, d_pointFeat, d_featRef, d_refStatic, nMap, d_mapPts=None, apply_points=True, d_counts=None, stream_ptr=None):
@@ -458,14 +443,14 @@ class MergeConstraints(_MergeHandle):
         if len(ptrs) != self.n_cams:
             raise ValueError(f"apply_map: {len(ptrs)} slot2map pointers, the handle has {self.n_cams} cameras")
         arr = (vp * self.n_cams)(*[vp(int(p)) if p else None for p in ptrs])
-        check(self._L.cs_merge_constraints_apply_map_dev(vp(self._m), vp(self._stream(stream_ptr)), arr, vp(d_pointFeat), vp(d_featRef),
-                                                         vp(d_refStatic), int(nMap), vp(d_mapPts), 1 if apply_points else 0, vp(d_counts)),
+        check(self._L.cs_merge_constraints_apply_map_dev(self._m, self._stream(stream_ptr), arr, d_pointFeat, d_featRef, d_refStatic, int(nMap),
+                                                         d_mapPts, 1 if apply_points else 0, d_counts),
               "cs_merge_constraints_apply_map_dev")
 
     def header(self, stream_ptr=None):
         """the header on the host; waits for the stream"""
         h = MergeConstraintsHeader()
-        check(self._L.cs_merge_constraints_header_get(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), C.byref(h)),
+        check(self._L.cs_merge_constraints_header_get(self._m, self._stream(stream_ptr), C.byref(h)),
               "cs_merge_constraints_header_get")
         return h
 
@@ -675,27 +660,25 @@ MERGE_MATCH_PAIRS_OVERFLOW, MERGE_MATCH_MATCHES_OVERFLOW = 1, 2
 
 
 class MergeMatchCam(C.Structure):
-    """== cs_merge_match_cam (include/coslam_hip.h): xy / state / imgSmall device pointers, K a HOST pointer."""
+    """xy / state / imgSmall device pointers, K a HOST pointer."""
 
+    _c_type_ = "cs_merge_match_cam"
     _fields_ = [("xy", C.c_void_p), ("state", C.c_void_p), ("K", C.c_void_p), ("imgSmall", C.c_void_p), ("imgScale", C.c_double)]
 
 
 class MergeMatchJob(C.Structure):
-    """== cs_merge_match_job."""
-
+    _c_type_ = "cs_merge_match_job"
     _fields_ = [("iCam", C.c_int), ("jCam", C.c_int), ("E", C.c_double * 9), ("nSeeds", C.c_int), ("seeds", C.c_void_p)]
 
 
 class MergeMatchBuffers(C.Structure):
-    """== cs_merge_match_buffers."""
-
+    _c_type_ = "cs_merge_match_buffers"
     _fields_ = [(n, C.c_void_p) for n in ("matches", "scores", "counts", "pairs", "pairCount", "blocks", "abc", "valid")] + \
                [(n, C.c_int) for n in ("nCams", "N", "maxJobs", "maxSeeds", "pairCap", "maxMatches")]
 
 
 class MergeMatchChoice(C.Structure):
-    """== cs_merge_match_choice."""
-
+    _c_type_ = "cs_merge_match_choice"
     _fields_ = [(n, C.c_int) for n in ("status", "entry", "maxk", "maxiCam", "maxjCam", "maxgId1", "maxgId2", "gid1", "gid2", "camid1", "camid2")]
 
     def as_dict(self):
@@ -715,7 +698,7 @@ def merge_match_fmat(K1, K2, E):
 
     a, b, e = (np.ascontiguousarray(v, dtype=np.float64).reshape(9) for v in (K1, K2, E))
     F = np.zeros(9)
-    p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+    p = lambda v: v.ctypes.data  # noqa: E731
     check(lib().cs_merge_match_fmat(p(a), p(b), p(e), p(F)), "cs_merge_match_fmat")
     return F
 
@@ -739,7 +722,7 @@ def merge_match_select(infos, surf_num, emat_ok, ncc_num, group_size, eligible=N
     gs = np.zeros(MAX_CAMS, np.int32)
     gs[:len(group_size)] = np.asarray(group_size, dtype=np.int32)
     el = None if eligible is None else np.ascontiguousarray(np.asarray(eligible) != 0, dtype=np.uint8).reshape(-1)
-    p = lambda v: C.c_void_p(v.ctypes.data) if v is not None and len(v) else None  # noqa: E731
+    p = lambda v: v.ctypes.data if v is not None and len(v) else None  # noqa: E731
     out = MergeMatchChoice()
     check(lib().cs_merge_match_select(n, arr, p(sn), p(ok), p(nn), p(el), p(gs), C.byref(out)), "cs_merge_match_select")
     return out.as_dict()
@@ -764,7 +747,6 @@ class MergeMatcher(_MergeHandle):
         Enqueues only."""
         import numpy as np
 
-        vp = C.c_void_p
         ca = (MergeMatchCam * max(len(cams), 1))()
         keep = []
         for a, c in zip(ca, cams):
@@ -779,8 +761,8 @@ class MergeMatcher(_MergeHandle):
             a.E[:] = [float(v) for v in np.asarray(j["E"], dtype=np.float64).reshape(9)]
         if len(cams) != self.n_cams:
             raise ValueError(f"MergeMatcher.run: {len(cams)} cameras, the handle has {self.n_cams}")
-        check(self._L.cs_merge_match_run_dev(vp(self._m), vp(self._stream(stream_ptr)), ca, int(Ws), int(Hs), len(jobs), ja if len(jobs) else None,
-                                             C.c_double(epi_max), C.c_double(ncc_min), C.c_double(max_disp)), "cs_merge_match_run_dev")
+        check(self._L.cs_merge_match_run_dev(self._m, self._stream(stream_ptr), ca, int(Ws), int(Hs), len(jobs), ja if len(jobs) else None, epi_max,
+                                             ncc_min, max_disp), "cs_merge_match_run_dev")
 
     def from_pairs(self, d_pairs, d_pair_count, d_xy1, d_xy2, seeds=None, max_disp=150.0, stream_ptr=None):
         """cs_merge_match_from_pairs_dev: the matcher alone.  Per job a device pointer to its cs_ncc_pair records, to its count, to the
@@ -794,15 +776,15 @@ class MergeMatcher(_MergeHandle):
                for s in (seeds if seeds is not None else [None] * n)]
         ns = (C.c_int * max(n, 1))(*[len(s) for s in sds])
         sp = (vp * max(n, 1))(*[vp(s.ctypes.data) if len(s) else None for s in sds])
-        check(self._L.cs_merge_match_from_pairs_dev(vp(self._m), vp(self._stream(stream_ptr)), n, arr(d_pairs), arr(d_pair_count), arr(d_xy1),
-                                                    arr(d_xy2), ns, sp, C.c_double(max_disp)), "cs_merge_match_from_pairs_dev")
+        check(self._L.cs_merge_match_from_pairs_dev(self._m, self._stream(stream_ptr), n, arr(d_pairs), arr(d_pair_count), arr(d_xy1), arr(d_xy2), ns,
+                                                    sp, max_disp), "cs_merge_match_from_pairs_dev")
 
     def counts(self, n_jobs, stream_ptr=None):
         """cs_merge_match_counts: the stage's one host wait -> int32 [n_jobs][4] = matches kept, flags, candidates, rounds"""
         import numpy as np
 
         out = np.zeros((max(int(n_jobs), 1), 4), np.int32)
-        check(self._L.cs_merge_match_counts(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), int(n_jobs), C.c_void_p(out.ctypes.data)),
+        check(self._L.cs_merge_match_counts(self._m, self._stream(stream_ptr), int(n_jobs), out.ctypes.data),
               "cs_merge_match_counts")
         return out[:int(n_jobs)]
 
@@ -839,8 +821,8 @@ class MergeMatcher(_MergeHandle):
 def ncc_small_image_dev(stream_ptr, d_img, W, H, scale, d_small, device=0):
     """cs_ncc_small_image_dev: SingleSLAM's small image, cv::resize(img, small, Size((int)(W s), (int)(H s))) -> (Ws, Hs); enqueues only"""
     ws, hs = C.c_int(), C.c_int()
-    check(lib().cs_ncc_small_dims(int(W), int(H), C.c_double(scale), C.byref(ws), C.byref(hs)), "cs_ncc_small_dims")
-    check(lib().cs_ncc_small_image_dev(int(device), C.c_void_p(stream_ptr), C.c_void_p(d_img), int(W), int(H), C.c_double(scale), C.c_void_p(d_small)),
+    check(lib().cs_ncc_small_dims(int(W), int(H), scale, C.byref(ws), C.byref(hs)), "cs_ncc_small_dims")
+    check(lib().cs_ncc_small_image_dev(int(device), stream_ptr, d_img, int(W), int(H), scale, d_small),
           "cs_ncc_small_image_dev")
     return ws.value, hs.value
 
@@ -850,26 +832,24 @@ MERGE_FRONT_TOO_FEW, MERGE_FRONT_NO_MODEL = 1, 2
 
 
 class MergeFrontCam(C.Structure):
-    """== cs_merge_front_cam (include/coslam_hip.h): pts / desc device pointers, K a HOST pointer."""
+    """pts / desc device pointers, K a HOST pointer."""
 
+    _c_type_ = "cs_merge_front_cam"
     _fields_ = [("pts", C.c_void_p), ("desc", C.c_void_p), ("K", C.c_void_p), ("n", C.c_int)]
 
 
 class MergeFrontJob(C.Structure):
-    """== cs_merge_front_job."""
-
+    _c_type_ = "cs_merge_front_job"
     _fields_ = [("iCam", C.c_int), ("jCam", C.c_int)]
 
 
 class MergeFrontResult(C.Structure):
-    """== cs_merge_front_result."""
-
+    _c_type_ = "cs_merge_front_result"
     _fields_ = [(n, C.c_int) for n in ("surfNum", "ematOk", "inlierNum", "rounds", "bestHyp", "flags")] + [("E", C.c_double * 9), ("epiErr", C.c_double)]
 
 
 class MergeFrontBuffers(C.Structure):
-    """== cs_merge_front_buffers."""
-
+    _c_type_ = "cs_merge_front_buffers"
     _fields_ = [(n, C.c_void_p) for n in ("matches", "dist", "count", "inlierFlag", "seeds", "newMatches", "results", "hypSample", "hypCount",
                                           "hypE", "pix", "valid")] + [(n, C.c_int) for n in ("nCams", "maxPts", "dimDesc", "maxJobs", "maxHyp")]
 
@@ -903,18 +883,15 @@ class MergeFront(_MergeHandle):
     def enqueue(self, cams, pairs, ratio=0.8, max_dist=0.6, n_ransac=200, max_epi_err=2.0, min_inlier_num=15, seed=0, stream_ptr=None):
         """cs_merge_front_run_dev.  cams: per camera a dict pts [n][2] f64, desc [n][dim] f32 (device pointers), n, K (9 doubles, HOST array);
         pairs: [(iCam, jCam)].  The defaults are the reference's call (0.8, 0.6; 200, 2.0, 15).  Enqueues only."""
-        vp = C.c_void_p
         ca, ja, _keep = self._tables(cams, pairs)
-        check(self._L.cs_merge_front_run_dev(vp(self._m), vp(self._stream(stream_ptr)), ca, len(pairs), ja if len(pairs) else None,
-                                             C.c_double(ratio), C.c_double(max_dist), int(n_ransac), C.c_double(max_epi_err),
-                                             int(min_inlier_num), C.c_ulonglong(int(seed))), "cs_merge_front_run_dev")
+        check(self._L.cs_merge_front_run_dev(self._m, self._stream(stream_ptr), ca, len(pairs), ja if len(pairs) else None, ratio, max_dist,
+                                             int(n_ransac), max_epi_err, int(min_inlier_num), int(seed)), "cs_merge_front_run_dev")
 
     def match(self, cams, pairs, ratio=0.8, max_dist=0.6, stream_ptr=None):
         """cs_merge_front_match_dev: the descriptor stage alone.  Enqueues only."""
-        vp = C.c_void_p
         ca, ja, _keep = self._tables(cams, pairs)
-        check(self._L.cs_merge_front_match_dev(vp(self._m), vp(self._stream(stream_ptr)), ca, len(pairs), ja if len(pairs) else None,
-                                               C.c_double(ratio), C.c_double(max_dist)), "cs_merge_front_match_dev")
+        check(self._L.cs_merge_front_match_dev(self._m, self._stream(stream_ptr), ca, len(pairs), ja if len(pairs) else None, ratio,
+                                               max_dist), "cs_merge_front_match_dev")
 
     def from_matches(self, cams, pairs, matches, n_ransac=200, max_epi_err=2.0, min_inlier_num=15, seed=0, stream_ptr=None):
         """cs_merge_front_from_matches_dev: the RANSAC stage alone (computeEMat's shape); matches: per job a host int [n][2].  Enqueues only."""
@@ -928,8 +905,8 @@ class MergeFront(_MergeHandle):
             raise ValueError("MergeFront.from_matches: one match list per job")
         mp = (vp * max(n, 1))(*[vp(m.ctypes.data) if len(m) else None for m in ms])
         nm = (C.c_int * max(n, 1))(*[len(m) for m in ms])
-        check(self._L.cs_merge_front_from_matches_dev(vp(self._m), vp(self._stream(stream_ptr)), ca, n, ja if n else None, mp, nm, int(n_ransac),
-                                                      C.c_double(max_epi_err), int(min_inlier_num), C.c_ulonglong(int(seed))),
+        check(self._L.cs_merge_front_from_matches_dev(self._m, self._stream(stream_ptr), ca, n, ja if n else None, mp, nm, int(n_ransac), max_epi_err,
+                                                      int(min_inlier_num), int(seed)),
               "cs_merge_front_from_matches_dev")
 
     def results(self, n_jobs, stream_ptr=None):
@@ -937,7 +914,7 @@ class MergeFront(_MergeHandle):
         import numpy as np
 
         arr = (MergeFrontResult * max(int(n_jobs), 1))()
-        check(self._L.cs_merge_front_results(C.c_void_p(self._m), C.c_void_p(self._stream(stream_ptr)), int(n_jobs), arr), "cs_merge_front_results")
+        check(self._L.cs_merge_front_results(self._m, self._stream(stream_ptr), int(n_jobs), arr), "cs_merge_front_results")
         return [dict(surf_num=int(r.surfNum), emat_ok=int(r.ematOk), inlier_num=int(r.inlierNum), rounds=int(r.rounds), best_hyp=int(r.bestHyp),
                      flags=int(r.flags), E=np.array(list(r.E)), epi_err=float(r.epiErr)) for r in arr[:int(n_jobs)]]
 

@@ -39,11 +39,9 @@ class NativeComm:
 
         from ._lib import CoslamHipError, check, lib
 
-        self._L, self._C = lib(), C
+        self._L = lib()
         self.world, self.rank, self.device = world, rank, device
         L = self._L
-        L.cs_comm_create.restype = C.c_void_p
-        L.cs_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         self.comms = []
         # no rank may enter ncclCommInitRank unless ALL can: (1) every rank can load RCCL (one all-reduce), (2) rank 0's unique id arrives
         # with a flag that says it was created -- a failure then raises on EVERY rank instead of leaving the others waiting
@@ -69,11 +67,10 @@ class NativeComm:
             h = L.cs_comm_create(ident, world, rank, device)
             if not h:
                 raise CoslamHipError("cs_comm_create: " + L.cs_last_error().decode())
-            self.comms.append(C.c_void_p(h))
+            self.comms.append(h)
         self.exchange_comm, self.ba_comm = self.comms
 
     def close(self):
-        self._L.cs_comm_destroy.argtypes = [self._C.c_void_p]
         for c in self.comms:
             self._L.cs_comm_destroy(c)
         self.comms = []
@@ -93,17 +90,13 @@ class CameraExchange:
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self._x = None
         if native is not None:
-            import ctypes as C
-
             from ._lib import CoslamHipError
 
             L = native._L
-            L.cs_exchange_create.restype = C.c_void_p
-            L.cs_exchange_create.argtypes = [C.c_void_p, C.c_int, C.c_int]
             h = L.cs_exchange_create(native.exchange_comm, cams_per_rank, n_features // cams_per_rank)
             if not h:
                 raise CoslamHipError("cs_exchange_create: " + L.cs_last_error().decode())
-            self._x = C.c_void_p(h)
+            self._x = h
             self.world = native.world
             return
         w = record_words(n_features // cams_per_rank) * cams_per_rank   # per-camera records back to back
@@ -141,8 +134,7 @@ class CameraExchange:
             dests, R, t = self._pending
             arr = (C.c_void_p * len(dests))(*[d.data_ptr() for d in dests])
             s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
-            check(self.native._L.cs_exchange_allgather_dev(self._x, C.c_void_p(s), arr, C.c_void_p(R.data_ptr()),
-                                                           C.c_void_p(t.data_ptr())), "cs_exchange_allgather_dev")
+            check(self.native._L.cs_exchange_allgather_dev(self._x, s, arr, R.data_ptr(), t.data_ptr()), "cs_exchange_allgather_dev")
             return None
         if self.world == 1:
             self.recv.copy_(self.send, non_blocking=True)
@@ -176,12 +168,10 @@ class CameraExchange:
         """every gathered camera's R | t into d_R [world * cams_per_rank, 9] / d_t [.., 3] (torch f64 tensors on this device), on
         `stream`; skip_own: this rank's own cameras are left alone (the pose solve wrote them in place)"""
         if self._x is not None:
-            import ctypes as C
-
             from ._lib import check
 
             s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
-            check(self.native._L.cs_exchange_unpack_poses_dev(self._x, C.c_void_p(s), C.c_void_p(d_R.data_ptr()), C.c_void_p(d_t.data_ptr()),
+            check(self.native._L.cs_exchange_unpack_poses_dev(self._x, s, d_R.data_ptr(), d_t.data_ptr(),
                                                               1 if skip_own else 0), "cs_exchange_unpack_poses_dev")
             return
         n1 = self.n // self.cams
@@ -202,14 +192,11 @@ class CameraExchange:
         if self.world == 1:
             return
         if self._x is not None:
-            import ctypes as C
-
             from ._lib import check
 
             s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
             L = self.native._L
-            L.cs_comm_broadcast_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-            check(L.cs_comm_broadcast_dev(self.native.exchange_comm, C.c_void_p(s), C.c_void_p(ptr), int(nbytes), int(root)),
+            check(L.cs_comm_broadcast_dev(self.native.exchange_comm, s, ptr, int(nbytes), int(root)),
                   "cs_comm_broadcast_dev")
             return
         t = torch.as_tensor(_DevArray(ptr, nbytes, "|u1"), device=torch.device("cuda", device))
@@ -219,7 +206,6 @@ class CameraExchange:
 
     def close(self):
         if self._x is not None:
-            self.native._L.cs_exchange_destroy.argtypes = [self.native._C.c_void_p]
             self.native._L.cs_exchange_destroy(self._x)
             self._x = None
 
@@ -314,12 +300,11 @@ class HipSlicedBA:
 
         from ._lib import check
 
-        self.ws, self.stream, self._check, self._C = ws, stream, check, C
+        self.ws, self.stream, self._check = ws, stream, check
         L = ws._L
         vp = C.c_void_p
-        check(L.cs_ba_dist_begin(ws._h, vp(stream.cuda_stream), ws.C, ws.P, ws.nObs, vp(d_Rs0), vp(d_Ts0), vp(d_pts0),
-                                 int(nCamsCon), int(nPtsCon), C.c_double(maxErr), int(innerMaxIter), int(pLo), int(pHi),
-                                 1 if add_lambda else 0), "cs_ba_dist_begin")
+        check(L.cs_ba_dist_begin(ws._h, stream.cuda_stream, ws.C, ws.P, ws.nObs, d_Rs0, d_Ts0, d_pts0, int(nCamsCon), int(nPtsCon), maxErr,
+                                 int(innerMaxIter), int(pLo), int(pHi), 1 if add_lambda else 0), "cs_ba_dist_begin")
         pS, pscal, ppts, pout, nred = vp(), vp(), vp(), vp(), C.c_int(0)
         check(L.cs_ba_dist_buffers(ws._h, C.byref(pS), C.byref(nred), C.byref(pscal), C.byref(ppts), C.byref(pout)),
               "cs_ba_dist_buffers")
@@ -330,8 +315,7 @@ class HipSlicedBA:
         self.outlier = torch.as_tensor(_DevArray(pout.value, max(ws.nObs, 1), "<i4"), device=dev)
 
     def phase(self, ph):
-        self._check(self.ws._L.cs_ba_dist_phase(self.ws._h, self._C.c_void_p(self.stream.cuda_stream), int(ph)),
-                    "cs_ba_dist_phase")
+        self._check(self.ws._L.cs_ba_dist_phase(self.ws._h, self.stream.cuda_stream, int(ph)), "cs_ba_dist_phase")
 
 
 def bundle_adjust_sliced(ws, stream, d_Rs0, d_Ts0, d_pts0, nCamsCon, nPtsCon, maxErr, maxIter, innerMaxIter, device,
@@ -340,14 +324,10 @@ def bundle_adjust_sliced(ws, stream, d_Rs0, d_Ts0, d_pts0, nCamsCon, nPtsCon, ma
     problem (already in `ws`) and receives the same result (ws.download()).  With `native` (a NativeComm) the whole
     schedule -- phases and RCCL all-reduces -- is enqueued by ONE C-ABI call (cs_ba_dist_solve)."""
     if native is not None:
-        import ctypes as C
-
         from ._lib import check
 
-        vp = C.c_void_p
-        check(ws._L.cs_ba_dist_solve(ws._h, native.ba_comm, vp(stream.cuda_stream), ws.C, ws.P, ws.nObs, vp(d_Rs0), vp(d_Ts0),
-                                     vp(d_pts0), int(nCamsCon), int(nPtsCon), C.c_double(maxErr), int(maxIter),
-                                     int(innerMaxIter)), "cs_ba_dist_solve")
+        check(ws._L.cs_ba_dist_solve(ws._h, native.ba_comm, stream.cuda_stream, ws.C, ws.P, ws.nObs, d_Rs0, d_Ts0, d_pts0, int(nCamsCon),
+                                     int(nPtsCon), maxErr, int(maxIter), int(innerMaxIter)), "cs_ba_dist_solve")
         return None
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0

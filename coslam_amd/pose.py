@@ -8,8 +8,9 @@ from ._lib import check, lib
 
 
 class IntraCamPoseOption(C.Structure):
-    """== class IntraCamPoseOption, src/slam/SL_IntraCamPose.h:19-57."""
+    """class IntraCamPoseOption, src/slam/SL_IntraCamPose.h:19-57."""
 
+    _c_type_ = "cs_pose_option"
     _fields_ = [
         ("maxIterLM", C.c_int), ("maxIterRW", C.c_int),
         ("epsErrorChangeLM", C.c_double), ("epsParamChangeLM", C.c_double), ("epsErrorChangeRW", C.c_double),
@@ -41,11 +42,8 @@ def intraCamEstimate(K, R0, t0, npts, prevErrs, Ms, ms, tau, opt=None, device=0)
     pe = None if prevErrs is None else _d(prevErrs).ravel()
     R_opt, t_opt = np.zeros(9), np.zeros(3)
     opt = opt or IntraCamPoseOption()
-    vp = C.c_void_p
-    rc = L.cs_pose_intracam(K.ctypes.data_as(vp), R0.ctypes.data_as(vp), t0.ctypes.data_as(vp), int(npts),
-                            None if pe is None else pe.ctypes.data_as(vp), Ms.ctypes.data_as(vp),
-                            ms.ctypes.data_as(vp), C.c_double(tau), R_opt.ctypes.data_as(vp), t_opt.ctypes.data_as(vp),
-                            C.byref(opt), int(device))
+    rc = L.cs_pose_intracam(K.ctypes.data, R0.ctypes.data, t0.ctypes.data, int(npts), None if pe is None else pe.ctypes.data, Ms.ctypes.data,
+                            ms.ctypes.data, tau, R_opt.ctypes.data, t_opt.ctypes.data, C.byref(opt), int(device))
     if rc < 0:
         check(rc, "cs_pose_intracam")
     return bool(rc), R_opt.reshape(3, 3), t_opt, opt
@@ -55,8 +53,5 @@ def intraCamEstimate_batch_dev(stream_ptr, nProb, ptsStride, d_K, d_R0, d_t0, d_
                                d_Ropt, d_topt, d_opt, d_ok, device=0):
     """Device-resident batch (one workgroup per camera); all d_* are device pointers (ints)."""
     L = lib()
-    vp = C.c_void_p
-    check(L.cs_pose_intracam_batch_dev(int(device), vp(stream_ptr), int(nProb), int(ptsStride), vp(d_K), vp(d_R0),
-                                       vp(d_t0), vp(d_npts), vp(d_prevErrs) if d_prevErrs else None, vp(d_Ms), vp(d_ms),
-                                       C.c_double(tau), vp(d_Ropt), vp(d_topt), vp(d_opt), vp(d_ok)),
-          "cs_pose_intracam_batch_dev")
+    check(L.cs_pose_intracam_batch_dev(int(device), stream_ptr, int(nProb), int(ptsStride), d_K, d_R0, d_t0, d_npts, d_prevErrs or None, d_Ms, d_ms,
+                                       tau, d_Ropt, d_topt, d_opt, d_ok), "cs_pose_intracam_batch_dev")

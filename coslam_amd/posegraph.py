@@ -33,7 +33,7 @@ class PoseGraphs:
         self.fixed, self.id1, self.id2 = cat(fx, np.uint8), cat(a, np.int32), cat(b, np.int32)
         self.n_nodes, self.n_edges = int(self.node_ptr[-1]), int(self.edge_ptr[-1])
         self._h = C.c_void_p()
-        p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+        p = lambda v: v.ctypes.data  # noqa: E731
         self.scale_id = None
         if scale_ids is not None:
             assert len(scale_ids) == len(graphs)
@@ -77,7 +77,7 @@ class PoseGraphs:
         edgeR = np.ascontiguousarray(edgeR, dtype=np.float64).reshape(self.n_edges, 9)
         edgeT = np.ascontiguousarray(edgeT, dtype=np.float64).reshape(self.n_edges, 3)
         newR, newT = np.zeros((self.n_nodes, 9)), np.zeros((self.n_nodes, 3))
-        p = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+        p = lambda v: v.ctypes.data  # noqa: E731
         if self.scale_id is not None:
             edgeS = np.zeros(self.n_edges)
             check(lib().cs_posegraph_relax_scaled(self._h, p(nodeR), p(nodeT), p(edgeR), p(edgeT), p(newR), p(newT), p(edgeS)),
@@ -87,34 +87,27 @@ class PoseGraphs:
         return newR, newT
 
     def relax_scaled_dev(self, stream_ptr, d_nodeR, d_nodeT, d_edgeR, d_edgeT, d_newR, d_newT, d_edgeS):
-        vp = C.c_void_p
-        check(lib().cs_posegraph_relax_scaled_dev(self._h, vp(stream_ptr), vp(d_nodeR), vp(d_nodeT), vp(d_edgeR), vp(d_edgeT), vp(d_newR),
-                                                  vp(d_newT), vp(d_edgeS)), "cs_posegraph_relax_scaled_dev")
+        check(lib().cs_posegraph_relax_scaled_dev(self._h, stream_ptr, d_nodeR, d_nodeT, d_edgeR, d_edgeT, d_newR, d_newT,
+                                                  d_edgeS), "cs_posegraph_relax_scaled_dev")
 
     def relax_dev(self, stream_ptr, d_nodeR, d_nodeT, d_edgeR, d_edgeT, d_newR, d_newT):
-        vp = C.c_void_p
-        check(lib().cs_posegraph_relax_dev(self._h, vp(stream_ptr), vp(d_nodeR), vp(d_nodeT), vp(d_edgeR), vp(d_edgeT), vp(d_newR),
-                                           vp(d_newT)), "cs_posegraph_relax_dev")
+        check(lib().cs_posegraph_relax_dev(self._h, stream_ptr, d_nodeR, d_nodeT, d_edgeR, d_edgeT, d_newR, d_newT), "cs_posegraph_relax_dev")
 
     def edges_dev(self, stream_ptr, d_nodeR, d_nodeT, d_edgeR, d_edgeT):
-        vp = C.c_void_p
-        check(lib().cs_posegraph_edges_dev(self._h, vp(stream_ptr), vp(d_nodeR), vp(d_nodeT), vp(d_edgeR), vp(d_edgeT)),
+        check(lib().cs_posegraph_edges_dev(self._h, stream_ptr, d_nodeR, d_nodeT, d_edgeR, d_edgeT),
               "cs_posegraph_edges_dev")
 
     def status(self, stream_ptr=None):
         """synchronises the stream; raises on a failed graph"""
-        check(lib().cs_posegraph_status(self._h, C.c_void_p(stream_ptr), None, None), "cs_posegraph_status")
+        check(lib().cs_posegraph_status(self._h, stream_ptr, None, None), "cs_posegraph_status")
 
 
 def posegraph_set_poses_dev(stream_ptr, n, d_nodeIdx, d_R, d_t, d_nodeR, d_nodeT, device=0):
-    vp = C.c_void_p
-    check(lib().cs_posegraph_set_poses_dev(int(device), vp(stream_ptr), int(n), vp(d_nodeIdx), vp(d_R), vp(d_t), vp(d_nodeR),
-                                           vp(d_nodeT)), "cs_posegraph_set_poses_dev")
+    check(lib().cs_posegraph_set_poses_dev(int(device), stream_ptr, int(n), d_nodeIdx, d_R, d_t, d_nodeR, d_nodeT), "cs_posegraph_set_poses_dev")
 
 
 class AfterBARec(C.Structure):
-    """== cs_posegraph_after_ba_rec (include/coslam_hip.h)."""
-
+    _c_type_ = "cs_posegraph_after_ba_rec"
     _fields_ = [("g", C.c_void_p), ("device", C.c_int), ("nCams", C.c_int), ("d_camNode", C.c_void_p), ("d_Rs", C.c_void_p),
                 ("d_Ts", C.c_void_p), ("d_nodeR", C.c_void_p), ("d_nodeT", C.c_void_p), ("d_edgeR", C.c_void_p),
                 ("d_edgeT", C.c_void_p), ("d_newR", C.c_void_p), ("d_newT", C.c_void_p)]

@@ -14,8 +14,7 @@ FLAG_UNMAPPED, FLAG_DYNAMIC, FLAG_MERGEABLE = 1, 2, 4
 
 
 class RegisterCam(C.Structure):
-    """== cs_register_cam (include/coslam_hip.h)."""
-
+    _c_type_ = "cs_register_cam"
     _fields_ = [(n, C.c_void_p) for n in ("K", "R", "t", "xy", "state", "slot2map", "isDynamic", "isStatic")]
 
 
@@ -34,16 +33,13 @@ def register_cams(cams):
 def register_search_dev(stream_ptr, cams, N, W, H, P, d_M, d_cov, d_pointFeat, sigmaSearch, maxDist, sigmaMerge, d_slot, d_m,
                         d_var, d_dist, d_flags, device=0):
     """cams: list of dicts of DEVICE pointers (ints) with the field names of cs_register_cam; outputs P x nCams tables."""
-    vp = C.c_void_p
-    check(lib().cs_register_search_dev(int(device), vp(stream_ptr), len(cams), register_cams(cams), int(N), int(W), int(H), int(P),
-                                       vp(d_M), vp(d_cov), vp(d_pointFeat), C.c_double(sigmaSearch), C.c_double(maxDist),
-                                       C.c_double(sigmaMerge), vp(d_slot), vp(d_m), vp(d_var), vp(d_dist), vp(d_flags)),
+    check(lib().cs_register_search_dev(int(device), stream_ptr, len(cams), register_cams(cams), int(N), int(W), int(H), int(P), d_M, d_cov,
+                                       d_pointFeat, sigmaSearch, maxDist, sigmaMerge, d_slot, d_m, d_var, d_dist, d_flags),
           "cs_register_search_dev")
 
 
 class RegisterPass(C.Structure):
-    """== cs_register_pass (include/coslam_hip.h)."""
-
+    _c_type_ = "cs_register_pass"
     _fields_ = [("P", C.c_int), ("sigmaSearch", C.c_double), ("maxDist", C.c_double), ("sigmaMerge", C.c_double)] + \
                [(n, C.c_void_p) for n in ("M", "cov", "pointFeat", "slot", "m", "var", "dist", "flags", "mapFlags")] + [("maxDistDynamic", C.c_double)] + \
                [("list", C.c_void_p)]
@@ -70,9 +66,8 @@ def register_list_current_dev(stream_ptr, nCams, nMap, d_mapCount, d_pointFeat, 
     """cs_register_list_current_cap_dev: the frame's current map points (a feature of this frame in some camera, below the live count, not
     false) as a compact list in map order -- what CoSLAM::currentMapPointsRegister walks (curMapPts).  listCap: at most that many are
     listed; the rest lose their candidate rows for this frame and are counted into d_overflow."""
-    vp = C.c_void_p
-    check(lib().cs_register_list_current_cap_dev(int(device), vp(stream_ptr), int(nCams), int(nMap), vp(d_mapCount), vp(d_pointFeat), vp(d_mapFlags),
-                                                 vp(d_list), vp(d_listCount), vp(d_slotTable), int(nMap if listCap is None else listCap), vp(d_overflow)),
+    check(lib().cs_register_list_current_cap_dev(int(device), stream_ptr, int(nCams), int(nMap), d_mapCount, d_pointFeat, d_mapFlags, d_list,
+                                                 d_listCount, d_slotTable, int(nMap if listCap is None else listCap), d_overflow),
           "cs_register_list_current_cap_dev")
 
 
@@ -81,9 +76,9 @@ def register_search_passes_dev(stream_ptr, cams, N, W, H, passes, device=0, cam0
     cam0 / nCamsRun: only these cameras' columns of the len(cams)-wide tables (cs_register_search_passes_range_dev)."""
     arr = register_passes(passes)
     ca = register_cams(cams)
-    check(lib().cs_register_search_passes_range_dev(int(device), C.c_void_p(stream_ptr), len(ca), int(cam0),
-                                                    int(len(ca) - cam0 if nCamsRun is None else nCamsRun), ca, int(N),
-                                                    int(W), int(H), len(arr), arr), "cs_register_search_passes_range_dev")
+    check(lib().cs_register_search_passes_range_dev(int(device), stream_ptr, len(ca), int(cam0),
+                                                    int(len(ca) - cam0 if nCamsRun is None else nCamsRun), ca, int(N), int(W), int(H), len(arr),
+                                                    arr), "cs_register_search_passes_range_dev")
 
 
 def register_search(W, H, Ks, Rs, ts, xy, state, slot2map, isDynamic, Ms, covs, pointFeat, sigmaSearch, maxDist, sigmaMerge,
@@ -115,50 +110,43 @@ def register_search(W, H, Ks, Rs, ts, xy, state, slot2map, isDynamic, Ms, covs, 
     var = np.zeros((P, nC, 4))
     dist = np.zeros((P, nC))
     flags = np.zeros((P, nC), dtype=np.int32)
-    vp = C.c_void_p
-    check(lib().cs_register_search(int(device), nC, register_cams(cams), int(N), int(W), int(H), int(P), vp(Ms.ctypes.data),
-                                   vp(covs.ctypes.data), vp(pf.ctypes.data), C.c_double(sigmaSearch), C.c_double(maxDist),
-                                   C.c_double(sigmaMerge), vp(slot.ctypes.data), vp(m.ctypes.data), vp(var.ctypes.data),
-                                   vp(dist.ctypes.data), vp(flags.ctypes.data)), "cs_register_search")
+    check(lib().cs_register_search(int(device), nC, register_cams(cams), int(N), int(W), int(H), int(P), Ms.ctypes.data, covs.ctypes.data,
+                                   pf.ctypes.data, sigmaSearch, maxDist, sigmaMerge, slot.ctypes.data, m.ctypes.data, var.ctypes.data,
+                                   dist.ctypes.data, flags.ctypes.data), "cs_register_search")
     return dict(slot=slot, m=m, var=var, dist=dist, flags=flags)
 
 
 def register_decide_scratch_bytes(nCams, N, P):
-    L = lib()
-    L.cs_register_decide_scratch_bytes.restype = C.c_size_t
-    return int(L.cs_register_decide_scratch_bytes(int(nCams), int(N), int(P)))
+    return lib().cs_register_decide_scratch_bytes(int(nCams), int(N), int(P))
 
 
 def register_decide_static_dev(stream_ptr, nCams, N, P, mapBase, d_slot, d_flags, d_mergeable, d_mapFlags, d_pointFeat, d_slot2map, d_attached,
                                d_regged, d_scratch, d_counts=0, device=0, n_sweeps=3, only_cam=-1, kinds=1):
     """cs_register_decide_kinds_dev (only_cam >= 0: ONE camera's loop of the reference; kinds 1: the certainly static points, 2: the
     certainly dynamic ones, 3: both): d_slot2map = list of nCams device pointers (or the prebuilt c_void_p array)"""
-    vp = C.c_void_p
     arr = d_slot2map if isinstance(d_slot2map, C.Array) else (C.c_void_p * nCams)(*[int(x) for x in d_slot2map])
-    check(lib().cs_register_decide_kinds_dev(int(device), vp(stream_ptr), int(nCams), int(N), int(P), int(mapBase), vp(d_slot), vp(d_flags),
-                                             vp(d_mergeable), vp(d_mapFlags), vp(d_pointFeat), arr, vp(d_attached), vp(d_regged),
-                                             vp(d_scratch), int(n_sweeps), vp(d_counts), int(only_cam), int(kinds)), "cs_register_decide_kinds_dev")
+    check(lib().cs_register_decide_kinds_dev(int(device), stream_ptr, int(nCams), int(N), int(P), int(mapBase), d_slot, d_flags, d_mergeable,
+                                             d_mapFlags, d_pointFeat, arr, d_attached, d_regged, d_scratch, int(n_sweeps), d_counts, int(only_cam),
+                                             int(kinds)), "cs_register_decide_kinds_dev")
     return arr
 
 
 def register_revisit_list_dev(stream_ptr, nCams, P, cap, first_round, d_pointFeat, d_attached, d_regIn, keep_in, d_visitLoop, d_nextLoop, d_list,
                               d_counts=0, device=0, d_regOutClear=0):
     """cs_register_revisit_list_dev: the points that registered in the previous round and are visited again in a later camera's loop"""
-    vp = C.c_void_p
-    check(lib().cs_register_revisit_list_dev(int(device), vp(stream_ptr), int(nCams), int(P), int(cap), int(bool(first_round)), vp(d_pointFeat),
-                                             vp(d_attached), vp(d_regIn), int(bool(keep_in)), vp(d_regOutClear), vp(d_visitLoop), vp(d_nextLoop), vp(d_list), vp(d_counts)),
+    check(lib().cs_register_revisit_list_dev(int(device), stream_ptr, int(nCams), int(P), int(cap), int(bool(first_round)), d_pointFeat, d_attached,
+                                             d_regIn, int(bool(keep_in)), d_regOutClear, d_visitLoop, d_nextLoop, d_list, d_counts),
           "cs_register_revisit_list_dev")
 
 
 def register_revisit_decide_dev(stream_ptr, nCams, N, P, cap, mapBase, kinds, d_list, d_nextLoop, d_visitLoop, d_slot, d_flags, d_mergeable, d_mapFlags,
                                 d_pointFeat, d_slot2map, d_attached, d_regOut, d_decideScratch, d_curList, d_curCount, curCap, d_counts=0, device=0, d_listCount=0):
     """cs_register_revisit_decide_dev: the listed points' walks in their next loop (see include/coslam_hip.h)"""
-    vp = C.c_void_p
     arr = d_slot2map if isinstance(d_slot2map, C.Array) else (C.c_void_p * nCams)(*[int(x) for x in d_slot2map])
-    check(lib().cs_register_revisit_decide_dev(int(device), vp(stream_ptr), int(nCams), int(N), int(P), int(cap), int(mapBase), int(kinds), vp(d_list),
-                                               vp(d_nextLoop), vp(d_visitLoop), vp(d_slot), vp(d_flags), vp(d_mergeable), vp(d_mapFlags),
-                                               vp(d_pointFeat), arr, vp(d_attached), vp(d_regOut), vp(d_decideScratch), vp(d_curList), vp(d_curCount),
-                                               int(curCap), vp(d_counts), vp(d_listCount)), "cs_register_revisit_decide_dev")
+    check(lib().cs_register_revisit_decide_dev(int(device), stream_ptr, int(nCams), int(N), int(P), int(cap), int(mapBase), int(kinds), d_list,
+                                               d_nextLoop, d_visitLoop, d_slot, d_flags, d_mergeable, d_mapFlags, d_pointFeat, arr, d_attached,
+                                               d_regOut, d_decideScratch, d_curList, d_curCount, int(curCap), d_counts,
+                                               d_listCount), "cs_register_revisit_decide_dev")
     return arr
 
 
@@ -167,12 +155,11 @@ def register_decide_kinds_rounds_dev(stream_ptr, nCams, N, P, mapBase, d_slot, d
     """cs_register_decide_kinds_rounds_dev: the single pass (self-settling launch, all cameras' loops) whose walks build the second visits'
     first list themselves -- d_rvLists [nRounds][rvCap] (cleared here), d_rvCounts [nRounds + 1] (the last entry, points beyond the lists, is
     not cleared), d_visitLoop / d_nextLoop [P]"""
-    vp = C.c_void_p
     arr = d_slot2map if isinstance(d_slot2map, C.Array) else (C.c_void_p * nCams)(*[int(x) for x in d_slot2map])
-    check(lib().cs_register_decide_kinds_rounds_dev(int(device), vp(stream_ptr), int(nCams), int(N), int(P), int(mapBase), vp(d_slot), vp(d_flags),
-                                                    vp(d_mergeable), vp(d_mapFlags), vp(d_pointFeat), arr, vp(d_attached), vp(d_regged), vp(d_scratch), 0,
-                                                    vp(d_counts), -1, int(kinds), vp(d_rvLists), int(rvCap), int(nRounds), vp(d_rvCounts), vp(d_visitLoop),
-                                                    vp(d_nextLoop)), "cs_register_decide_kinds_rounds_dev")
+    check(lib().cs_register_decide_kinds_rounds_dev(int(device), stream_ptr, int(nCams), int(N), int(P), int(mapBase), d_slot, d_flags, d_mergeable,
+                                                    d_mapFlags, d_pointFeat, arr, d_attached, d_regged, d_scratch, 0, d_counts, -1, int(kinds),
+                                                    d_rvLists, int(rvCap), int(nRounds), d_rvCounts, d_visitLoop,
+                                                    d_nextLoop), "cs_register_decide_kinds_rounds_dev")
     return arr
 
 
@@ -181,12 +168,11 @@ def register_revisit_decide_next_dev(stream_ptr, nCams, N, P, cap, mapBase, kind
                                      d_listCount=0, d_nextList=0, d_nextCount=0, d_overflow=0):
     """cs_register_revisit_decide_next_dev: cs_register_revisit_decide_dev whose walks append the points that registered again to the next
     round's list (d_nextList / d_nextCount: both or neither)"""
-    vp = C.c_void_p
     arr = d_slot2map if isinstance(d_slot2map, C.Array) else (C.c_void_p * nCams)(*[int(x) for x in d_slot2map])
-    check(lib().cs_register_revisit_decide_next_dev(int(device), vp(stream_ptr), int(nCams), int(N), int(P), int(cap), int(mapBase), int(kinds), vp(d_list),
-                                                    vp(d_nextLoop), vp(d_visitLoop), vp(d_slot), vp(d_flags), vp(d_mergeable), vp(d_mapFlags),
-                                                    vp(d_pointFeat), arr, vp(d_attached), vp(d_regOut), vp(d_decideScratch), vp(d_curList), vp(d_curCount),
-                                                    int(curCap), vp(d_counts), vp(d_listCount), vp(d_nextList), vp(d_nextCount), vp(d_overflow)),
+    check(lib().cs_register_revisit_decide_next_dev(int(device), stream_ptr, int(nCams), int(N), int(P), int(cap), int(mapBase), int(kinds), d_list,
+                                                    d_nextLoop, d_visitLoop, d_slot, d_flags, d_mergeable, d_mapFlags, d_pointFeat, arr, d_attached,
+                                                    d_regOut, d_decideScratch, d_curList, d_curCount, int(curCap), d_counts, d_listCount, d_nextList,
+                                                    d_nextCount, d_overflow),
           "cs_register_revisit_decide_next_dev")
     return arr
 
@@ -240,17 +226,12 @@ def register_revisit_rounds_dev(stream_ptr, history, reg_cams, pu_cams, W, H, se
     refine of the listed rows; an empty list ends it (at once when round 0's is).  history: a TrackHistory (coslam_amd.poseupdate)."""
     from .poseupdate import poseupdate_cams
 
-    vp = C.c_void_p
     nC = len(reg_cams)
     arr = d_slot2map if isinstance(d_slot2map, C.Array) else (C.c_void_p * nC)(*[int(x) for x in d_slot2map])
     sp = search_pass[0] if isinstance(search_pass, C.Array) else search_pass
-    f = lib().cs_register_revisit_rounds_dev
-    f.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, C.c_int,
-                  C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
-    check(f(vp(history._h), vp(stream_ptr), C.cast(register_cams(reg_cams), vp), C.cast(poseupdate_cams(pu_cams), vp), int(W), int(H),
-            C.cast(C.pointer(sp), vp), int(nMap), int(curFrame), int(mapBase), int(kinds), vp(d_mapPts), vp(d_mapCov), float(pixelErrVar),
-            float(tolPix), vp(d_mergeCache), vp(d_mergeable), vp(d_rvLists), vp(d_rvCounts), int(cap), int(nRounds), vp(d_visitLoop),
-            vp(d_nextLoop), vp(d_mapFlags), vp(d_pointFeat), C.cast(arr, vp), vp(d_attached), vp(d_regOut), vp(d_decideScratch), vp(d_curList),
-            vp(d_curCount), int(curCap), vp(d_rvCnt), vp(d_featRef), vp(d_refStatic), vp(d_frefCounts)),
-          "cs_register_revisit_rounds_dev")
+    check(lib().cs_register_revisit_rounds_dev(history._h, stream_ptr, register_cams(reg_cams), poseupdate_cams(pu_cams), int(W), int(H), C.byref(sp),
+                                               int(nMap), int(curFrame), int(mapBase), int(kinds), d_mapPts, d_mapCov, float(pixelErrVar),
+                                               float(tolPix), d_mergeCache, d_mergeable, d_rvLists, d_rvCounts, int(cap), int(nRounds), d_visitLoop,
+                                               d_nextLoop, d_mapFlags, d_pointFeat, arr, d_attached, d_regOut, d_decideScratch, d_curList, d_curCount,
+                                               int(curCap), d_rvCnt, d_featRef, d_refStatic, d_frefCounts), "cs_register_revisit_rounds_dev")
     return arr

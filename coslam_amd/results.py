@@ -9,8 +9,7 @@ from ._lib import check, lib
 
 
 class ExportCam(C.Structure):
-    """== cs_export_cam (include/coslam_hip.h)."""
-
+    _c_type_ = "cs_export_cam"
     _fields_ = [("videoFilePath", C.c_char_p), ("K", C.c_void_p), ("kc", C.c_void_p), ("W", C.c_int), ("H", C.c_int),
                 ("startFrameInVideo", C.c_int), ("nPoses", C.c_int), ("poseFrame", C.c_void_p), ("poseR", C.c_void_p),
                 ("poseT", C.c_void_p), ("featPtr", C.c_void_p), ("featPointId", C.c_void_p), ("featXY", C.c_void_p)]
@@ -38,15 +37,14 @@ def export_results_v1(dir_path, cams, cur_frame, pt_id, pt_M, pt_cov, cov_as_ref
     pt_M = np.ascontiguousarray(pt_M, np.float64).reshape(-1, 3)
     pt_cov = np.ascontiguousarray(pt_cov, np.float64).reshape(-1, 9)
     assert len(pt_M) == len(pt_id) == len(pt_cov)
-    p = lambda x: C.c_void_p(x.ctypes.data)  # noqa: E731
+    p = lambda x: x.ctypes.data  # noqa: E731
     path = dir_path if isinstance(dir_path, bytes) else str(dir_path).encode()
     check(lib().cs_export_results_v1(path, len(cams), arr, int(cur_frame), len(pt_id), p(pt_id), p(pt_M), p(pt_cov),
                                      1 if cov_as_reference else 0), "cs_export_results_v1")
 
 
 class LoopExportCam(C.Structure):
-    """== cs_loop_export_cam (include/coslam_hip.h)."""
-
+    _c_type_ = "cs_loop_export_cam"
     _fields_ = [("videoFilePath", C.c_char_p), ("K", C.c_void_p), ("kc", C.c_void_p), ("W", C.c_int), ("H", C.c_int),
                 ("startFrameInVideo", C.c_int)]
 
@@ -65,8 +63,7 @@ def loop_export_results(dir_path, history, stream_ptr, d_feat_ref, n_map, d_M, d
         a.K, a.kc = K.ctypes.data, kc.ctypes.data
         a.W, a.H, a.startFrameInVideo = int(c["W"]), int(c["H"]), int(c.get("startFrameInVideo", 0))
     stats = (C.c_longlong * 3)()
-    vp = C.c_void_p
     path = dir_path if isinstance(dir_path, bytes) else str(dir_path).encode()
-    check(lib().cs_loop_export_results(path, vp(history._h), vp(stream_ptr), vp(d_feat_ref), int(n_map), vp(d_M), vp(d_cov), vp(d_map_flags),
-                                       arr, 1 if cov_as_reference else 0, stats), "cs_loop_export_results")
+    check(lib().cs_loop_export_results(path, history._h, stream_ptr, d_feat_ref, int(n_map), d_M, d_cov, d_map_flags, arr,
+                                       1 if cov_as_reference else 0, stats), "cs_loop_export_results")
     return dict(points=int(stats[0]), features=int(stats[1]), features_from_archive=int(stats[2]))

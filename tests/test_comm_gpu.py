@@ -67,8 +67,6 @@ def test_single_rank_communicator_exchange_and_sliced_ba(hip):
     import ctypes as C
 
     L = coslam_amd.lib()
-    L.cs_comm_allgather_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.cs_comm_broadcast_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     send = torch.arange(0, 100003, dtype=torch.int32, device=dev)
     recv = torch.zeros_like(send)
     assert L.cs_comm_allgather_dev(comm.exchange_comm, C.c_void_p(s.cuda_stream), C.c_void_p(send.data_ptr()), C.c_void_p(recv.data_ptr()), send.numel() * 4) == 0
@@ -194,13 +192,6 @@ def _host_transport_worker(rank, world, name, out_dir):
     import torch
 
     L = coslam_amd.lib()
-    L.cs_comm_create_host.restype = C.c_void_p
-    L.cs_comm_create_host.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int]
-    L.cs_comm_destroy.argtypes = [C.c_void_p]
-    L.cs_comm_world.argtypes = [C.c_void_p]
-    L.cs_comm_rank.argtypes = [C.c_void_p]
-    L.cs_comm_allgather_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.cs_comm_broadcast_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     dev = torch.device("cuda:0")
     c = L.cs_comm_create_host(name.encode(), world, rank, 0)
     ok = bool(c) and L.cs_comm_world(c) == world and L.cs_comm_rank(c) == rank

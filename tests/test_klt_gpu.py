@@ -654,7 +654,6 @@ def test_cu_masked_stream_and_budget(hip):
     sc = Scene(1, W, H, 5000, seed=88)
     frames = [sc.render(0, f) for f in range(4)]
     lib = coslam_amd.lib()
-    lib.cs_stream_create_cu_range.restype = C.c_void_p
     n_cus = torch.cuda.get_device_properties(0).multi_processor_count
 
     def run(stream_ptr, cu_count):

@@ -1,7 +1,6 @@
 """The live view without a GPU: known answers, worked by hand, of the restatement of the curMapPts rule, CoSLAM::getNumDynamicStaticPoints,
 CoSLAM::storeDynamicPoints and getDynTracks (tests/liveview_ref.py; reference src/app/SL_CoSLAM.cpp:1182-1197, :1447-1471, :1900-1911,
 src/gui/GLScenePane.cpp:19-52), the C-ABI's new symbols and the loud failure of the wrappers where there is no device."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -95,10 +94,6 @@ def test_the_library_exports_the_live_view_entries_the_header_declares_them_and_
         assert hasattr(lib, s), s
         assert s + "(" in header, s
     assert coslam_amd.LiveView is liveview.LiveView
-    assert C.sizeof(liveview.MapCounts) == 4 * 34
-    assert C.sizeof(liveview.LiveHeader) == 4 * 8 + 4 * 34 + 8 * (16 * 9 + 16 * 3) + 4 * (1 + 16 + 256 + 16) + 3 * 4
-    assert C.sizeof(liveview.LiveHeader) % 8 == 0 and liveview.LiveHeader.R.offset % 8 == 0
-    assert liveview.LIVE_POINT_DTYPE.itemsize == 32 and liveview.LIVE_DYN_DTYPE.itemsize == 32
     assert liveview.map_counts_scratch_bytes() >= 4 * 35
 
 

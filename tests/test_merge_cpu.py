@@ -72,13 +72,10 @@ def test_the_info_list_follows_the_group_order_not_the_camera_order():
 
 
 def test_ctypes_structs_have_the_headers_sizes():
-    from coslam_amd.merge import MergeCam, MergeCandidates, MergeInfo
+    """(sizes and offsets against the compiler: tests/test_abi.py's table of mirrors)"""
+    from coslam_amd.merge import MergeCandidates
 
-    assert C.sizeof(MergeCam) == 6 * C.sizeof(C.c_void_p)
-    assert C.sizeof(MergeInfo) == 24
-    assert C.sizeof(MergeCandidates) == 16 + 256 * 24 + 16 * 4 + 2 * 256 * 4 + 256 + 256 * 8 == 10576
-    assert MergeCandidates.camDist.offset % 8 == 0 and MergeCandidates.info.offset == 16 and MergeCandidates.nFeat.offset == 16 + 6144
-    m = MergeCandidates.from_bytes(np.full(10576, 255, dtype=np.uint8).tobytes())
+    m = MergeCandidates.from_bytes(np.full(C.sizeof(MergeCandidates), 255, dtype=np.uint8).tobytes())
     assert m.nMergeInfo == -1 and m.inNum[15][15] == -1 and m.fromTo[3][4] == 255
     hdr = open(os.path.join(ROOT, "include", "coslam_hip.h")).read()
     for sym in ("cs_merge_check_dev", "cs_merge_check_scratch_bytes", "cs_merge_check", "cs_merge_cam", "cs_merge_info", "cs_merge_candidates"):

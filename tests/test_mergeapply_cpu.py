@@ -1,7 +1,6 @@
 """The merge's map and group side without a device: the restatement (tests/mergeapply_ref.py) against the reference's own
 updateStaticPointPositionAtKeyFrms (tests/golden/mergeapply_golden.npz), what the golden file has to hold, cs_merge_matched_groups (host
 code of the library) against the restatement, struct and symbol presence, and the end-to-end scene on the host."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -143,9 +142,6 @@ def test_symbols_and_structs():
     for name in ("cs_recompute_map_points_keyfrms_dev", "cs_merge_apply_create", "cs_merge_apply_run_dev", "cs_merge_apply_status",
                  "cs_merge_apply_guard", "cs_merge_apply_destroy", "cs_merge_matched_groups", "cs_track_history_set_span_guarded_dev"):
         assert hasattr(L, name), name
-    from coslam_amd.grouping import CameraGroups
-
-    assert C.sizeof(CameraGroups) == 4 * (1 + 16 + 256 + 16)
     hdr = open(os.path.join(ROOT, "include", "coslam_hip.h")).read()
     for name in ("cs_recompute_map_points_keyfrms_dev", "cs_merge_apply_run_dev", "cs_merge_matched_groups", "cs_track_history_set_span_guarded_dev"):
         assert name + "(" in hdr

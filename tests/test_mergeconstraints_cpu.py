@@ -1,7 +1,6 @@
 """The merge constraints on the host: the plain restatement tests/mergeconstraints_ref.py reproduces the reference's own
 MergeCameraGroup::genMergeInfoVer2 (tests/golden/mergeconstraints_golden.npz, recorded with a solver stand-in that changes nothing) bit for
 bit; cs_merge_first_constrain equals the reference's m_pFirstConstrainFrm and pose order; the library exports what the header declares."""
-import ctypes as C
 import os
 import re
 
@@ -91,7 +90,7 @@ def test_first_constrain_rule_and_refusals():
 
 
 def test_symbols_and_structs():
-    """every cs_merge_* name the header declares is exported, and the ctypes mirrors have the header's sizes"""
+    """every cs_merge_* name the header declares is exported (the mirrors' layouts: tests/test_abi.py's table)"""
     hdr = open(os.path.join(ROOT, "include", "coslam_hip.h")).read()
     names = sorted(set(re.findall(r"\b(cs_merge_[a-z_]+)\(", hdr)))
     for need in ("cs_merge_first_constrain", "cs_merge_constraints_create", "cs_merge_constraints_assemble_dev", "cs_merge_info_dev",
@@ -100,7 +99,4 @@ def test_symbols_and_structs():
     L = coslam_amd.lib()
     for name in names:
         assert hasattr(L, name), name
-    from coslam_amd.merge import MergeConstraintsBuffers, MergeConstraintsHeader
-
-    assert C.sizeof(MergeConstraintsHeader) == 4 * (12 + 16 + 2) + 8 and C.sizeof(MergeConstraintsBuffers) == 14 * 8 + 4 * 4 + 4 * 8
     assert all(hasattr(coslam_amd, n) for n in ("MergeConstraints", "merge_first_constrain"))

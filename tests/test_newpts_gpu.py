@@ -241,7 +241,6 @@ def test_bad_arguments_are_refused(hip):
     assert L.cs_newpts_from_pairs_dev(0, None, 1, 512, None, None, None, 16, None, None, None, None, None, None, None, None, 10, None, 0,
                                       C.c_double(80.0), C.c_double(3.0), C.c_double(10.0), 2, 640, 480, None, None) != 0
     assert b"cs_newpts_from_pairs_dev" in L.cs_last_error()
-    L.cs_newpts_scratch_bytes.restype = C.c_size_t
     assert L.cs_newpts_scratch_bytes(1, 512) == 0 and L.cs_newpts_scratch_bytes(4, 0) == 0
 
 

@@ -1,5 +1,5 @@
 """diagnostic: host time and device time of cs_klt_group_stage_h alone (8 x 640x480 images per call)"""
-import ctypes as C, os, sys, time
+import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, coslam_amd
 W, H, L, fw, fh, nc = 640, 480, 4, 50, 40, 8
@@ -9,7 +9,7 @@ for _ in range(nc):
     t = coslam_amd.KLT_SequenceTracker(cfg, 0); t.allocate(W, H, L, fw, fh); ts.append(t)
 grp = coslam_amd.KLT_TrackerGroup(ts)
 s = torch.cuda.Stream(); grp.set_stream(s.cuda_stream)
-lib = coslam_amd.lib(); lib.cs_pinned_alloc.restype = C.c_void_p; lib.cs_pinned_alloc.argtypes = [C.c_size_t]
+lib = coslam_amd.lib()
 for kind in ("torch_pinned", "cs_pinned", "pageable"):
     n = nc * W * H
     if kind == "torch_pinned":
