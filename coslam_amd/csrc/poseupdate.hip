@@ -3160,7 +3160,7 @@ extern "C" int cs_register_revisit_rounds_dev(cs_track_history* h, void* hip_str
     V.attached = d_attached, V.regOut = d_regOut, V.curList = d_curList, V.curCount = d_curCount, V.curCap = curCap, V.counts = d_rvCnt;
     V.nextLoopW = d_nextLoop, V.overflow = d_rvCounts + nRounds;
     V.debug = cs_debug_get(CS_DBG_MERGE_PRINT) == 1;
-    int* scr = (int*)d_decideScratch + (size_t)nCams * nMap + nMap;   // (cs_register_decide_kinds_dev's carve-up: code | base | owner x 3 | ...)
+    int* scr = rd_scratch_owners(d_decideScratch, nCams, nMap);   // (cs_register_decide_kinds_dev's carve-up: head | code | base | owner x 3 | ...)
     for (int k = 0; k < 3; ++k) V.owner[k] = scr, scr += (size_t)nCams * N;
     // advance + refine (cs_feat_ref_advance_refine_dev's, over a list, the marks consumed)
     ArArgs& R = A.ar;

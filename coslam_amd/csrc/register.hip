@@ -375,8 +375,9 @@ namespace {
 // that (a) are reached -- no earlier camera of the same walk met a feature mapped on arrival: mapped before the pass, or owned by a
 // step of smaller order -- and (b) may attach.  That is a recursion along a total order, so it has ONE solution, the sequential
 // result; Jacobi sweeps (every walk re-evaluated against the previous sweep's owners) reach it in as many sweeps as the longest
-// chain of walks cutting each other short -- two or three here.  One workgroup, a thread per point (its <= 16 candidate features and
-// their flags in registers), sweeps separated by workgroup barriers; the owners live in a caller-supplied scratch (L2-resident).
+// chain of walks cutting each other short -- two or three here.  A fixed number of sweeps as launches over all points (k_decide_sweep,
+// the owners in a caller-supplied scratch), or -- what the frame loops run -- as many as it takes, in the launch that builds the walks'
+// tables, among the few walks that can claim a feature at all (rd_resolve).
 // A point's later visits (it appears once per camera in which it has a feature) find what its first visit left and change nothing.
 struct RdArgs {
     int nCams, N, P, mapBase, nSweeps, onlyCam, kinds;
@@ -393,14 +394,15 @@ struct RdArgs {
     int* owner[3];                   // scratch 3 x [nCams * N]: the sweeps rotate through them
     int* counts;                     // [4] out: features attached, points regged, sweeps, converged
     int* unconverged;                // the scratch's last word: the NUMBER of calls whose sweeps did not settle (never cleared here)
-    int* timeouts;                   // the word before it: the number of those calls that ended on a grid-barrier TIME-OUT (the launch's workgroups
-                                     // were not co-resident within 20 ms: nothing was attached) -- apart from `sweeps ran out`
-    int* callFlag;                   // the word before it: this call has been counted
-    int* changed;                    // scratch [RD_MAX_SWEEPS]: sweep k changed an owner (the self-settling launch, k_decide_settle)
-    int* bar;                        // scratch [1]: its grid barrier's arrival counter
+    int* timeouts;                   // the word before it: calls that ended on a time-out.  Nothing here waits for anything any more: it
+                                     // stays 0 (both frame loops read it)
+    int* callFlag;                   // the word before it: this call has been counted (k_decide_sweep)
+    int* ticket;                     // the scratch's FIRST word: workgroups of the self-settling launch that have arrived (0 between calls)
+    int* nActive;                    // the word behind it: walks on the active list (0 between calls)
+    int* active;                     // scratch [P]: the points whose walk can claim a feature (the self-settling launch)
     // the second visits' first list built by the walks themselves (cs_register_decide_kinds_rounds_dev; null: not asked for): a point that
     // registered and holds a feature in a later camera's loop appends itself -- what k_revisit_list(firstRound) would find
-    int* rvLists;                    // [nRounds][rvCap]: cleared to -1 by the prepare launch, list 0 filled by the settle launch
+    int* rvLists;                    // [nRounds][rvCap]: cleared to -1 by the launch's prepare part, list 0 filled by its resolver
     int* rvCounts;                   // [nRounds]: cleared; [0] = points appended (may exceed rvCap: the rest is not visited again)
     int rvCap, nRounds;
     int* visitLoop;                  // [P]: the loop of a registered point's visit
@@ -408,42 +410,275 @@ struct RdArgs {
 };
 constexpr int RD_MAX_SWEEPS = 64;
 
-// entry-parallel (coalesced over the P x nCams tables): what every walk will see of (point, camera); the owners start at "nobody"
-__global__ __launch_bounds__(256) void k_decide_prepare(RdArgs A) {
-    const int k = blockIdx.x * 256 + threadIdx.x, C = A.nCams, nFeat = C * A.N;
-    for (int f = k; f < nFeat; f += gridDim.x * 256) A.owner[0][f] = RD_INF, A.owner[1][f] = RD_INF, A.owner[2][f] = RD_INF;
-    if (k < 4 && A.counts) A.counts[k] = k == 2 ? A.nSweeps : (k == 3 ? 1 : 0);   // (converged: cleared by the last launch when not)
-    if (k == 0) *A.callFlag = 0, *A.bar = 0;
-    if (k < RD_MAX_SWEEPS) A.changed[k] = 0;
-    if (A.rvLists) {
-        for (int f = k; f < A.nRounds * A.rvCap; f += gridDim.x * 256) A.rvLists[f] = -1;
-        if (k < A.nRounds) A.rvCounts[k] = 0;
+constexpr int RD_THREADS = 256;
+// the resolver's owners in LDS: open addressing on the feature, at most half full (else the owner arrays of the scratch, through L2)
+constexpr int RD_LDS_BITS = 10, RD_LDS_CELLS = 1 << RD_LDS_BITS, RD_LDS_ENTRIES = RD_LDS_CELLS / 2;
+
+// ---- the resolver of the self-settling launch: the ACTIVE walks among themselves ---------------------------------------------------------
+// A walk influences another only by claiming a feature, and it can only claim a candidate that is unmapped and mergeable with no candidate
+// mapped on arrival in front of it.  Every other walk claims nothing and attaches nothing whatever the owners say: the sweeps over the
+// active walks alone pass through the same owners, sweep for sweep, as the sweeps over all walks, and end on the same (unique) fixed point.
+// A listed walk's codes, cut where the walk ends whatever the owners say (a candidate mapped before the pass): what is left are its
+// unmapped candidates, the only features whose owners it reads or claims.  p < 0: no row.
+// owner array k mod 3 (selected, not indexed: the arguments then stay in registers -- no private segment)
+__device__ __forceinline__ int* rd_owner(const RdArgs& A, int k) {
+    const int r = k % 3;
+    return r == 0 ? A.owner[0] : (r == 1 ? A.owner[1] : A.owner[2]);
+}
+template <int MC>
+__device__ __forceinline__ void rd_row_load(const RdArgs& A, int p, int (&code)[MC], int& base) {
+    base = p >= 0 ? rd_ld(A.base + p) : -1;
+#pragma unroll
+    for (int i = 0; i < MC; ++i) code[i] = (p >= 0 && i < A.nCams) ? rd_ld(A.code + (size_t)i * A.P + p) : -1;   // (independent loads)
+    bool go = base >= 0;
+#pragma unroll
+    for (int i = 0; i < MC; ++i) {
+        if (go && code[i] >= 0 && (code[i] & RD_INIT_MAPPED)) go = false;
+        if (!go) code[i] = -1;
     }
-    if (k >= A.P * C) return;
-    const int p = k / C, i = k - p * C;
-    A.attached[k] = 0;
-    if (i == 0) A.regged[p] = 0;
-    int code = -1;
-    // the point's kind: 0 certainly static, 1 certainly dynamic (its walk takes DYNAMIC features only, :981), -1 not visited
-    const unsigned char fl = A.mapFlags[p] & (CS_MAP_DYNAMIC | CS_MAP_FALSE | CS_MAP_UNCERTAIN);
-    const int kind = (fl == 0 && (A.kinds & 1)) ? 0 : ((fl == CS_MAP_DYNAMIC && (A.kinds & 2)) ? 1 : -1);
-    if (A.pointFeat[k] < 0 && kind >= 0) {   // (else :736-737: the point has a feature of this frame there)
-        const int s = A.slot[k];
-        if (s >= 0 && s < A.N && ((A.flags[k] >> 1) & 1) == kind) {   // (else: nothing found / a feature of the other type, :757 / :981)
-            code = i * A.N + s;
-            if (A.slot2map[i][s] >= 0) code |= RD_INIT_MAPPED;
-            if (A.mergeable[k] == 1) code |= RD_CAN_MERGE;
+}
+// the owners in `fin` are final (or the best the sweeps reached): attach (k_decide_sweep's mode 1), and the second visits' first list.
+// The low bits of a code index `fin`: the feature itself, or (keys != null) the cell of the LDS table that holds it.
+template <int MC>
+__device__ __forceinline__ void rd_row_attach(const RdArgs& A, int p, const int (&code)[MC], int base, const int* fin, const int* keys) {
+    if (base < 0) return;
+    const int C = A.nCams;
+    bool go = true, reg = false;
+    int nAtt = 0;
+#pragma unroll
+    for (int i = 0; i < MC; ++i) {
+        if (go && code[i] >= 0) {
+            const int ord = base + i, cell = code[i] & RD_FEAT, own = rd_ld(fin + cell);
+            if (own < ord) {
+                go = false;                                    // mapped on arrival: the walk ends (:789-790)
+            } else if ((code[i] & RD_CAN_MERGE) && own == ord) {
+                const int s2 = (keys ? keys[cell] : cell) - i * A.N;
+                A.slot2map[i][s2] = A.mapBase + p;             // the feature and its predecessors on the track (:771-775): slot2map is per track
+                A.pointFeat[(size_t)p * C + i] = s2;            // MapPoint::addFeature
+                A.attached[(size_t)p * C + i] = 1;
+                reg = true, ++nAtt;
+            }
         }
     }
-    A.code[(size_t)i * A.P + p] = code;
-    if (i == 0) {   // the order of the point's walk = ((first camera in which it has a feature of this frame) x P + point) x nCams
-        int ofirst = -1;
-        for (int q = C - 1; q >= 0; --q)
-            if (A.pointFeat[(size_t)p * C + q] >= 0) ofirst = q;
-        // onlyCam >= 0: ONE camera's loop of the reference (:864-869): the points with a feature of this frame in that camera, map order
-        if (A.onlyCam >= 0) ofirst = A.pointFeat[(size_t)p * C + A.onlyCam] >= 0 ? 0 : -1;
-        A.base[p] = (ofirst >= 0 && kind >= 0) ? (ofirst * A.P + p) * C : -1;
+    if (reg) {
+        A.regged[p] = 1;
+        if (A.counts) atomicAdd(A.counts, nAtt), atomicAdd(A.counts + 1, 1);
+        if (A.rvLists && A.onlyCam < 0) {   // k_revisit_list's first round, by the walk itself
+            const int last = (base / C) / A.P;   // the loop of this visit: the first camera that held a feature before the pass (the prepare part)
+            A.visitLoop[p] = last;
+            int b = -1;
+            for (int c = C - 1; c > last; --c)
+                if (A.pointFeat[(size_t)p * C + c] >= 0) b = c;
+            if (b >= 0) {
+                const int q = atomicAdd(A.rvCounts, 1);
+                if (q < A.rvCap) A.rvLists[q] = p, A.nextLoop[p] = b;
+                else atomicAdd(A.rvCounts + A.nRounds, 1);   // (never cleared here: the points beyond the lists over the run)
+            }
+        }
     }
+}
+// ONE workgroup, n > 0 listed walks: Jacobi sweeps among them (rv_row_*: the rounds' sweeps), workgroup barriers between the steps, until a
+// sweep changes no owner or RD_MAX_SWEEPS have run; then the attach.  Few walks (the usual frame): a thread per walk, its codes in
+// registers, the owners in an LDS table keyed by the feature.  A list longer than the workgroup, or one whose candidates would fill the
+// table beyond a half (the bootstrap frame): in turns, the codes read again in every step, the owners in the scratch -- only the listed
+// walks' candidates are cleared, read or claimed there, so what an earlier call of any shape left in those arrays does not matter.
+template <int MC>
+__device__ __forceinline__ void rd_resolve(const RdArgs& A, int n, int* sKey, int* sOwn) {
+    __shared__ int sChanged;
+    const int tid = threadIdx.x;
+    int code[MC], base = -1, k = 0;
+    bool settled = false;
+    if (n <= RD_THREADS && n * A.nCams <= RD_LDS_ENTRIES) {   // (uniform)
+        for (int c = tid; c < RD_LDS_CELLS; c += RD_THREADS)
+            sKey[c] = -1, sOwn[c] = RD_INF, sOwn[RD_LDS_CELLS + c] = RD_INF, sOwn[2 * RD_LDS_CELLS + c] = RD_INF;
+        const int p = tid < n ? rd_ld(A.active + tid) : -1;
+        rd_row_load<MC>(A, p, code, base);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < MC; ++i) {
+            if (code[i] < 0) continue;
+            const int f = code[i] & RD_FEAT;
+            unsigned h = ((unsigned)f * 2654435761u) >> (32 - RD_LDS_BITS);
+            for (;;) {   // (ends: the table is never more than half full)
+                const int old = atomicCAS(&sKey[h], -1, f);
+                if (old == -1 || old == f) break;
+                h = (h + 1) & (RD_LDS_CELLS - 1);
+            }
+            code[i] = (code[i] & ~RD_FEAT) | (int)h;
+        }
+        __syncthreads();
+        const int* fin = sOwn;
+        for (; k < RD_MAX_SWEEPS;) {
+            const int* prev = sOwn + (k % 3) * RD_LDS_CELLS;
+            int* next = sOwn + ((k + 1) % 3) * RD_LDS_CELLS;
+            int* clear = sOwn + ((k + 2) % 3) * RD_LDS_CELLS;
+            if (tid == 0) sChanged = 0;
+            rv_row_clear<MC>(code, base, clear);
+            __syncthreads();
+            rv_row_claim<MC>(code, base, prev, next);
+            __syncthreads();
+            if (rv_row_changed<MC>(code, base, prev, next)) sChanged = 1;
+            __syncthreads();
+            fin = next, ++k;
+            const int chg = sChanged;
+            __syncthreads();
+            if (!chg) {
+                settled = true;
+                break;
+            }
+        }
+        if (p >= 0) rd_row_attach<MC>(A, p, code, base, fin, sKey);
+    } else {
+        for (int j = tid; j < n; j += RD_THREADS) {
+            rd_row_load<MC>(A, rd_ld(A.active + j), code, base);
+#pragma unroll
+            for (int i = 0; i < MC; ++i)
+                if (code[i] >= 0) rd_st(A.owner[0] + (code[i] & RD_FEAT), RD_INF), rd_st(A.owner[1] + (code[i] & RD_FEAT), RD_INF), rd_st(A.owner[2] + (code[i] & RD_FEAT), RD_INF);
+        }
+        __syncthreads();
+        const int* fin = A.owner[0];
+        for (; k < RD_MAX_SWEEPS;) {
+            const int* prev = rd_owner(A, k);
+            int* next = rd_owner(A, k + 1);
+            int* clear = rd_owner(A, k + 2);
+            if (tid == 0) sChanged = 0;
+            for (int j = tid; j < n; j += RD_THREADS) {
+                rd_row_load<MC>(A, rd_ld(A.active + j), code, base);
+                rv_row_clear<MC>(code, base, clear);
+            }
+            __syncthreads();
+            for (int j = tid; j < n; j += RD_THREADS) {
+                rd_row_load<MC>(A, rd_ld(A.active + j), code, base);
+                rv_row_claim<MC>(code, base, prev, next);
+            }
+            __syncthreads();
+            int ch = 0;
+            for (int j = tid; j < n; j += RD_THREADS) {
+                rd_row_load<MC>(A, rd_ld(A.active + j), code, base);
+                ch |= rv_row_changed<MC>(code, base, prev, next);
+            }
+            if (ch) sChanged = 1;
+            __syncthreads();
+            fin = next, ++k;
+            const int chg = sChanged;
+            __syncthreads();
+            if (!chg) {
+                settled = true;
+                break;
+            }
+        }
+        for (int j = tid; j < n; j += RD_THREADS) {
+            const int p = rd_ld(A.active + j);
+            rd_row_load<MC>(A, p, code, base);
+            rd_row_attach<MC>(A, p, code, base, fin, nullptr);
+        }
+    }
+    if (tid == 0) {
+        if (A.counts) A.counts[2] = k, A.counts[3] = settled ? 1 : 0;
+        if (!settled) atomicAdd(A.unconverged, 1);
+    }
+}
+
+// entry-parallel (coalesced over the P x nCams tables): what every walk will see of (point, camera).  A workgroup takes WHOLE points
+// (RD_THREADS / nCams of them: a point's entries are nCams consecutive threads of one workgroup, whatever nCams is).
+// nSweeps > 0: the owners start at "nobody" for the sweep launches that follow.
+// nSweeps == 0, the self-settling form, ONE launch: the first entry of a point also decides from the workgroup's codes whether its walk
+// is ACTIVE (rd_resolve) and appends it to the scratch's list; the workgroup then waits for its (write-through) stores and draws a
+// ticket, one relaxed atomic; the workgroup that draws the last one resolves the list -- nobody waits for anybody, nothing has to be co-resident, and
+// on a frame without an active walk that is all.  ticket and nActive are left at 0 for the next call (the scratch arrives zeroed, as
+// its sticky last word needs it to): they are the scratch's first words, where a call of any other shape finds them too.
+template <int MC>
+__global__ __launch_bounds__(RD_THREADS) void k_decide_prepare(RdArgs A) {
+    __shared__ int sCode[RD_THREADS];
+    __shared__ int sKey[RD_LDS_CELLS], sOwn[3 * RD_LDS_CELLS];
+    __shared__ int sCount, sFirst, sLast;
+    const int tid = threadIdx.x, C = A.nCams, nFeat = C * A.N, ppb = RD_THREADS / C;
+    const int g = blockIdx.x * RD_THREADS + tid, stride = gridDim.x * RD_THREADS;
+    const bool settle = A.nSweeps == 0;
+    if (!settle)
+        for (int f = g; f < nFeat; f += stride) A.owner[0][f] = RD_INF, A.owner[1][f] = RD_INF, A.owner[2][f] = RD_INF;
+    // Everything the resolver reads, or writes again, is stored WRITE-THROUGH (agent-scope stores: rd_st, rd_st8): it is in memory when
+    // the workgroup draws its ticket, with no release fence -- that would write back every dirty line of the XCD's L2, the tracker's too,
+    // once per workgroup (the launch took 18 us that way on a frame without an active walk, 11 us more than these tables cost).
+    // (sweeps: the resolver's count; 2 where it has nothing to do -- converged: cleared when not)
+    if (g < 4 && A.counts) rd_st(A.counts + g, g == 2 ? (settle ? 2 : A.nSweeps) : (g == 3 ? 1 : 0));
+    if (g == 0) *A.callFlag = 0;
+    if (A.rvLists) {
+        for (int f = g; f < A.nRounds * A.rvCap; f += stride) rd_st(A.rvLists + f, -1);
+        if (g < A.nRounds) rd_st(A.rvCounts + g, 0);
+    }
+    const int pl = tid / C, i = tid - pl * C, p = blockIdx.x * ppb + pl;
+    const bool live = pl < ppb && p < A.P;
+    int code = -1, base = -1;
+    if (live) {
+        const size_t k = (size_t)p * C + i;
+        rd_st8(A.attached + k, 0);
+        if (i == 0) rd_st8(A.regged + p, 0);
+        // the point's kind: 0 certainly static, 1 certainly dynamic (its walk takes DYNAMIC features only, :981), -1 not visited
+        const unsigned char fl = A.mapFlags[p] & (CS_MAP_DYNAMIC | CS_MAP_FALSE | CS_MAP_UNCERTAIN);
+        const int kind = (fl == 0 && (A.kinds & 1)) ? 0 : ((fl == CS_MAP_DYNAMIC && (A.kinds & 2)) ? 1 : -1);
+        if (A.pointFeat[k] < 0 && kind >= 0) {   // (else :736-737: the point has a feature of this frame there)
+            const int s = A.slot[k];
+            if (s >= 0 && s < A.N && ((A.flags[k] >> 1) & 1) == kind) {   // (else: nothing found / a feature of the other type, :757 / :981)
+                code = i * A.N + s;
+                if (A.slot2map[i][s] >= 0) code |= RD_INIT_MAPPED;
+                if (A.mergeable[k] == 1) code |= RD_CAN_MERGE;
+            }
+        }
+        rd_st(A.code + (size_t)i * A.P + p, code);
+        if (i == 0) {   // the order of the point's walk = ((first camera in which it has a feature of this frame) x P + point) x nCams
+            int ofirst = -1;
+            for (int q = C - 1; q >= 0; --q)
+                if (A.pointFeat[(size_t)p * C + q] >= 0) ofirst = q;
+            // onlyCam >= 0: ONE camera's loop of the reference (:864-869): the points with a feature of this frame in that camera, map order
+            if (A.onlyCam >= 0) ofirst = A.pointFeat[(size_t)p * C + A.onlyCam] >= 0 ? 0 : -1;
+            base = (ofirst >= 0 && kind >= 0) ? (ofirst * A.P + p) * C : -1;
+            rd_st(A.base + p, base);
+        }
+    }
+    if (!settle) return;   // (uniform)
+    // ---- the active walks of this workgroup's points, appended to the list
+    sCode[tid] = code;
+    if (tid == 0) sCount = 0;
+    __syncthreads();
+    bool act = false;
+    if (base >= 0) {   // (the point's first entry; its walk, on the codes alone: does it reach a candidate it may take?)
+        for (int q = 0; q < C; ++q) {
+            const int c = sCode[tid + q];
+            if (c < 0) continue;
+            if (c & RD_INIT_MAPPED) break;
+            if (c & RD_CAN_MERGE) {
+                act = true;
+                break;
+            }
+        }
+    }
+    if (__syncthreads_or(act)) {   // (uniform; the usual workgroup has none)
+        const int at = act ? atomicAdd(&sCount, 1) : 0;
+        __syncthreads();
+        if (tid == 0) sFirst = atomicAdd(A.nActive, sCount);
+        __syncthreads();
+        if (act && sFirst >= 0 && sFirst + at < A.P) rd_st(A.active + sFirst + at, p);   // (in bounds by construction: the count starts at 0)
+    }
+    // ---- every wave's stores are in memory; draw a ticket
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) sLast = __hip_atomic_fetch_add(A.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+    __syncthreads();
+    if (!sLast) return;   // (uniform)
+    // ---- the last workgroup to arrive: every other one's tables, clears and list entries are in memory.  The resolver reads them past
+    // its caches (rd_ld); the acquire is for whatever else it loads
+    const int n = min(rd_ld(A.nActive), A.P);   // (never beyond the list, whatever a scratch that did not arrive zeroed holds)
+    if (n > 0) {
+        if (tid == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __syncthreads();
+        rd_resolve<MC>(A, n, sKey, sOwn);
+    }
+    __syncthreads();
+    if (tid == 0) rd_st(A.ticket, 0), rd_st(A.nActive, 0);
 }
 // one Jacobi sweep, thread per point: its walk against the owners of the previous sweep (prev), claims into next; `clear` is the
 // buffer the FOLLOWING sweep will claim into.  mode 1: the owners in prev are final -- attach instead of claiming.
@@ -492,124 +727,6 @@ __global__ __launch_bounds__(256) void k_decide_sweep(RdArgs A, const int* __res
     if (mode == 1 && reg) {
         A.regged[p] = 1;
         if (A.counts) atomicAdd(A.counts, nAtt), atomicAdd(A.counts + 1, 1);
-    }
-}
-
-// ---- the sweeps as ONE launch that stops when they have settled ------------------------------------------------------------------------
-// nSweeps launches with a fixed count either waste launches or, on a frame whose walks cut each other short in a longer chain than
-// the count allows, end on an answer that is not the sequential one (counted, not repaired -- ADVICE r04).  Here every workgroup of
-// ONE launch sweeps until a sweep changes no owner: sweep, grid barrier, compare the sweep's owners with the previous sweep's, grid
-// barrier, stop or go on -- as many sweeps as the frame needs (two on a quiet frame), never more than RD_MAX_SWEEPS, then the
-// attach.  The grid is P / 256 workgroups of 44 registers and no LDS: co-resident beside anything (the barrier spins on an arrival
-// counter in the scratch; a wait of more than 20 ms -- a grid that is NOT co-resident -- gives up and counts the call as unsettled).
-// Owners are read and cleared with agent-scope accesses (they are claimed by atomicMin in L2; a cached line of an earlier sweep must
-// not be read back).
-__device__ __forceinline__ bool rd_grid_barrier(int* ctr, int target) {
-    __syncthreads();
-    __shared__ int ok;
-    if (threadIdx.x == 0) {
-        __threadfence();
-        atomicAdd(ctr, 1);
-        const long long t0 = wall_clock64();
-        int good = 1;
-        while (__hip_atomic_load(ctr, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(2);
-            if (wall_clock64() - t0 > 2000000LL) {
-                good = 0;
-                break;
-            }
-        }
-        ok = good;
-    }
-    __syncthreads();
-    return ok != 0;
-}
-
-__global__ __launch_bounds__(256) void k_decide_settle(RdArgs A) {
-    const int p = blockIdx.x * 256 + threadIdx.x, C = A.nCams, nFeat = C * A.N, nB = gridDim.x, stride = nB * 256;
-    const int base = p < A.P ? A.base[p] : -1;
-    int code[RD_MAX_CAMS];
-#pragma unroll
-    for (int i = 0; i < RD_MAX_CAMS; ++i) code[i] = (base >= 0 && i < C) ? A.code[(size_t)i * A.P + p] : -1;
-    int arrivals = 0, k = 0;
-    bool settled = false, alive = true;
-    const int* fin = A.owner[0];
-    for (; k < RD_MAX_SWEEPS; ++k) {
-        const int* prev = A.owner[k % 3];
-        int* next = A.owner[(k + 1) % 3];
-        int* clear = A.owner[(k + 2) % 3];
-        for (int f = p; f < nFeat; f += stride) rd_st(clear + f, RD_INF);
-        if (base >= 0) {
-            bool go = true;
-#pragma unroll
-            for (int i = 0; i < RD_MAX_CAMS; ++i) {
-                if (go && code[i] >= 0) {
-                    const int ord = base + i, f = code[i] & RD_FEAT;
-                    if ((code[i] & RD_INIT_MAPPED) || rd_ld(prev + f) < ord) {
-                        go = false;
-                    } else if (code[i] & RD_CAN_MERGE) {
-                        atomicMin(&next[f], ord);
-                    }
-                }
-            }
-        }
-        arrivals += nB;
-        if (!rd_grid_barrier(A.bar, arrivals)) {
-            alive = false;
-            break;
-        }
-        int ch = 0;
-        for (int f = p; f < nFeat; f += stride) ch |= rd_ld(next + f) != rd_ld(prev + f);
-        if (__syncthreads_or(ch) && threadIdx.x == 0) atomicOr(A.changed + k, 1);
-        arrivals += nB;
-        if (!rd_grid_barrier(A.bar, arrivals)) {
-            alive = false;
-            break;
-        }
-        fin = next;
-        if (rd_ld(A.changed + k) == 0) {
-            settled = true;
-            ++k;
-            break;
-        }
-    }
-    if (p == 0 && A.counts) A.counts[2] = k, A.counts[3] = settled ? 1 : 0;
-    if (!settled && p == 0) atomicAdd(A.unconverged, 1);
-    if (!alive && p == 0) atomicAdd(A.timeouts, 1);
-    if (!alive || base < 0) return;
-    // the owners in `fin` are final (or the best the sweeps reached): attach (k_decide_sweep's mode 1)
-    bool go = true, reg = false;
-    int nAtt = 0;
-#pragma unroll
-    for (int i = 0; i < RD_MAX_CAMS; ++i) {
-        if (go && code[i] >= 0) {
-            const int ord = base + i, f = code[i] & RD_FEAT, own = rd_ld(fin + f);
-            if ((code[i] & RD_INIT_MAPPED) || own < ord) {
-                go = false;
-            } else if ((code[i] & RD_CAN_MERGE) && own == ord) {
-                const int s2 = f - i * A.N;
-                A.slot2map[i][s2] = A.mapBase + p;
-                A.pointFeat[(size_t)p * C + i] = s2;
-                A.attached[(size_t)p * C + i] = 1;
-                reg = true, ++nAtt;
-            }
-        }
-    }
-    if (reg) {
-        A.regged[p] = 1;
-        if (A.counts) atomicAdd(A.counts, nAtt), atomicAdd(A.counts + 1, 1);
-        if (A.rvLists && A.onlyCam < 0) {   // k_revisit_list's first round, by the walk itself
-            const int last = (base / C) / A.P;   // the loop of this visit: the first camera that held a feature before the pass (k_decide_prepare)
-            A.visitLoop[p] = last;
-            int b = -1;
-            for (int c = C - 1; c > last; --c)
-                if (A.pointFeat[(size_t)p * C + c] >= 0) b = c;
-            if (b >= 0) {
-                const int q = atomicAdd(A.rvCounts, 1);
-                if (q < A.rvCap) A.rvLists[q] = p, A.nextLoop[p] = b;
-                else atomicAdd(A.rvCounts + A.nRounds, 1);   // (never cleared here: the points beyond the lists over the run)
-            }
-        }
     }
 }
 
@@ -731,7 +848,7 @@ extern "C" int cs_register_revisit_decide_next_dev(int device, void* hip_stream,
     A.attached = d_attached, A.regOut = d_regOut, A.curList = d_curList, A.curCount = d_curCount, A.curCap = curCap, A.counts = d_counts, A.listCount = d_listCount;
     A.nextList = d_nextList, A.nextCount = d_nextCount, A.nextLoopW = d_nextLoop, A.overflow = d_overflow;
     A.debug = cs_debug_get(CS_DBG_MERGE_PRINT) == 1;
-    int* scr = (int*)d_decideScratch + (size_t)nCams * P + P;   // (cs_register_decide_kinds_dev's carve-up: code | base | owner x 3 | ...)
+    int* scr = rd_scratch_owners(d_decideScratch, nCams, P);   // (cs_register_decide_kinds_dev's carve-up: head | code | base | owner x 3 | ...)
     for (int k = 0; k < 3; ++k) A.owner[k] = scr, scr += (size_t)nCams * N;
     CS_HIP(hipSetDevice(device));
     if (nCams <= 8)
@@ -743,7 +860,9 @@ extern "C" int cs_register_revisit_decide_next_dev(int device, void* hip_stream,
 }
 extern "C" size_t cs_register_decide_scratch_bytes(int nCams, int N, int P) {
     if (nCams < 1 || N < 1 || P < 0) return 0;
-    return sizeof(int) * ((size_t)nCams * P + (size_t)P + 3 * (size_t)nCams * N + RD_MAX_SWEEPS + 4);
+    // head | code | base | owner x 3 | active list (at least the RD_MAX_SWEEPS words that stood here before: the size never shrinks) | 4 words
+    const size_t nList = (size_t)P > (size_t)RD_MAX_SWEEPS ? (size_t)P : (size_t)RD_MAX_SWEEPS;
+    return sizeof(int) * (RD_SCRATCH_HEAD + (size_t)nCams * P + (size_t)P + 3 * (size_t)nCams * N + nList + 4);
 }
 
 extern "C" int cs_register_decide_static_dev(int device, void* hip_stream, int nCams, int N, int P, int mapBase, const int* d_slot, const int* d_flags,
@@ -804,18 +923,21 @@ extern "C" int cs_register_decide_kinds_rounds_dev(int device, void* hip_stream,
     A.attached = d_attached, A.regged = d_regged, A.counts = d_counts;
     A.rvLists = d_rvLists, A.rvCap = rvCap, A.nRounds = nRounds, A.rvCounts = d_rvCounts, A.visitLoop = d_visitLoop, A.nextLoop = d_nextLoop;
     int* scr = (int*)d_scratch;
+    A.ticket = scr, A.nActive = scr + 1, scr += RD_SCRATCH_HEAD;
     A.code = scr, scr += (size_t)nCams * P;
     A.base = scr, scr += P;
     for (int k = 0; k < 3; ++k) A.owner[k] = scr, scr += (size_t)nCams * N;
-    A.changed = scr, scr += RD_MAX_SWEEPS;
-    A.bar = scr, A.callFlag = scr + 1, A.timeouts = scr + 2, A.unconverged = scr + 3;
+    A.active = scr, scr += P > RD_MAX_SWEEPS ? P : RD_MAX_SWEEPS;
+    A.callFlag = scr + 1, A.timeouts = scr + 2, A.unconverged = scr + 3;
     CS_HIP(hipSetDevice(device));
     if (P == 0) return CS_OK;
     hipStream_t s = (hipStream_t)hip_stream;
-    const int gE = (P * nCams + 255) / 256, gP = (P + 255) / 256;
-    hipLaunchKernelGGL(k_decide_prepare, dim3(gE), dim3(256), 0, s, A);
-    if (nSweeps == 0) {   // as many sweeps as the frame needs, ONE launch (k_decide_settle)
-        hipLaunchKernelGGL(k_decide_settle, dim3(gP), dim3(256), 0, s, A);
+    const int ppb = RD_THREADS / nCams, gE = (P + ppb - 1) / ppb, gP = (P + 255) / 256;   // (whole points per workgroup)
+    if (nCams <= 8)
+        hipLaunchKernelGGL(k_decide_prepare<8>, dim3(gE), dim3(RD_THREADS), 0, s, A);
+    else
+        hipLaunchKernelGGL(k_decide_prepare<RD_MAX_CAMS>, dim3(gE), dim3(RD_THREADS), 0, s, A);
+    if (nSweeps == 0) {   // as many sweeps as the frame needs, in that ONE launch (rd_resolve)
         CS_CHECK_LAUNCH();
         return CS_OK;
     }

@@ -147,6 +147,11 @@ constexpr int RD_INIT_MAPPED = 1 << 29, RD_CAN_MERGE = 1 << 28, RD_FEAT = (1 << 
 constexpr int RD_INF = 0x7fffffff;
 __device__ __forceinline__ int rd_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void rd_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void rd_st8(unsigned char* p, unsigned char v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// the decision's scratch (cs_register_decide_scratch_bytes), in ints: head (the self-settling launch's ticket and list count, 0 between
+// calls) | code [nCams][P] | base [P] | owner x 3 [nCams * N] | the decision's own rest.  The second visits' rounds borrow the owner arrays.
+constexpr int RD_SCRATCH_HEAD = 4;
+inline int* rd_scratch_owners(void* scratch, int nCams, int P) { return (int*)scratch + RD_SCRATCH_HEAD + (size_t)nCams * P + P; }
 
 // ---- one round of the SECOND VISITS (register.hip: the rounds' account): the listed points' walks, their Jacobi sweeps among themselves,
 // the attach, the next round's list and the conflict count.  ONE workgroup of at least cap threads, a thread per listed row; the caller
@@ -252,7 +257,7 @@ __device__ __forceinline__ void rv_row_build(const RvArgs& A, int p, int (&code)
             if (code[i] >= 0) rd_st(A.owner[0] + (code[i] & RD_FEAT), RD_INF), rd_st(A.owner[1] + (code[i] & RD_FEAT), RD_INF), rd_st(A.owner[2] + (code[i] & RD_FEAT), RD_INF);
     }
 }
-// the three steps of a Jacobi sweep (k_decide_settle's recursion), a barrier between them
+// the three steps of a Jacobi sweep (the decision's recursion: rd_resolve runs its sweeps on these too), a barrier between them
 template <int MC>
 __device__ __forceinline__ void rv_row_clear(const int (&code)[MC], int base, int* clear) {
     if (base < 0) return;
@@ -394,7 +399,7 @@ __device__ __forceinline__ void rv_decide_rows(const RvArgs& A, const RvRound& R
     rv_row_build<MC>(A, p, code, base, nConf);
     __syncthreads();   // (ONE workgroup: its barrier orders the agent-scope accesses above -- an agent-scope fence here writes the XCD's L2 back, tracker's lines and all: 30-70 us a launch)
     if (A.debug) tD1 = wall_clock64();
-    // Jacobi sweeps among the round's visits (k_decide_settle's recursion, one workgroup)
+    // Jacobi sweeps among the round's visits (the decision's recursion, one workgroup)
     int k = 0;
     const int* fin = A.owner[0];
     bool settled = false;

@@ -403,15 +403,18 @@ int cs_register_search(int device, int nCams, const cs_register_cam* cams, int N
  * walk -- ends the point's walk (:789-790).  The sequential "first claimant wins" is a recursion along the order of the walk steps;
  * nSweeps Jacobi sweeps (one small launch each) solve it -- exactly once two consecutive sweeps agree (d_counts[3] = 1), which takes as
  * many sweeps as the longest chain of walks cutting each other short: 1-2 on tracked frames (csrc/register.hip).  nSweeps = 0: ONE
- * launch whose workgroups sweep behind a grid barrier until a sweep changes nothing (at most 64 sweeps; d_counts[2] = the sweeps it took)
- * -- what a frame loop should pass: the answer is then always the sequential one.
+ * launch for all of it: while it builds the walks' tables it lists the walks that can claim a feature at all (they reach an unmapped,
+ * mergeable candidate with no mapped one in front of it: a handful on a tracked frame, often none), and the workgroup that finishes last
+ * sweeps over those alone until a sweep changes nothing (at most 64 sweeps; d_counts[2] = the sweeps it took, 2 when nothing was listed)
+ * and attaches -- no grid barrier, nothing waits -- what a frame loop should pass: the answer is then always the sequential one.
  * d_slot / d_flags: the search's P x nCams tables; d_mapFlags [P]: CS_MAP_* bytes of the pass's points (map points mapBase ..
  * mapBase + P - 1); IN / OUT: d_pointFeat [P][nCams] (MapPoint::addFeature) and every camera's slot2map [N] (the attached feature's
  * whole track takes the point, :771-775); OUT: d_attached [P][nCams], d_regged [P] (refineMapPoint is due: hand it to
  * cs_refine_map_points_dev as d_select), d_counts [4] or NULL (features attached, points regged, sweeps, converged).
  * d_scratch: cs_register_decide_scratch_bytes; its LAST int COUNTS the calls whose sweeps did not settle (the decision then is not
- * the sequential one), the int before it how many of those ended on a grid-barrier time-out of the self-settling launch (its workgroups were
- * not co-resident within 20 ms: nothing was attached that frame); never cleared here -- zero the scratch once, read the words at the end of a run.  Not done here: the projections are those of the search as it ran (the reference
+ * the sequential one), the int before it counted the time-outs of the self-settling launch's grid barrier while it had one and now
+ * stays 0; never cleared here -- zero the scratch once (the self-settling launch also counts on its first two ints being 0 between calls,
+ * which it leaves them), read the words at the end of a run.  Not done here: the projections are those of the search as it ran (the reference
  * refines a point before the next camera's round of walks, :889-893), and the bMerge == true branch (every 50th frame: checkUnify on
  * a conflict) -- that one is cs_register_decide_merge_dev further down. */
 size_t cs_register_decide_scratch_bytes(int nCams, int N, int P);
@@ -467,7 +470,7 @@ int cs_register_revisit_decide_dev(int device, void* hip_stream, int nCams, int 
                                    NULL: an empty list ends the launch at once */);
 
 /* The same rounds with TWO launches fewer each: the lists are built by the walks themselves.
- *   cs_register_decide_kinds_rounds_dev   cs_register_decide_kinds_dev (nSweeps 0, all cameras' loops) whose prepare launch clears
+ *   cs_register_decide_kinds_rounds_dev   cs_register_decide_kinds_dev (nSweeps 0, all cameras' loops) whose launch first clears
  *       d_rvLists [nRounds][rvCap] to -1 and d_rvCounts [nRounds] to 0 and whose walks append the points that registered and hold a
  *       feature in a later loop to list 0 (d_visitLoop / d_nextLoop [P] written as cs_register_revisit_list_dev(firstRound) writes them;
  *       d_rvCounts[0] = points appended, beyond rvCap they are not visited again and counted in d_rvCounts[nRounds], which is NOT cleared:
