@@ -229,7 +229,9 @@ __device__ __forceinline__ void rv_row_build(const RvArgs& A, int p, int (&code)
         for (int i = 0; i < MC; ++i) {
             const bool cand = i < C && pfv[i] < 0 && slv[i] >= 0 && slv[i] < A.N && ((flv[i] >> 1) & 1) == kind;   // :736-737; nothing found / the other type
             if (!cand) slv[i] = -1;
-            own[i] = cand ? A.slot2map[i][slv[i]] - A.mapBase : -1;
+            // (the owner as a row of the pass; a point of the map below mapBase carries the feature all the same: A.P, "mapped, not one of ours")
+            const int raw = cand ? A.slot2map[i][slv[i]] : -1;
+            own[i] = raw < 0 ? -1 : (raw >= A.mapBase ? raw - A.mapBase : A.P);
         }
         int oAtt[MC], oPf[MC], oLoop[MC];
 #pragma unroll
