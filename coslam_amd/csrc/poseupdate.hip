@@ -1943,6 +1943,38 @@ static void hist_centres(const cs_track_history* h, hipStream_t s);
 constexpr int PU_SEG_CAP = 1 << 15;  // linked segments a camera's pool holds (16 bytes each; never recycled: a full pool drops further links)
 static inline int hist_walk(const cs_track_history* h) { return h->count < h->walkLen ? h->count : h->walkLen; }
 
+namespace {
+// the history's ring into a launch's arguments: every struct whose kernel walks the ring names these fields alike (`cen` where it has one)
+template <class Args>
+auto hist_set_cen(Args& A, const cs_track_history* h, int) -> decltype((void)(A.cen = h->cen)) {
+    A.cen = h->cen;
+}
+template <class Args>
+void hist_set_cen(Args&, const cs_track_history*, long) {}
+template <class Args>
+void hist_set_ring(Args& A, const cs_track_history* h) {
+    A.nCams = h->nCams, A.N = h->N, A.H = h->H, A.head = h->head, A.nHist = hist_walk(h);
+    A.histXY = h->xy, A.histR = h->R, A.histT = h->t;
+    hist_set_cen(A, h, 0);
+}
+// the reference tables of a *_ref_dev call into the launch arguments
+template <class Args>
+void up_set_refs(Args& A, const cs_track_history* h) {
+    A.segPool = h->segPool, A.segCap = h->segCap, A.curFrame = h->lastFrame, A.stored = h->count < h->H ? h->count : h->H;
+}
+// the advance's `alive` scratch, grown on first use / for a larger map (a point nobody has seen yet has no live reference).  Behind the
+// caller's validation and its hipSetDevice (the thread's current device may be another): a refused call allocates and enqueues nothing.
+int hist_alive(cs_track_history* h, int nMap, hipStream_t s) {
+    if (nMap <= h->aliveCap) return CS_OK;
+    if (h->alive) CS_HIP(hipFree(h->alive));
+    h->alive = nullptr, h->aliveCap = 0;
+    CS_HIP(hipMalloc((void**)&h->alive, (size_t)nMap));
+    CS_HIP(hipMemsetAsync(h->alive, 1, (size_t)nMap, s));   // (1: look at every row once)
+    h->aliveCap = nMap;
+    return CS_OK;
+}
+}  // namespace
+
 extern "C" cs_track_history* cs_track_history_create(int device, int nCams, int N, int histLen) {
     return cs_track_history_create_ex(device, nCams, N, histLen, histLen);
 }
@@ -2089,8 +2121,7 @@ int pu_advance(const char* who, cs_track_history* h, hipStream_t s, int frame) {
 }
 
 void pu_fill_dyn(PuArgs& A, cs_track_history* h, int minLen, int minOutNum, double maxEpiErr, int* d_numDyn) {
-    A.H = h->H, A.head = h->head, A.nHist = hist_walk(h);
-    A.histXY = h->xy, A.histR = h->R, A.histT = h->t;
+    hist_set_ring(A, h);
     A.minLen = minLen, A.minOutNum = minOutNum, A.maxEpiErr = maxEpiErr;
     A.numDyn = d_numDyn;
 }
@@ -2161,6 +2192,38 @@ extern "C" int cs_pose_update_frame_dev(cs_track_history* h, void* hip_stream, c
     return pu_launch("cs_pose_update_frame_dev", h->device, hip_stream, A, cams, true, true);
 }
 
+namespace {
+// MgCore of a walk over the history as it stands, and on top of it MgRunCore of a running-verdict pass (list / nList are the caller's): what
+// k_register_mergability(_running) and the mergability phase of k_revisit_rounds read.  The cameras are checked, not copied: the argument
+// block that owns the array does that.
+int mg_fill_core(const char* who, MgCore& A, const cs_track_history* h, const cs_poseupdate_cam* cams, int cam0, int P, const double* d_M,
+                 const double* d_cov, const int* d_slot, double pixelErrVar, unsigned char* d_mergeable) {
+    for (int c = 0; c < h->nCams && P > 0; ++c)
+        if (!cams[c].K || !cams[c].trackSpan) {
+            cs_set_error("%s: null pointer in camera %d (K, trackSpan are read)", who, c);
+            return CS_ERR_INVALID;
+        }
+    hist_set_ring(A, h);
+    A.cam0 = cam0, A.P = P, A.sigma = pixelErrVar, A.M = d_M, A.cov = d_cov, A.slot = d_slot, A.out = d_mergeable;
+    return CS_OK;
+}
+int mg_fill_running(const char* who, MgRunCore& B, const cs_track_history* h, const cs_poseupdate_cam* cams, int cam0, int P, const double* d_M,
+                    const double* d_cov, const int* d_slot, const int* d_flags, double pixelErrVar, double tolPix, void* d_cache,
+                    unsigned char* d_mergeable, int* d_counts) {
+    if (P > 0 && (!d_M || !d_cov || !d_slot || !d_mergeable || !d_cache)) {
+        cs_set_error("%s: bad arguments (null map, covariances, candidates, verdicts or cache)", who);
+        return CS_ERR_INVALID;
+    }
+    if (h->count < 1) {
+        cs_set_error("%s: the history holds no frame", who);
+        return CS_ERR_INVALID;
+    }
+    B.W = hist_walk(h), B.count = h->count, B.curFrame = h->lastFrame, B.epoch = h->tailEpoch, B.fromMin = h->tailFromMin;
+    B.tolPix = tolPix, B.cache = (MgCache*)d_cache, B.counts = d_counts, B.flags = d_flags;
+    return mg_fill_core(who, B.a, h, cams, cam0, P, d_M, d_cov, d_slot, pixelErrVar, d_mergeable);
+}
+}  // namespace
+
 extern "C" int cs_register_mergability_dev(const cs_track_history* h, void* hip_stream, const cs_poseupdate_cam* cams, int P,
                                            const double* d_M, const double* d_cov, const int* d_slot, double pixelErrVar,
                                            unsigned char* d_mergeable) {
@@ -2185,18 +2248,8 @@ extern "C" int cs_register_mergability_range_dev(const cs_track_history* h, void
     if (P == 0 || nCamsRun == 0) return CS_OK;
     MgArgs A;
     memset(&A, 0, sizeof(A));
-    A.cam0 = cam0;
-    A.nCams = h->nCams, A.N = h->N, A.P = P, A.H = h->H, A.head = h->head, A.nHist = hist_walk(h);
-    A.sigma = pixelErrVar;
-    A.M = d_M, A.cov = d_cov, A.slot = d_slot, A.out = d_mergeable;
-    A.histXY = h->xy, A.histR = h->R, A.histT = h->t;
-    for (int c = 0; c < h->nCams; ++c) {
-        if (!cams[c].K || !cams[c].trackSpan) {
-            cs_set_error("cs_register_mergability_dev: null pointer in camera %d", c);
-            return CS_ERR_INVALID;
-        }
-        A.cam[c] = cams[c];
-    }
+    if (const int rc = mg_fill_core("cs_register_mergability_dev", A, h, cams, cam0, P, d_M, d_cov, d_slot, pixelErrVar, d_mergeable)) return rc;
+    for (int c = 0; c < h->nCams; ++c) A.cam[c] = cams[c];
     CS_HIP(hipSetDevice(h->device));
     hipLaunchKernelGGL(k_register_mergability, dim3((P * MG_LPC + 255) / 256, nCamsRun), dim3(256), sizeof(double) * 12 * (size_t)hist_walk(h),
                        (hipStream_t)hip_stream, A);
@@ -2225,41 +2278,23 @@ extern "C" int cs_register_mergability_running_list_dev(const cs_track_history* 
         cs_set_error("cs_register_mergability_running_dev: camera range %d + %d of %d", cam0, nCamsRun, h->nCams);
         return CS_ERR_INVALID;
     }
-    if (!h || !cams || P < 0 || tolPix < 0 || (P > 0 && (!d_M || !d_cov || !d_slot || !d_mergeable || !d_cache))) {
+    if (!h || !cams || P < 0 || tolPix < 0) {
         cs_set_error("cs_register_mergability_running_dev: bad arguments");
-        return CS_ERR_INVALID;
-    }
-    if (h->count < 1) {
-        cs_set_error("cs_register_mergability_running_dev: the history holds no frame");
         return CS_ERR_INVALID;
     }
     if (d_list && nList < 0) {
         cs_set_error("cs_register_mergability_running_list_dev: nList < 0");
         return CS_ERR_INVALID;
     }
-    const int rows = d_list ? nList : P;
-    if (P == 0 || nCamsRun == 0 || rows == 0) return CS_OK;
     MgRunArgs B;
     memset(&B, 0, sizeof(B));
-    B.list = d_list, B.nList = nList, B.flags = d_flags;
-    MgCore& A = B.a;
-    A.cam0 = cam0;
-    A.nCams = h->nCams, A.N = h->N, A.P = P, A.H = h->H, A.head = h->head, A.nHist = hist_walk(h);
-    A.sigma = pixelErrVar;
-    A.M = d_M, A.cov = d_cov, A.slot = d_slot, A.out = d_mergeable;
-    A.histXY = h->xy, A.histR = h->R, A.histT = h->t;
-    for (int c = 0; c < h->nCams; ++c) {
-        if (!cams[c].K || !cams[c].trackSpan) {
-            cs_set_error("cs_register_mergability_running_dev: null pointer in camera %d", c);
-            return CS_ERR_INVALID;
-        }
-        B.cam[c] = cams[c];
-    }
-    B.W = hist_walk(h), B.count = h->count, B.curFrame = h->lastFrame;
-    B.epoch = h->tailEpoch, B.fromMin = h->tailFromMin;
-    B.tolPix = tolPix;
-    B.cache = (MgCache*)d_cache;
-    B.counts = d_counts;
+    if (const int rc = mg_fill_running("cs_register_mergability_running_dev", B, h, cams, cam0, P, d_M, d_cov, d_slot, d_flags, pixelErrVar, tolPix,
+                                       d_cache, d_mergeable, d_counts))
+        return rc;
+    const int rows = d_list ? nList : P;
+    if (P == 0 || nCamsRun == 0 || rows == 0) return CS_OK;
+    B.list = d_list, B.nList = nList;
+    for (int c = 0; c < h->nCams; ++c) B.cam[c] = cams[c];
     CS_HIP(hipSetDevice(h->device));
     hipLaunchKernelGGL(k_register_mergability_running, dim3((rows * MG_LPC + 255) / 256, nCamsRun), dim3(256), sizeof(double) * 12 * (size_t)B.W,
                        (hipStream_t)hip_stream, B);
@@ -2390,8 +2425,7 @@ int up_launch(const char* who, const cs_track_history* h, void* hip_stream, cons
         cs_set_error("%s: the history holds no frame (cs_pose_update_frame_dev / cs_detect_dynamic_dev push one per frame)", who);
         return CS_ERR_INVALID;
     }
-    A.nCams = h->nCams, A.N = h->N, A.H = h->H, A.head = h->head, A.nHist = hist_walk(h);
-    A.histXY = h->xy, A.histR = h->R, A.histT = h->t;
+    hist_set_ring(A, h);
     A.counts = d_counts;
     for (int c = 0; c < h->nCams; ++c) {
         if (!cams[c].K || !cams[c].iK || (!A.featRef && !cams[c].trackSpan) || (!A.refine && !A.refStatic && !cams[c].isStatic)) {
@@ -2408,7 +2442,6 @@ int up_launch(const char* who, const cs_track_history* h, void* hip_stream, cons
         CS_HIP(ops.run(s));
     }
     if (A.nMap == 0) return CS_OK;
-    A.cen = h->cen;
     hist_centres(h, s);
     hipLaunchKernelGGL(k_update_points, dim3((A.nMap * UP_LPP + 255) / 256), dim3(256), 0, s, A);
     CS_HIP(hipGetLastError());
@@ -2629,9 +2662,9 @@ extern "C" int cs_newpts_intracam_dev(const cs_track_history* h, void* hip_strea
     }
     InArgs A;
     memset(&A, 0, sizeof(A));
-    A.nCams = h->nCams, A.N = h->N, A.H = h->H, A.head = h->head, A.nHist = hist_walk(h), A.stored = h->count < h->H ? h->count : h->H;
+    hist_set_ring(A, h);
+    A.stored = h->count < h->H ? h->count : h->H;
     A.curFrame = h->lastFrame, A.minTrackLen = minTrackLen, A.maxWalk = maxWalk, A.readyMin = readyMin, A.mapCap = mapCap;
-    A.histXY = h->xy, A.histR = h->R, A.histT = h->t, A.cen = h->cen;
     A.ready = d_ready, A.maxEpiErr = maxEpiErr, A.sigma = pixelErrVar;
     const size_t n = (size_t)h->nCams * h->N;
     A.rec = (double*)d_scratch, A.first = (int*)((char*)d_scratch + n * 12 * sizeof(double)), A.ok = (unsigned char*)(A.first + n);
@@ -2681,6 +2714,40 @@ struct FrCore {
 struct FrArgs : FrCore {
     cs_poseupdate_cam cam[PU_MAX_CAMS];
 };
+// the slot whose track span an entry's rule needs: the feature's of this frame, else the reference's (0 where neither names one: not read)
+__device__ __forceinline__ int fr_span_slot(const FrCore& A, int s, const int4& ref) {
+    return s >= 0 && s < A.N ? s : ((ref.x >= 0 && ref.x < A.N) ? ref.x : 0);
+}
+// The rule above for ONE reference (entry e = map point, camera c) on values already loaded: s the point's feature of this frame, ref the
+// reference as it stands, g1 / g2 the first / last frame of the track on fr_span_slot.  The only copy of the state machine and its stores
+// (featRef, segPool, refStatic, cnt: tracked on, first, re-linked, links dropped, detached).  Returns whether the reference is alive now.
+__device__ __forceinline__ bool fr_entry_rule(const FrCore& A, const cs_poseupdate_cam& C, size_t e, int c, int s, int4 ref, int g1, int g2,
+                                              int (&cnt)[5]) {
+    if (s < 0 || s >= A.N) {
+        if (ref.x >= 0 && ref.x < A.N && ref.y == A.curFrame - 1 && g1 >= 0 && g1 <= ref.y && g2 == A.curFrame) {
+            ref.x = -1, ++cnt[4];   // the same track, alive in this frame, no longer the point's: detached
+            A.featRef[e] = ref;
+        }
+        return ref.x >= 0 && ref.y == A.curFrame;
+    }
+    if (ref.x == s && g1 >= 0 && ref.y >= g1 && ref.y <= A.curFrame) {
+        if (ref.y != A.curFrame) ++cnt[0];   // (a second call within the frame changes and counts nothing)
+        ref.y = A.curFrame;
+    } else if (ref.x >= 0 && ref.y < A.curFrame) {
+        const int idx = atomicAdd(A.segCount + c, 1);
+        ++cnt[2];
+        if (idx < A.segCap)
+            A.segPool[(size_t)c * A.segCap + idx] = ref;   // {slot, last = its frame, first, next = its segment}
+        else
+            ++cnt[3];
+        ref = make_int4(s, A.curFrame, A.curFrame, idx < A.segCap ? idx : -1);
+    } else {
+        ref = make_int4(s, A.curFrame, g1 >= 0 ? g1 : A.curFrame, -1), ++cnt[1];
+    }
+    A.featRef[e] = ref;
+    if (A.refStatic) A.refStatic[e] = C.isStatic ? C.isStatic[s] : 1;
+    return true;
+}
 // one row (a map point's nCams references) of cs_feat_ref_advance_dev; cnt: tracked on, first, re-linked, links dropped, detached
 __device__ __forceinline__ void fr_advance_row(const FrCore& A, const cs_poseupdate_cam* cam, int m, int (&cnt)[5]) {
     if (m >= 0 && m < A.nMap) {
@@ -2707,44 +2774,14 @@ __device__ __forceinline__ void fr_advance_row(const FrCore& A, const cs_poseupd
                 for (int q = 0; q < 4; ++q) {
                     const int c = c0 + q < A.nCams ? c0 + q : A.nCams - 1;
                     const int* span = cam[c].trackSpan;
-                    const bool on = sl[q] >= 0 && sl[q] < A.N;
-                    const int look = on ? sl[q] : ((refs[q].x >= 0 && refs[q].x < A.N) ? refs[q].x : 0);
+                    const int look = fr_span_slot(A, sl[q], refs[q]);
                     g1[q] = span[look], g2[q] = span[A.N + look];
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int c = c0 + q;
                     if (c >= A.nCams) break;
-                    const size_t e = (size_t)m * A.nCams + c;
-                    const int s = sl[q];
-                    int4 ref = refs[q];
-                    const cs_poseupdate_cam& C = cam[c];
-                    if (s < 0 || s >= A.N) {
-                        if (ref.x >= 0 && ref.x < A.N && ref.y == A.curFrame - 1 && g1[q] >= 0 && g1[q] <= ref.y && g2[q] == A.curFrame) {
-                            ref.x = -1, ++cnt[4];   // the same track, alive in this frame, no longer the point's: detached
-                            A.featRef[e] = ref;
-                        }
-                        aliveNow = aliveNow || (ref.x >= 0 && ref.y == A.curFrame);
-                        continue;
-                    }
-                    const int f1 = g1[q];
-                    if (ref.x == s && f1 >= 0 && ref.y >= f1 && ref.y <= A.curFrame) {
-                        if (ref.y != A.curFrame) ++cnt[0];   // (a second call within the frame changes and counts nothing)
-                        ref.y = A.curFrame;
-                    } else if (ref.x >= 0 && ref.y < A.curFrame) {
-                        const int idx = atomicAdd(A.segCount + c, 1);
-                        ++cnt[2];
-                        if (idx < A.segCap)
-                            A.segPool[(size_t)c * A.segCap + idx] = ref;   // {slot, last = its frame, first, next = its segment}
-                        else
-                            ++cnt[3];
-                        ref = make_int4(s, A.curFrame, A.curFrame, idx < A.segCap ? idx : -1);
-                    } else {
-                        ref = make_int4(s, A.curFrame, f1 >= 0 ? f1 : A.curFrame, -1), ++cnt[1];
-                    }
-                    A.featRef[e] = ref;
-                    if (A.refStatic) A.refStatic[e] = C.isStatic ? C.isStatic[s] : 1;
-                    aliveNow = true;
+                    aliveNow |= fr_entry_rule(A, cam[c], (size_t)m * A.nCams + c, c, sl[q], refs[q], g1[q], g2[q], cnt);
                 }
             }
             A.alive[m] = aliveNow ? 1 : 0;
@@ -2753,28 +2790,55 @@ __device__ __forceinline__ void fr_advance_row(const FrCore& A, const cs_poseupd
 }
 // a thread per MAP POINT (its nCams entries): most of a map's points are seen by no camera in a frame and were not the frame before --
 // their row of pointFeat (and one byte saying whether any of their references was alive last frame) is all that is read
+// the five counters of a workgroup of NW waves added to counts (null: not asked for; uniform): wave shuffle, LDS, then ONE atomic per
+// workgroup and counter: atomics on one address serialise (360 waves' worth were most of k_feat_ref_advance's time).  Every thread calls it.
+template <int NW>
+__device__ __forceinline__ void fr_fold_counts(const int (&cnt)[5], int (&sCnt)[NW][5], int* counts) {
+    if (!counts) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        int v = cnt[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) sCnt[wv][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        int v = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) v += sCnt[w][threadIdx.x];
+        if (v) atomicAdd(counts + threadIdx.x, v);
+    }
+}
 __global__ __launch_bounds__(256) void k_feat_ref_advance(FrArgs A) {
+    __shared__ int sCnt[4][5];
     const int idx0 = blockIdx.x * 256 + threadIdx.x;
     const int m = A.list ? (idx0 < A.nList ? A.list[idx0] : -1) : idx0;
     int cnt[5] = {0, 0, 0, 0, 0};   // tracked on, first, re-linked, links dropped, detached
     fr_advance_row(A, A.cam, m, cnt);
-    if (A.counts) {   // one atomic per WORKGROUP and counter: atomics on one address serialise (360 waves' worth were most of this kernel's time)
-        __shared__ int sCnt[4][5];
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            int v = cnt[k];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) sCnt[wv][k] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < 5) {
-            const int v = (sCnt[0][threadIdx.x] + sCnt[1][threadIdx.x]) + (sCnt[2][threadIdx.x] + sCnt[3][threadIdx.x]);
-            if (v) atomicAdd(A.counts + threadIdx.x, v);
-        }
-    }
+    fr_fold_counts(cnt, sCnt, A.counts);
 }
+
+namespace {
+// what every advance reads into FrCore (list / nList and `alive` are the caller's: hist_alive once nothing can refuse the call any more).
+// The cameras are checked, not copied: the argument block that owns the array does that.
+int fr_fill(const char* who, FrCore& F, const cs_track_history* h, const cs_poseupdate_cam* cams, int nMap, const int* d_pointFeat, int curFrame,
+            cs_feat_ref* d_featRef, unsigned char* d_refStatic, int* d_counts) {
+    if (nMap > 0 && (!d_pointFeat || !d_featRef)) {
+        cs_set_error("%s: bad arguments (null feature table or references)", who);
+        return CS_ERR_INVALID;
+    }
+    for (int c = 0; c < h->nCams; ++c)
+        if (!cams[c].trackSpan) {
+            cs_set_error("%s: null trackSpan in camera %d", who, c);
+            return CS_ERR_INVALID;
+        }
+    F.nCams = h->nCams, F.N = h->N, F.nMap = nMap, F.curFrame = curFrame, F.segCap = h->segCap, F.counts = d_counts;
+    F.pointFeat = d_pointFeat, F.featRef = (int4*)d_featRef, F.refStatic = d_refStatic, F.segPool = h->segPool, F.segCount = h->segCount;
+    return CS_OK;
+}
+}  // namespace
 
 extern "C" int cs_feat_ref_advance_dev(cs_track_history* h, void* hip_stream, const cs_poseupdate_cam* cams, int nMap, const int* d_pointFeat,
                                        int curFrame, cs_feat_ref* d_featRef, unsigned char* d_refStatic, int* d_counts) {
@@ -2784,34 +2848,21 @@ extern "C" int cs_feat_ref_advance_dev(cs_track_history* h, void* hip_stream, co
 extern "C" int cs_feat_ref_advance_list_dev(cs_track_history* h, void* hip_stream, const cs_poseupdate_cam* cams, int nMap, const int* d_pointFeat,
                                             int curFrame, cs_feat_ref* d_featRef, unsigned char* d_refStatic, int* d_counts, const int* d_list,
                                             int nList) {
-    if (!h || !cams || nMap < 0 || nList < 0 || (nMap > 0 && (!d_pointFeat || !d_featRef))) {
+    if (!h || !cams || nMap < 0 || nList < 0) {
         cs_set_error("cs_feat_ref_advance_dev: bad arguments");
         return CS_ERR_INVALID;
     }
     FrArgs A;
     memset(&A, 0, sizeof(A));
-    A.nCams = h->nCams, A.N = h->N, A.nMap = nMap, A.curFrame = curFrame, A.segCap = h->segCap;
-    A.pointFeat = d_pointFeat, A.featRef = (int4*)d_featRef, A.refStatic = d_refStatic, A.segPool = h->segPool, A.segCount = h->segCount;
-    A.counts = d_counts;
-    CS_HIP(hipSetDevice(h->device));   // (before the allocation below: the calling thread's current device may be another)
-    if (nMap > h->aliveCap) {   // (grown on first use / for a larger map: a point nobody has seen yet has no live reference)
-        if (h->alive) CS_HIP(hipFree(h->alive));
-        h->alive = nullptr, h->aliveCap = 0;
-        CS_HIP(hipMalloc((void**)&h->alive, (size_t)nMap));
-        CS_HIP(hipMemsetAsync(h->alive, 1, (size_t)nMap, (hipStream_t)hip_stream));   // (1: look at every row once)
-        h->aliveCap = nMap;
-    }
-    A.alive = h->alive;
-    for (int c = 0; c < h->nCams; ++c) {
-        if (!cams[c].trackSpan) {
-            cs_set_error("cs_feat_ref_advance_dev: null trackSpan in camera %d", c);
-            return CS_ERR_INVALID;
-        }
-        A.cam[c] = cams[c];
-    }
-    if (nMap == 0 || (d_list && nList == 0)) return CS_OK;
+    if (const int rc = fr_fill("cs_feat_ref_advance_dev", A, h, cams, nMap, d_pointFeat, curFrame, d_featRef, d_refStatic, d_counts)) return rc;
+    for (int c = 0; c < h->nCams; ++c) A.cam[c] = cams[c];
     A.list = d_list, A.nList = nList;
-    hipLaunchKernelGGL(k_feat_ref_advance, dim3(((d_list ? nList : nMap) + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, A);
+    CS_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (const int rc = hist_alive(h, nMap, s)) return rc;
+    A.alive = h->alive;
+    if (nMap == 0 || (d_list && nList == 0)) return CS_OK;
+    hipLaunchKernelGGL(k_feat_ref_advance, dim3(((d_list ? nList : nMap) + 255) / 256), dim3(256), 0, s, A);
     CS_HIP(hipGetLastError());
     return CS_OK;
 }
@@ -2824,47 +2875,27 @@ __device__ __forceinline__ bool fr_advance_entry(const FrCore& A, const cs_poseu
     const int s = A.pointFeat[e];
     int4 ref = A.featRef[e];
     const int* span = cam[c].trackSpan;
-    const bool on = s >= 0 && s < A.N;
-    const int look = on ? s : ((ref.x >= 0 && ref.x < A.N) ? ref.x : 0);
-    const int g1 = span[look], g2 = span[A.N + look];
-    if (!on) {
-        if (ref.x >= 0 && ref.x < A.N && ref.y == A.curFrame - 1 && g1 >= 0 && g1 <= ref.y && g2 == A.curFrame) {
-            ref.x = -1, ++cnt[4];   // the same track, alive in this frame, no longer the point's: detached
-            A.featRef[e] = ref;
-        }
-        return ref.x >= 0 && ref.y == A.curFrame;
-    }
-    const int f1 = g1;
-    if (ref.x == s && f1 >= 0 && ref.y >= f1 && ref.y <= A.curFrame) {
-        if (ref.y != A.curFrame) ++cnt[0];
-        ref.y = A.curFrame;
-    } else if (ref.x >= 0 && ref.y < A.curFrame) {
-        const int idx = atomicAdd(A.segCount + c, 1);
-        ++cnt[2];
-        if (idx < A.segCap)
-            A.segPool[(size_t)c * A.segCap + idx] = ref;
-        else
-            ++cnt[3];
-        ref = make_int4(s, A.curFrame, A.curFrame, idx < A.segCap ? idx : -1);
-    } else {
-        ref = make_int4(s, A.curFrame, f1 >= 0 ? f1 : A.curFrame, -1), ++cnt[1];
-    }
-    A.featRef[e] = ref;
-    if (A.refStatic) A.refStatic[e] = cam[c].isStatic ? cam[c].isStatic[s] : 1;
-    return true;
+    const int look = fr_span_slot(A, s, ref);
+    return fr_entry_rule(A, cam[c], e, c, s, ref, span[look], span[A.N + look], cnt);
 }
 // cs_feat_ref_advance_(list_)dev + cs_refine_map_points_ref_dev as ONE launch: the rows that are not refined are advanced by the first
 // blocks (a thread per row, as k_feat_ref_advance); a row that IS refined (select[m] != 0; it has to be on `list`) is advanced by lane 0 of
 // its own wave, which then re-triangulates the point from the references it has just written (k_update_points' refine mode).  Rows are
 // independent (a pool segment is taken with an atomic), so the table and the map come out as the two calls leave them.
+// The marks: `select` says which half of a launch owns a row, so every reader must see it as the launch found it.  Within a launch a
+// `select` byte is written only by the owner of its row, and only where a barrier or the launch boundary separates that write from every
+// other reader: k_advance_refine, whose advance-only blocks and refine waves are different workgroups, writes none (the marks it consumed
+// are cleared by k_clear_marks behind it); k_revisit_rounds' one workgroup clears a row's mark in its refine phase, behind the barrier
+// that ends the advance phase's reads.
 struct ArArgs : UpArgs {
     FrCore F;
     const int* list;     // the rows refined are among list[0 .. nList) (entries < 0 skipped)
     int nList, advAll;   // advAll: the first blocks advance every row of the map (the frame's first call), else the listed rows
-    int blocksA, clearSelect;
-    unsigned char* selectW;   // = select (written when clearSelect: the mark is consumed)
+    int blocksA;
+    unsigned char* selectW;   // = select, for the one writer the rule above allows
 };
-// a refined row, by its own wave (lane r): advanced entry by entry, then re-triangulated from the references it has just written
+// a refined row, by its own wave (lane r): advanced entry by entry, then re-triangulated from the references it has just written (its mark
+// stands: consuming it is the caller's, under ArArgs' rule)
 __device__ __forceinline__ void ar_refine_row(const ArArgs& A, int m, int r, int (&cnt)[5]) {
     const bool al = r < A.nCams && fr_advance_entry(A.F, A.cam, m, r, cnt);
     const bool anyAlive = __builtin_amdgcn_ballot_w64(al) != 0ull;
@@ -2873,9 +2904,9 @@ __device__ __forceinline__ void ar_refine_row(const ArArgs& A, int m, int r, int
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     up_point(A, m, r);
-    if (A.clearSelect && r == 0) A.selectW[m] = 0;
 }
 __global__ __launch_bounds__(256) void k_advance_refine(ArArgs A) {
+    __shared__ int sCnt[4][5];
     int cnt[5] = {0, 0, 0, 0, 0};
     if ((int)blockIdx.x < A.blocksA) {
         const int idx0 = blockIdx.x * 256 + threadIdx.x;
@@ -2886,68 +2917,64 @@ __global__ __launch_bounds__(256) void k_advance_refine(ArArgs A) {
         const int m = j < A.nList ? A.list[j] : -1;
         if (m >= 0 && m < A.nMap && A.select[m]) ar_refine_row(A, m, r, cnt);   // (uniform over the wave)
     }
-    if (A.F.counts) {
-        __shared__ int sCnt[4][5];
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            int v = cnt[k];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) sCnt[wv][k] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < 5) {
-            const int v = (sCnt[0][threadIdx.x] + sCnt[1][threadIdx.x]) + (sCnt[2][threadIdx.x] + sCnt[3][threadIdx.x]);
-            if (v) atomicAdd(A.F.counts + threadIdx.x, v);
-        }
-    }
+    fr_fold_counts(cnt, sCnt, A.F.counts);
 }
+// the marks of the listed rows consumed, behind the k_advance_refine launch that read them (ArArgs' rule)
+__global__ __launch_bounds__(256) void k_clear_marks(unsigned char* select, const int* list, int nList, int nMap) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int m = j < nList ? list[j] : -1;
+    if (m >= 0 && m < nMap) select[m] = 0;
+}
+
+namespace {
+// the refine half of ArArgs -- k_update_points' refine mode over references, at the history's newest frame -- and the cameras both halves read
+int ar_fill_refine(const char* who, ArArgs& A, const cs_track_history* h, const cs_poseupdate_cam* cams, int nMap, int curFrame,
+                   const cs_feat_ref* d_featRef, unsigned char* d_select, double* d_mapPts, double* d_mapCov, double pixelErrVar) {
+    if (!d_featRef || !d_select || !d_mapPts || !d_mapCov) {
+        cs_set_error("%s: bad arguments (null references, marks, map or covariances)", who);
+        return CS_ERR_INVALID;
+    }
+    if (h->count < 1 || curFrame != h->lastFrame) {
+        cs_set_error("%s: the history's newest entry must be frame %d (it holds %d frame(s), the newest %d)", who, curFrame, h->count, h->lastFrame);
+        return CS_ERR_INVALID;
+    }
+    for (int c = 0; c < h->nCams; ++c) {
+        if (!cams[c].K || !cams[c].iK) {
+            cs_set_error("%s: null pointer in camera %d (K, iK are read)", who, c);
+            return CS_ERR_INVALID;
+        }
+        A.cam[c] = cams[c];
+    }
+    hist_set_ring(A, h);
+    up_set_refs(A, h);
+    A.nMap = nMap, A.featRef = (const int4*)d_featRef, A.mapPts = d_mapPts, A.mapCov = d_mapCov, A.sigma = pixelErrVar;
+    A.refine = 1, A.select = d_select, A.selectW = d_select;
+    return CS_OK;
+}
+}  // namespace
 
 extern "C" int cs_feat_ref_advance_refine_dev(cs_track_history* h, void* hip_stream, const cs_poseupdate_cam* cams, int nMap, const int* d_pointFeat,
                                               int curFrame, cs_feat_ref* d_featRef, unsigned char* d_refStatic, int* d_counts, const int* d_list,
                                               int nList, int advanceAll, unsigned char* d_select, int clearSelect, double* d_mapPts,
                                               double* d_mapCov, double pixelErrVar) {
-    if (!h || !cams || nMap < 1 || nList < 1 || !d_pointFeat || !d_featRef || !d_list || !d_select || !d_mapPts || !d_mapCov) {
-        cs_set_error("cs_feat_ref_advance_refine_dev: bad arguments");
-        return CS_ERR_INVALID;
-    }
-    if (h->count < 1 || curFrame != h->lastFrame) {
-        cs_set_error("cs_feat_ref_advance_refine_dev: the history's newest entry must be frame %d (it holds %d frame(s), the newest %d)", curFrame,
-                     h->count, h->lastFrame);
+    const char* who = "cs_feat_ref_advance_refine_dev";
+    if (!h || !cams || nMap < 1 || nList < 1 || !d_list) {
+        cs_set_error("%s: bad arguments", who);
         return CS_ERR_INVALID;
     }
     ArArgs A;
     memset((void*)&A, 0, sizeof(A));
-    A.nMap = nMap, A.featRef = (const int4*)d_featRef, A.mapPts = d_mapPts, A.mapCov = d_mapCov, A.sigma = pixelErrVar;
-    A.refine = 1, A.select = d_select, A.selectW = d_select, A.clearSelect = clearSelect ? 1 : 0;
-    A.segPool = h->segPool, A.segCap = h->segCap, A.curFrame = h->lastFrame, A.stored = h->count < h->H ? h->count : h->H;
-    A.nCams = h->nCams, A.N = h->N, A.H = h->H, A.head = h->head, A.nHist = hist_walk(h);
-    A.histXY = h->xy, A.histR = h->R, A.histT = h->t, A.cen = h->cen;
-    A.F.nCams = h->nCams, A.F.N = h->N, A.F.nMap = nMap, A.F.curFrame = curFrame, A.F.segCap = h->segCap;
-    A.F.pointFeat = d_pointFeat, A.F.featRef = (int4*)d_featRef, A.F.refStatic = d_refStatic, A.F.segPool = h->segPool, A.F.segCount = h->segCount;
-    A.F.counts = d_counts;
+    if (const int rc = ar_fill_refine(who, A, h, cams, nMap, curFrame, d_featRef, d_select, d_mapPts, d_mapCov, pixelErrVar)) return rc;
+    if (const int rc = fr_fill(who, A.F, h, cams, nMap, d_pointFeat, curFrame, d_featRef, d_refStatic, d_counts)) return rc;
     A.list = d_list, A.nList = nList, A.advAll = advanceAll ? 1 : 0;
+    A.blocksA = ((advanceAll ? nMap : nList) + 255) / 256;
     CS_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)hip_stream;
-    if (nMap > h->aliveCap) {
-        if (h->alive) CS_HIP(hipFree(h->alive));
-        h->alive = nullptr, h->aliveCap = 0;
-        CS_HIP(hipMalloc((void**)&h->alive, (size_t)nMap));
-        CS_HIP(hipMemsetAsync(h->alive, 1, (size_t)nMap, s));
-        h->aliveCap = nMap;
-    }
+    if (const int rc = hist_alive(h, nMap, s)) return rc;
     A.F.alive = h->alive;
-    for (int c = 0; c < h->nCams; ++c) {
-        if (!cams[c].K || !cams[c].iK || !cams[c].trackSpan) {
-            cs_set_error("cs_feat_ref_advance_refine_dev: null pointer in camera %d (K, iK, trackSpan are read)", c);
-            return CS_ERR_INVALID;
-        }
-        A.cam[c] = cams[c];
-    }
     hist_centres(h, s);
-    A.blocksA = ((advanceAll ? nMap : nList) + 255) / 256;
     hipLaunchKernelGGL(k_advance_refine, dim3(A.blocksA + (nList + 3) / 4), dim3(256), 0, s, A);
+    if (clearSelect) hipLaunchKernelGGL(k_clear_marks, dim3((nList + 255) / 256), dim3(256), 0, s, d_select, d_list, nList, nMap);
     CS_HIP(hipGetLastError());
     return CS_OK;
 }
@@ -3042,25 +3069,14 @@ __global__ __launch_bounds__(RR_THREADS) void k_revisit_rounds(RrArgs A) {
         __syncthreads();   // (the refine below clears the marks the advance above reads)
         for (int j = wave; j < n; j += RR_THREADS / 64) {
             const int m = list[j];
-            if (m >= 0 && m < A.ar.nMap && A.ar.select[m]) ar_refine_row(A.ar, m, lane, cnt);   // (uniform over the wave)
+            if (m >= 0 && m < A.ar.nMap && A.ar.select[m]) {   // (uniform over the wave)
+                ar_refine_row(A.ar, m, lane, cnt);
+                if (lane == 0) A.ar.selectW[m] = 0;   // (the row's owner, behind the barrier above: ArArgs' rule)
+            }
         }
         __syncthreads();
     }
-    if (A.ar.F.counts) {   // one atomic per counter (k_advance_refine: one per workgroup and round; the sums are the same)
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            int v = cnt[k];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) sCnt[wave][k] = v;
-        }
-        __syncthreads();
-        if (tid < 5) {
-            int v = 0;
-            for (int w = 0; w < RR_THREADS / 64; ++w) v += sCnt[w][tid];
-            if (v) atomicAdd(A.ar.F.counts + tid, v);
-        }
-    }
+    fr_fold_counts(cnt, sCnt, A.ar.F.counts);   // (one atomic per counter: k_advance_refine's are one per workgroup and round; the sums are the same)
 }
 // The dynamic LDS a launch of k_revisit_rounds<MC> may carry on this device: the default 64 KB for 8 cameras, the compute unit's 160 KB
 // for 16 (whose rows' state alone is 68 KB: the attribute is set when the device is first asked about, not per launch), less the kernel's own.
@@ -3094,34 +3110,28 @@ extern "C" int cs_register_revisit_rounds_dev(cs_track_history* h, void* hip_str
                                               unsigned char* d_attached, unsigned char* d_regOut, void* d_decideScratch, const int* d_curList,
                                               const int* d_curCount, int curCap, int* d_rvCnt, cs_feat_ref* d_featRef, unsigned char* d_refStatic,
                                               int* d_frefCounts) {
-    // the checks of the four calls it replaces (cs_register_search_passes_range_dev, cs_register_mergability_running_list_dev,
-    // cs_register_revisit_decide_next_dev, cs_feat_ref_advance_refine_dev) and of the rounds' lists (cs_register_decide_kinds_rounds_dev)
+    // its own checks -- the pass and its cameras (cs_register_search_passes_range_dev's), the ranges, the rounds' lists
+    // (cs_register_decide_kinds_rounds_dev's) -- then the fillers of the calls it fuses, each with the null checks of what its phase reads
+    const char* who = "cs_register_revisit_rounds_dev";
     if (!h || !regCams || !cams || !pass) {
-        cs_set_error("cs_register_revisit_rounds_dev: bad arguments (null history, cameras or pass)");
+        cs_set_error("%s: bad arguments (null history, cameras or pass)", who);
         return CS_ERR_INVALID;
     }
     const int nCams = h->nCams, N = h->N;
     const cs_register_pass& q = *pass;
     if (nCams < 1 || nCams > RG_MAX_CAMS || nCams > RD_MAX_CAMS || N < 1 || W < 1 || H < 1 || !(q.maxDist > 0) || !(q.sigmaSearch >= 0) ||
         !(q.sigmaMerge >= 0) || (q.mapFlags && !(q.maxDistDynamic > 0))) {
-        cs_set_error("cs_register_revisit_rounds_dev: bad arguments (1..%d cameras, N >= 1, maxDist > 0; mapFlags with maxDistDynamic > 0)", RD_MAX_CAMS);
+        cs_set_error("%s: bad arguments (1..%d cameras, N >= 1, maxDist > 0; mapFlags with maxDistDynamic > 0)", who, RD_MAX_CAMS);
         return CS_ERR_INVALID;
     }
     if (!q.M || !q.cov || !q.pointFeat || !q.slot || !q.m || !q.var || !q.dist || !q.flags || q.M != d_mapPts || q.cov != d_mapCov ||
         q.pointFeat != d_pointFeat) {
-        cs_set_error("cs_register_revisit_rounds_dev: the pass needs every table, and its map, covariances and feature table are the ones refined");
+        cs_set_error("%s: the pass needs every table, and its map, covariances and feature table are the ones refined", who);
         return CS_ERR_INVALID;
     }
     if (nMap < 1 || cap < 1 || cap > RV_MAX_ROWS || nRounds < 1 || nRounds > 8 || kinds < 1 || kinds > 3 || mapBase < 0 || !(tolPix >= 0) ||
-        !d_mapPts || !d_mapCov || !d_mergeCache || !d_mergeable || !d_rvLists || !d_rvCounts || !d_visitLoop || !d_nextLoop || !d_mapFlags ||
-        !d_pointFeat || !d_slot2map || !d_attached || !d_regOut || !d_decideScratch || !d_curList || !d_curCount || !d_featRef ||
-        (long long)nCams * N > RD_FEAT || (long long)nCams * nMap * nCams > 0x7fffffffLL) {
-        cs_set_error("cs_register_revisit_rounds_dev: bad arguments (1..%d rows, 1..8 rounds, kinds 1..3, every table)", RV_MAX_ROWS);
-        return CS_ERR_INVALID;
-    }
-    if (h->count < 1 || curFrame != h->lastFrame) {
-        cs_set_error("cs_register_revisit_rounds_dev: the history's newest entry must be frame %d (it holds %d frame(s), the newest %d)", curFrame,
-                     h->count, h->lastFrame);
+        !d_rvLists || !d_rvCounts || (long long)nCams * N > RD_FEAT || (long long)nCams * nMap * nCams > 0x7fffffffLL) {
+        cs_set_error("%s: bad arguments (1..%d rows, 1..8 rounds, kinds 1..3, the rounds' lists and counts)", who, RV_MAX_ROWS);
         return CS_ERR_INVALID;
     }
     RrArgs A;
@@ -3129,15 +3139,7 @@ extern "C" int cs_register_revisit_rounds_dev(cs_track_history* h, void* hip_str
     for (int c = 0; c < nCams; ++c) {
         const cs_register_cam& rc = regCams[c];
         if (!rc.K || !rc.R || !rc.t || !rc.xy || !rc.state || !rc.slot2map) {
-            cs_set_error("cs_register_revisit_rounds_dev: null pointer in search camera %d", c);
-            return CS_ERR_INVALID;
-        }
-        if (!cams[c].K || !cams[c].iK || !cams[c].trackSpan) {
-            cs_set_error("cs_register_revisit_rounds_dev: null pointer in camera %d (K, iK, trackSpan are read)", c);
-            return CS_ERR_INVALID;
-        }
-        if (!d_slot2map[c]) {
-            cs_set_error("cs_register_revisit_rounds_dev: null slot2map of camera %d", c);
+            cs_set_error("%s: null pointer in search camera %d", who, c);
             return CS_ERR_INVALID;
         }
         A.rcam[c] = rc;
@@ -3145,34 +3147,16 @@ extern "C" int cs_register_revisit_rounds_dev(cs_track_history* h, void* hip_str
     A.nRounds = nRounds, A.W = W, A.H = H, A.lists = d_rvLists, A.rvCounts = d_rvCounts;
     A.pass = q;
     A.pass.P = cap, A.pass.list = nullptr;
-    // the mergability (cs_register_mergability_running_list_dev's set-up: no counters)
-    MgCore& G = A.mg.a;
-    G.cam0 = 0, G.nCams = nCams, G.N = N, G.P = nMap, G.H = h->H, G.head = h->head, G.nHist = hist_walk(h);
-    G.sigma = pixelErrVar, G.M = d_mapPts, G.cov = d_mapCov, G.slot = q.slot, G.out = d_mergeable;
-    G.histXY = h->xy, G.histR = h->R, G.histT = h->t;
-    A.mg.W = hist_walk(h), A.mg.count = h->count, A.mg.curFrame = h->lastFrame, A.mg.epoch = h->tailEpoch, A.mg.fromMin = h->tailFromMin;
-    A.mg.tolPix = tolPix, A.mg.cache = (MgCache*)d_mergeCache, A.mg.counts = nullptr, A.mg.flags = q.flags;
-    // the walks (cs_register_revisit_decide_next_dev's)
-    RvArgs& V = A.rv;
-    V.nCams = nCams, V.N = N, V.P = nMap, V.cap = cap, V.mapBase = mapBase, V.kinds = kinds, V.nextLoop = d_nextLoop, V.visitLoop = d_visitLoop;
-    V.slot = q.slot, V.flags = q.flags, V.mergeable = d_mergeable, V.mapFlags = d_mapFlags, V.pointFeat = d_pointFeat;
-    for (int c = 0; c < nCams; ++c) V.slot2map[c] = d_slot2map[c];
-    V.attached = d_attached, V.regOut = d_regOut, V.curList = d_curList, V.curCount = d_curCount, V.curCap = curCap, V.counts = d_rvCnt;
-    V.nextLoopW = d_nextLoop, V.overflow = d_rvCounts + nRounds;
-    V.debug = cs_debug_get(CS_DBG_MERGE_PRINT) == 1;
-    int* scr = rd_scratch_owners(d_decideScratch, nCams, nMap);   // (cs_register_decide_kinds_dev's carve-up: head | code | base | owner x 3 | ...)
-    for (int k = 0; k < 3; ++k) V.owner[k] = scr, scr += (size_t)nCams * N;
-    // advance + refine (cs_feat_ref_advance_refine_dev's, over a list, the marks consumed)
-    ArArgs& R = A.ar;
-    R.nMap = nMap, R.featRef = (const int4*)d_featRef, R.mapPts = d_mapPts, R.mapCov = d_mapCov, R.sigma = pixelErrVar;
-    R.refine = 1, R.select = d_regOut, R.selectW = d_regOut, R.clearSelect = 1;
-    R.segPool = h->segPool, R.segCap = h->segCap, R.curFrame = h->lastFrame, R.stored = h->count < h->H ? h->count : h->H;
-    R.nCams = nCams, R.N = N, R.H = h->H, R.head = h->head, R.nHist = hist_walk(h);
-    R.histXY = h->xy, R.histR = h->R, R.histT = h->t, R.cen = h->cen;
-    R.F.nCams = nCams, R.F.N = N, R.F.nMap = nMap, R.F.curFrame = curFrame, R.F.segCap = h->segCap;
-    R.F.pointFeat = d_pointFeat, R.F.featRef = (int4*)d_featRef, R.F.refStatic = d_refStatic, R.F.segPool = h->segPool, R.F.segCount = h->segCount;
-    R.F.counts = d_frefCounts;
-    for (int c = 0; c < nCams; ++c) R.cam[c] = cams[c];
+    // over the rounds' lists: no list of their own in the blocks below; the mergability without counters, the marks consumed
+    if (const int rc = ar_fill_refine(who, A.ar, h, cams, nMap, curFrame, d_featRef, d_regOut, d_mapPts, d_mapCov, pixelErrVar)) return rc;
+    if (const int rc = fr_fill(who, A.ar.F, h, cams, nMap, d_pointFeat, curFrame, d_featRef, d_refStatic, d_frefCounts)) return rc;
+    if (const int rc = mg_fill_running(who, A.mg, h, cams, 0, nMap, d_mapPts, d_mapCov, q.slot, q.flags, pixelErrVar, tolPix, d_mergeCache,
+                                       d_mergeable, nullptr))
+        return rc;
+    if (const int rc = rv_fill(who, A.rv, nCams, N, nMap, cap, mapBase, kinds, d_nextLoop, d_visitLoop, q.slot, q.flags, d_mergeable, d_mapFlags,
+                               d_pointFeat, d_slot2map, d_attached, d_regOut, d_decideScratch, d_curList, d_curCount, curCap, d_rvCnt,
+                               d_rvCounts + nRounds))
+        return rc;
     CS_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)hip_stream;
     const int MC = nCams <= 8 ? 8 : RD_MAX_CAMS;
@@ -3180,18 +3164,12 @@ extern "C" int cs_register_revisit_rounds_dev(cs_track_history* h, void* hip_str
     size_t ldsMax = 0;   // (checked before anything is enqueued: a refused call leaves nothing behind)
     if (const int rc = MC == 8 ? rr_dynamic_lds_limit<8>(h->device, &ldsMax) : rr_dynamic_lds_limit<RD_MAX_CAMS>(h->device, &ldsMax)) return rc;
     if (lds > ldsMax) {
-        cs_set_error("cs_register_revisit_rounds_dev: %zu B of LDS (a history window of %d frames, lists of %d rows, %d cameras) where the "
-                     "launch may carry %zu", lds, A.mg.W, cap, nCams, ldsMax);
+        cs_set_error("%s: %zu B of LDS (a history window of %d frames, lists of %d rows, %d cameras) where the launch may carry %zu", who, lds,
+                     A.mg.W, cap, nCams, ldsMax);
         return CS_ERR_INVALID;
     }
-    if (nMap > h->aliveCap) {
-        if (h->alive) CS_HIP(hipFree(h->alive));
-        h->alive = nullptr, h->aliveCap = 0;
-        CS_HIP(hipMalloc((void**)&h->alive, (size_t)nMap));
-        CS_HIP(hipMemsetAsync(h->alive, 1, (size_t)nMap, s));
-        h->aliveCap = nMap;
-    }
-    R.F.alive = h->alive;
+    if (const int rc = hist_alive(h, nMap, s)) return rc;
+    A.ar.F.alive = h->alive;
     hist_centres(h, s);
     if (MC == 8)
         hipLaunchKernelGGL(k_revisit_rounds<8>, dim3(1), dim3(RR_THREADS), lds, s, A);
@@ -3248,14 +3226,6 @@ extern "C" int cs_track_history_download_segments(const cs_track_history* h, cs_
     return CS_OK;
 }
 
-namespace {
-// the reference tables of a *_ref_dev call into the launch arguments
-template <class Args>
-void up_set_refs(Args& A, const cs_track_history* h) {
-    A.segPool = h->segPool, A.segCap = h->segCap, A.curFrame = h->lastFrame, A.stored = h->count < h->H ? h->count : h->H;
-}
-}  // namespace
-
 extern "C" int cs_update_new_poses_points_ref_dev(const cs_track_history* h, void* hip_stream, const cs_poseupdate_cam* cams,
                                                   const cs_feat_ref* d_featRef, const unsigned char* d_refStatic, int nMap, const int* d_lastFrame,
                                                   const unsigned char* d_isCurrent, int firstKeyFrame, double* d_mapPts, double* d_mapCov,
@@ -3309,11 +3279,10 @@ int cu_launch(const char* who, const cs_track_history* h, void* hip_stream, cons
     if (nPairs == 0) return CS_OK;
     CuArgs A;
     memset(&A, 0, sizeof(A));
-    A.nCams = h->nCams, A.N = h->N, A.H = h->H, A.head = h->head, A.nHist = hist_walk(h), A.nPairs = nPairs;
-    A.pf1 = d_pf1, A.pf2 = d_pf2, A.M1 = d_M1, A.M2 = d_M2;
+    hist_set_ring(A, h);
+    A.nPairs = nPairs, A.pf1 = d_pf1, A.pf2 = d_pf2, A.M1 = d_M1, A.M2 = d_M2;
     A.ref1 = (const int4*)d_ref1, A.ref2 = (const int4*)d_ref2;
     if (byRef) up_set_refs(A, h);
-    A.histXY = h->xy, A.histR = h->R, A.histT = h->t, A.cen = h->cen;
     A.sigma = pixelErrVar;
     A.ok = d_ok, A.M = d_M, A.cov = d_cov;
     for (int c = 0; c < h->nCams; ++c) {
@@ -3378,8 +3347,7 @@ extern "C" int cs_register_decide_merge_list_dev(const cs_track_history* h, void
     }
     DmArgs A;
     memset(&A, 0, sizeof(A));
-    A.cu.nCams = h->nCams, A.cu.N = h->N, A.cu.H = h->H, A.cu.head = h->head, A.cu.nHist = hist_walk(h);
-    A.cu.histXY = h->xy, A.cu.histR = h->R, A.cu.histT = h->t, A.cu.cen = h->cen;
+    hist_set_ring(A.cu, h);
     A.cu.sigma = pixelErrVar;
     for (int c = 0; c < h->nCams; ++c) {
         if (!cams[c].K || !cams[c].iK || !cams[c].trackSpan || !cams[c].slot2map) {
@@ -3393,7 +3361,7 @@ extern "C" int cs_register_decide_merge_list_dev(const cs_track_history* h, void
     A.mapPts = d_mapPts, A.mapCov = d_mapCov, A.attached = d_attached, A.regged = d_regged, A.inVec = (unsigned char*)d_scratch, A.counts = d_counts;
     A.list = d_list, A.nList = nList;
     A.featRef = h->mergeFeatRef, A.refStatic = h->mergeRefStatic, A.segPoolW = h->segPool, A.segCount = h->segCount;
-    if (A.featRef) A.cu.segPool = h->segPool, A.cu.segCap = h->segCap, A.cu.curFrame = h->lastFrame, A.cu.stored = h->count < h->H ? h->count : h->H;
+    if (A.featRef) up_set_refs(A.cu, h);
     A.debug = cs_debug_get(CS_DBG_MERGE_PRINT) == 1;   // (cs_debug_set("merge_print", 1): the kernel prints its own account)
     CS_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)hip_stream;
@@ -3440,12 +3408,12 @@ static int cls_run(const cs_track_history* h, void* hip_stream, const cs_poseupd
     }
     ClsArgs A;
     memset(&A, 0, sizeof(A));
-    A.nCams = h->nCams, A.N = h->N, A.nMap = nMap, A.H = h->H, A.head = h->head, A.nHist = hist_walk(h), A.curFrame = curFrame;
+    hist_set_ring(A, h);
+    A.nMap = nMap, A.curFrame = curFrame;
     A.pointFeat = d_pointFeat, A.featFrame = d_featFrame, A.featFirst = d_featFirst;
     A.featRef = h->clsFeatRef, A.refStatic = h->clsRefStatic, A.segPool = h->segPool, A.segCap = h->segCap;
     A.stored = h->count < h->H ? h->count : h->H;
     if (A.featRef) A.featFrame = nullptr, A.featFirst = nullptr;
-    A.histXY = h->xy, A.histR = h->R, A.histT = h->t, A.cen = h->cen;
     A.mapPts = d_mapPts, A.mapCov = d_mapCov, A.mapFlags = d_mapFlags, A.newPt = d_newPt, A.staticFrameNum = d_staticFrameNum;
     A.firstFrame = d_firstFrame;
     A.sigma = pixelVar;

@@ -834,22 +834,18 @@ extern "C" int cs_register_revisit_decide_next_dev(int device, void* hip_stream,
         cs_set_error("cs_register_revisit_decide_next_dev: the next round's list and its count go together");
         return CS_ERR_INVALID;
     }
-    if (nCams < 1 || nCams > RD_MAX_CAMS || N < 1 || P < 1 || cap < 1 || cap > RV_MAX_ROWS || kinds < 1 || kinds > 3 || !d_list || !d_nextLoop || !d_visitLoop ||
-        !d_slot || !d_flags || !d_mergeable || !d_mapFlags || !d_pointFeat || !d_slot2map || !d_attached || !d_regOut || !d_decideScratch ||
-        !d_curList || !d_curCount || (long long)nCams * N > RD_FEAT || (long long)nCams * P * nCams > 0x7fffffffLL) {
+    if (nCams < 1 || nCams > RD_MAX_CAMS || N < 1 || P < 1 || cap < 1 || cap > RV_MAX_ROWS || kinds < 1 || kinds > 3 || !d_list ||
+        (long long)nCams * N > RD_FEAT || (long long)nCams * P * nCams > 0x7fffffffLL) {
         cs_set_error("cs_register_revisit_decide_dev: bad arguments");
         return CS_ERR_INVALID;
     }
     RvArgs A;
     memset(&A, 0, sizeof(A));
-    A.nCams = nCams, A.N = N, A.P = P, A.cap = cap, A.mapBase = mapBase, A.kinds = kinds, A.list = d_list, A.nextLoop = d_nextLoop, A.visitLoop = d_visitLoop;
-    A.slot = d_slot, A.flags = d_flags, A.mergeable = d_mergeable, A.mapFlags = d_mapFlags, A.pointFeat = d_pointFeat;
-    for (int c = 0; c < nCams; ++c) A.slot2map[c] = d_slot2map[c];
-    A.attached = d_attached, A.regOut = d_regOut, A.curList = d_curList, A.curCount = d_curCount, A.curCap = curCap, A.counts = d_counts, A.listCount = d_listCount;
-    A.nextList = d_nextList, A.nextCount = d_nextCount, A.nextLoopW = d_nextLoop, A.overflow = d_overflow;
-    A.debug = cs_debug_get(CS_DBG_MERGE_PRINT) == 1;
-    int* scr = rd_scratch_owners(d_decideScratch, nCams, P);   // (cs_register_decide_kinds_dev's carve-up: head | code | base | owner x 3 | ...)
-    for (int k = 0; k < 3; ++k) A.owner[k] = scr, scr += (size_t)nCams * N;
+    if (const int rc = rv_fill("cs_register_revisit_decide_dev", A, nCams, N, P, cap, mapBase, kinds, d_nextLoop, d_visitLoop, d_slot, d_flags, d_mergeable,
+                               d_mapFlags, d_pointFeat, d_slot2map, d_attached, d_regOut, d_decideScratch, d_curList, d_curCount, curCap, d_counts,
+                               d_overflow))
+        return rc;
+    A.list = d_list, A.listCount = d_listCount, A.nextList = d_nextList, A.nextCount = d_nextCount;
     CS_HIP(hipSetDevice(device));
     if (nCams <= 8)
         hipLaunchKernelGGL(k_revisit_decide<8>, dim3(1), dim3(cap <= 256 ? 256 : (cap + 63) / 64 * 64), 0, (hipStream_t)hip_stream, A);

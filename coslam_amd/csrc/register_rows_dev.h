@@ -182,6 +182,34 @@ struct RvArgs {
     int debug;                       // cs_debug_set("merge_print", 1): the launch prints where its time went
 };
 constexpr int RV_MAX_ROWS = 1024;
+// what the walks of every round read, for the launch of one round (k_revisit_decide) and for the one that plays them all (k_revisit_rounds):
+// the tables, the owner arrays out of the decision's scratch, where the points beyond the next list are counted.  A round's own list and the
+// next one's (list, listCount, nextList, nextCount) are the caller's; the ranges (cameras, rows, kinds) it has checked.
+inline int rv_fill(const char* who, RvArgs& A, int nCams, int N, int P, int cap, int mapBase, int kinds, int* d_nextLoop, int* d_visitLoop,
+                   const int* d_slot, const int* d_flags, const unsigned char* d_mergeable, const unsigned char* d_mapFlags, int* d_pointFeat,
+                   int* const* d_slot2map, unsigned char* d_attached, unsigned char* d_regOut, void* d_decideScratch, const int* d_curList,
+                   const int* d_curCount, int curCap, int* d_counts, int* d_overflow) {
+    if (!d_nextLoop || !d_visitLoop || !d_slot || !d_flags || !d_mergeable || !d_mapFlags || !d_pointFeat || !d_slot2map || !d_attached || !d_regOut ||
+        !d_decideScratch || !d_curList || !d_curCount) {
+        cs_set_error("%s: bad arguments (every table of the walks)", who);
+        return CS_ERR_INVALID;
+    }
+    for (int c = 0; c < nCams; ++c) {
+        if (!d_slot2map[c]) {
+            cs_set_error("%s: null slot2map of camera %d", who, c);
+            return CS_ERR_INVALID;
+        }
+        A.slot2map[c] = d_slot2map[c];
+    }
+    A.nCams = nCams, A.N = N, A.P = P, A.cap = cap, A.mapBase = mapBase, A.kinds = kinds, A.nextLoop = d_nextLoop, A.visitLoop = d_visitLoop;
+    A.slot = d_slot, A.flags = d_flags, A.mergeable = d_mergeable, A.mapFlags = d_mapFlags, A.pointFeat = d_pointFeat;
+    A.attached = d_attached, A.regOut = d_regOut, A.curList = d_curList, A.curCount = d_curCount, A.curCap = curCap, A.counts = d_counts;
+    A.nextLoopW = d_nextLoop, A.overflow = d_overflow;
+    A.debug = cs_debug_get(CS_DBG_MERGE_PRINT) == 1;
+    int* scr = rd_scratch_owners(d_decideScratch, nCams, P);   // (cs_register_decide_kinds_dev's carve-up: head | code | base | owner x 3 | ...)
+    for (int k = 0; k < 3; ++k) A.owner[k] = scr, scr += (size_t)nCams * N;
+    return CS_OK;
+}
 // a round's list and the next round's: RvArgs' own fields, or (k_revisit_rounds) the round's slices of the frame's lists
 struct RvRound {
     const int* list;

@@ -970,8 +970,8 @@ int cs_feat_ref_advance_list_dev(cs_track_history* h, void* hip_stream, const cs
 /* cs_feat_ref_advance_(list_)dev and cs_refine_map_points_ref_dev of the same rows as ONE launch (the pose stream's launches are its
  * time: DESIGN.md 3.13.1): the rows of d_list[0 .. nList) with d_select[m] != 0 are advanced AND refined (CoSLAM::refineMapPoint,
  * src/app/SL_CoSLAM.cpp:666-713, over the references just written), every other row -- of the whole map when advanceAll, else of the
- * list -- is advanced only.  A row that is to be refined has to be on the list.  clearSelect: the marks are consumed (set to 0).  Same
- * tables and map as the two calls. */
+ * list -- is advanced only.  A row that is to be refined has to be on the list.  clearSelect: the marks are consumed (the listed rows'
+ * set to 0 by a small launch BEHIND the one that read them).  Same tables and map as the two calls. */
 int cs_feat_ref_advance_refine_dev(cs_track_history* h, void* hip_stream, const cs_poseupdate_cam* cams, int nMap, const int* d_pointFeat,
                                    int curFrame, cs_feat_ref* d_featRef, unsigned char* d_refStatic, int* d_counts, const int* d_list, int nList,
                                    int advanceAll, unsigned char* d_select, int clearSelect, double* d_mapPts, double* d_mapCov,

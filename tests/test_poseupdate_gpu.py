@@ -927,6 +927,86 @@ def test_feature_references_follow_the_registration_like_the_references_pointers
     th.close()
 
 
+def test_advance_refine_relinks_every_row_once_and_consumes_the_marks_behind_the_launch():
+    """cs_feat_ref_advance_refine_dev with clearSelect over a map whose every row is marked and re-links in camera 0: 1024 rows = 4
+    advance-only workgroups next to 256 refine workgroups in ONE launch, all looking at the same marks.  A row is advanced once, by its own
+    wave: 1024 re-links, 1024 pool segments -- each the row's old reference, each named by one reference --, camera 1's stale references
+    stand, every mark is cleared, and map and covariances are the bytes cs_feat_ref_advance_dev + cs_refine_map_points_ref_dev leave on a
+    second copy of the tables.  Slot k of both cameras shows point k in the frame before and point k - 1 in this one: a row's old feature
+    (slot a) and its new one (slot a + 1, a track of its own) are views of one point."""
+    import torch
+
+    from coslam_amd.poseupdate import TrackHistory
+
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    d = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    nC, N, nMap, cur, sigma = 2, 8, 1024, 21, 3.0
+    K = np.array([[500.0, 0, 320], [0, 500, 240], [0, 0, 1]])
+    k_ = np.arange(N)
+    X = np.stack([0.3 * (k_ - 3.5), 0.2 * ((3 * k_) % N - 3.5), 5 + 0.25 * k_], axis=1)
+    t = {(0, cur - 1): [0.0, 0, 0], (0, cur): [-0.4, 0, 0], (1, cur - 1): [-1.0, 0.1, 0], (1, cur): [-1.2, 0.1, 0]}   # R = I throughout
+
+    def pixels(c, f):
+        q = (X if f == cur - 1 else np.roll(X, 1, axis=0)) + np.asarray(t[c, f])
+        uv = (K @ q.T).T
+        return np.concatenate([uv[:, 0] / uv[:, 2], uv[:, 1] / uv[:, 2]])
+
+    a = np.arange(nMap) % N
+    b = (a + 1) % N
+    span = np.stack([np.full(2 * N, cur, np.int32), np.full(2 * N, cur - 1, np.int32)])   # camera 0: new tracks; camera 1: tracks that ended
+    ref0 = np.full((nMap, nC, 4), -1, np.int32)
+    ref0[:, :, 0], ref0[:, :, 1], ref0[:, :, 2] = a[:, None], cur - 1, cur - 1
+    pf = np.stack([b, np.full(nMap, -1)], axis=1).astype(np.int32)
+    M0 = X[a] + np.random.default_rng(5).normal(size=(nMap, 3)) * 0.05
+    cov0 = np.tile(np.eye(3).reshape(9), (nMap, 1))
+    d_K, d_iK, d_span = d(K.reshape(9)), d(np.linalg.inv(K).reshape(9)), d(span)
+    d_stat, d_state = torch.ones((nC, N), dtype=torch.uint8, device=dev), torch.zeros((nC, N), dtype=torch.int32, device=dev)
+    d_s2m, d_fl = torch.full((nC, N), -1, dtype=torch.int32, device=dev), torch.zeros(nMap, dtype=torch.uint8, device=dev)
+    d_eye, d_pf = d(np.tile(np.eye(3).reshape(9), (nC, 1))), d(pf)
+
+    def tables():
+        th = TrackHistory(nC, N, 2)
+        keep = []
+        for f in (cur - 1, cur):
+            xy, d_t = d(np.stack([pixels(c, f) for c in range(nC)])), d(np.array([t[c, f] for c in range(nC)], dtype=np.float64))
+            keep += [xy, d_t]
+            cams = [dict(K=d_K.data_ptr(), iK=d_iK.data_ptr(), xy=xy[c].data_ptr(), state=d_state[c].data_ptr(), slot2map=d_s2m[c].data_ptr(),
+                         trackSpan=d_span[c].data_ptr(), isStatic=d_stat[c].data_ptr()) for c in range(nC)]
+            th.detect_dynamic_dev(s, cams, d_eye.data_ptr(), d_t.data_ptr(), nMap, d_fl.data_ptr(), f, minLen=1 << 30)
+        T = dict(th=th, keep=keep, ref=d(ref0), rs=torch.zeros((nMap, nC), dtype=torch.uint8, device=dev), M=d(M0), cov=d(cov0),
+                 sel=torch.ones(nMap, dtype=torch.uint8, device=dev), cnt=torch.zeros(5, dtype=torch.int32, device=dev))
+        T["cams"] = [dict(K=d_K.data_ptr(), iK=d_iK.data_ptr(), trackSpan=d_span[c].data_ptr(), isStatic=d_stat[c].data_ptr()) for c in range(nC)]
+        return T
+
+    A, B = tables(), tables()
+    d_list = torch.arange(nMap, dtype=torch.int32, device=dev)
+    A["th"].feat_ref_advance_refine_dev(s, A["cams"], nMap, d_pf.data_ptr(), cur, A["ref"].data_ptr(), A["rs"].data_ptr(), d_list.data_ptr(), nMap, True,
+                                        A["sel"].data_ptr(), True, A["M"].data_ptr(), A["cov"].data_ptr(), sigma, d_counts=A["cnt"].data_ptr())
+    B["th"].feat_ref_advance_dev(s, B["cams"], nMap, d_pf.data_ptr(), cur, B["ref"].data_ptr(), d_refStatic=B["rs"].data_ptr(), d_counts=B["cnt"].data_ptr())
+    B["th"].refine_map_points_ref_dev(s, B["cams"], B["ref"].data_ptr(), nMap, B["M"].data_ptr(), B["cov"].data_ptr(), sigma, d_select=B["sel"].data_ptr())
+    torch.cuda.synchronize()
+    old = ref0[:, 0]
+    for name, T in (("one launch", A), ("two calls", B)):
+        ref, pool, (nSeg, _) = T["ref"].cpu().numpy(), T["th"].segments(), T["th"].segment_counts()
+        print(name, "counts", T["cnt"].tolist(), "segments", nSeg.tolist(), "marks left", int(T["sel"].sum().item()))
+        assert T["cnt"].tolist() == [0, 0, nMap, 0, 0], name
+        assert nSeg.tolist() == [nMap, 0], name
+        assert np.array_equal(np.sort(ref[:, 0, 3]), np.arange(nMap)), name                         # a permutation: no segment named twice
+        assert np.array_equal(pool[0][ref[:, 0, 3]], old), name                                     # every segment is its row's old reference
+        assert np.array_equal(ref[:, 0, :3], np.stack([b, np.full(nMap, cur), np.full(nMap, cur)], axis=1)), name
+        assert np.array_equal(ref[:, 1], ref0[:, 1]), name                                          # stale: stands as it was
+    assert int(A["sel"].sum().item()) == 0 and int(B["sel"].sum().item()) == nMap                   # consumed / the plain refine leaves them
+    M, cov = A["M"].cpu().numpy(), A["cov"].cpu().numpy()
+    assert np.array_equal(M, B["M"].cpu().numpy()) and np.array_equal(cov, B["cov"].cpu().numpy())
+    assert np.array_equal(A["rs"].cpu().numpy(), B["rs"].cpu().numpy())
+    # (segments as sets: an index into the pool is handed out by an atomic)
+    assert sorted(map(tuple, A["th"].segments()[0])) == sorted(map(tuple, B["th"].segments()[0]))
+    # every row was refined, to its point (the pixels are exact projections in binary64: what is left is rounding, orders below 1e-6)
+    assert np.isfinite(M).all() and (M != M0).any(axis=1).all() and np.abs(M - X[a]).max() < 1e-6
+    A["th"].close(), B["th"].close()
+
+
 def _golden_ring(g, sc, dev, s):
     """the history of golden scene sc: the ring filled frame by frame with placeholder poses, then given the scene's poses (the way
     test_update_new_poses_points_reproduces_the_reference_on_its_golden_scenes builds it)"""
