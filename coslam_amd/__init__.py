@@ -40,4 +40,5 @@ from .grouping import (CameraGroups, GroupingCam, camera_grouping_dev, camera_gr
 from .merge import (MergeApply, MergeCamGroups, MergeConstraints, MergeFront, MergeMatcher, MergePoseCorrection, merge_first_constrain,  # noqa: F401,E402
                     merge_keygraph_plan, merge_match_fmat, merge_match_select, merge_matched_groups, ncc_small_image_dev,
                     recompute_map_points_keyfrms_dev)
+from .surf import Surf  # noqa: F401,E402
 from .liveview import LiveHeader, LiveView, MapCounts, map_counts_dev, map_counts_scratch_bytes  # noqa: F401,E402

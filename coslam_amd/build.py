@@ -31,6 +31,7 @@ HIP_SOURCES = [
     "merge_constraints.hip",
     "merge_match.hip",
     "merge_front.hip",
+    "surf.hip",
     "liveview.hip",
     "poseupdate.hip",
     "ncc.hip",

@@ -1313,7 +1313,7 @@ int cs_merge_match_select(int nInfo, const cs_merge_info* info, const int* surfN
 
 /* ---- the merge front: matchSURFPoints -> computeEMat -> getMatchedPts of matchMergableCameras (src/app/SL_MergeCameraGroup.cpp:360-378);
  * DESIGN.md 3.25 ----
- * From per-camera key points + descriptors (SURF detection stays outside) to what cs_merge_match_run_dev and cs_merge_match_select take per
+ * From per-camera key points + descriptors (cs_surf below computes them from the images) to what cs_merge_match_run_dev and cs_merge_match_select take per
  * candidate camera pair (a JOB): E, the seed rows, surfNum, ematOk.  matchSurf / estimateEMat / evaluateEMat are un-vendored: OUR definitions,
  * DESIGN.md 5.1 (restated in numpy by tests/mergefront_ref.py).  Per camera (host array): pts n x 2 doubles {x, y} and desc n x dimDesc
  * floats in DEVICE memory, n, K as 9 doubles in HOST memory (iK is formed on the host by cs_merge_match_fmat's mat33Inv).
@@ -1385,6 +1385,66 @@ int cs_merge_front_results(cs_merge_front* mf, void* hip_stream, int nJobs, cs_m
 int cs_merge_front_buffers_get(const cs_merge_front* mf, cs_merge_front_buffers* out);
 /* bytes of one of the handle's device buffers to the host; waits for hip_stream */
 int cs_merge_front_download(cs_merge_front* mf, void* hip_stream, const void* d_src, void* h_dst, size_t bytes);
+
+/* ---- SURF key points and descriptors: ::detectSURFPoints(img, surfPts, surfDesc) of mergeCamGroups (src/app/SL_MergeCameraGroup.cpp:
+ * 308-313), the primitive of NewMapPtsSURF::detectSURFPoints and InitMap::matchSurfBetween as well; DESIGN.md 3.26 ----
+ * The reference's SURF is external (OpenCV nonfree / asrl GPU-SURF): the definition is OURS, restated in numpy by
+ * tests/surf_ref.py.  Per camera a u8 image W x H with a row pitch in DEVICE memory; cs_surf_run_dev enqueues on hip_stream, for all
+ * cameras of the call in each launch and with no host wait:
+ *   integral    u32 [(H + 1)][(W + 1)], exact; EVERY box sum clamps its corners into the image (a box that leaves it is its part inside)
+ *   layers      octave o, layer l = 0 .. nOctaveLayers + 1: filter size L = (9 + 6 l) << o, a sample every 1 << o pixels; Dxx, Dyy, Dxy
+ *               integer box sums; det = dx dy - 0.81 dxy dxy in f64 from d = D / (L L); the Laplacian byte is dx + dy > 0; a layer
+ *               with L >= min(W, H) stays zero and takes no part
+ *   maxima      det > hessianThreshold and strictly above its 26 neighbours, margin (L_upper / 2) / step + 1 samples; the 3 x 3 Newton
+ *               step (explicit adjugate solve), rejected beyond 1 in any component or with determinant 0; the key point is the centre of
+ *               the filter window: half a pixel up-left of the interpolated sample where L is even (every octave above the first)
+ *   order       ascending (octave, layer, row, column) from counts and prefix sums; the first maxPts are kept, overflow counts the
+ *               rest; rows >= count: NaN pts / size / angle / response, zero descriptor, zero integers
+ *   orientation 109 Haar samples of size 4 s, 72 windows of 60 degrees every 5 degrees, sums in sample order (upright: angle 0)
+ *   descriptor  20 s window, 4 x 4 subregions of 5 x 5 samples, Haar size 2 s, sigma 3.3 s; 64: {sum dx, sum dy, sum |dx|, sum |dy|},
+ *               128: each split by the sign of the other component; unit L2 norm, f32; a zero norm gives a zero descriptor and NaN pts
+ * so that {pts, desc, n = maxPts} of a camera is a cs_merge_front_cam with no read-back of the count.  d_img: HOST array of nCams device
+ * pointers, NULL = camera skipped (count 0, all padding).  Results are the same bits from run to run.
+ * CS_ERR_INVALID before any launch (cs_last_error text): null handle or table, pitch < W, a non-finite or negative threshold; creation:
+ * nCams 1..16, maxPts 1..32768, nOctaves 1..5, nOctaveLayers 1..4, dimDesc 64 | 128, W, H >= 1, W H 255 < 2^32. */
+#define CS_SURF_MAX_OCTAVES 5
+#define CS_SURF_MAX_LAYERS 6          /* nOctaveLayers + 2 */
+#define CS_SURF_ORI_SAMPLES 109
+#define CS_SURF_ORI_WINDOWS 72
+typedef struct {
+    const double* pts;                /* [nCams][maxPts][2] {x, y} */
+    const float* desc;                /* [nCams][maxPts][dimDesc] */
+    const double* size;               /* [nCams][maxPts]; the scale is s = 1.2 size / 9 */
+    const double* angle;              /* [nCams][maxPts] */
+    const double* response;           /* [nCams][maxPts] */
+    const unsigned char* laplacian;   /* [nCams][maxPts] */
+    const int* octave;                /* [nCams][maxPts] */
+    const int* layer;                 /* [nCams][maxPts] */
+    const int* cell;                  /* [nCams][maxPts][2]: row, column of the sample in its octave's map */
+    const int* count;                 /* [nCams] */
+    const int* overflow;              /* [nCams] */
+    const unsigned int* integral;     /* [nCams][(H + 1)][(W + 1)] */
+    const double* det;                /* [nCams][mapElems]: layer l of octave o at mapOff[o * CS_SURF_MAX_LAYERS + l], mapH[o] x mapW[o] */
+    const unsigned char* lap;         /* [nCams][mapElems], as det */
+    int nCams, W, H, maxPts, nOctaves, nOctaveLayers, dimDesc, mapElems;
+    int mapW[CS_SURF_MAX_OCTAVES], mapH[CS_SURF_MAX_OCTAVES];
+    int mapOff[CS_SURF_MAX_OCTAVES * CS_SURF_MAX_LAYERS];      /* -1: no such layer */
+    int layerSize[CS_SURF_MAX_OCTAVES * CS_SURF_MAX_LAYERS];   /* L */
+    int layerFits[CS_SURF_MAX_OCTAVES * CS_SURF_MAX_LAYERS];
+} cs_surf_buffers;
+typedef struct cs_surf cs_surf;
+cs_surf* cs_surf_create(int device, int nCams, int W, int H, int maxPts, int nOctaves, int nOctaveLayers, int dimDesc);
+void cs_surf_destroy(cs_surf* sf);
+int cs_surf_run_dev(cs_surf* sf, void* hip_stream, const unsigned char* const* d_img /* host [nCams] */, int pitch, double hessianThreshold,
+                    int upright);
+/* the first stages alone: the integral images; those and the layer maps; those and the key-point lists (angle 0, descriptors zero) */
+int cs_surf_integral_dev(cs_surf* sf, void* hip_stream, const unsigned char* const* d_img /* host [nCams] */, int pitch);
+int cs_surf_layers_dev(cs_surf* sf, void* hip_stream, const unsigned char* const* d_img /* host [nCams] */, int pitch);
+int cs_surf_detect_dev(cs_surf* sf, void* hip_stream, const unsigned char* const* d_img /* host [nCams] */, int pitch, double hessianThreshold);
+/* count [nCams] and overflow [nCams] (either may be NULL) in host memory: the stage's ONE host wait */
+int cs_surf_counts(cs_surf* sf, void* hip_stream, int* count, int* overflow);
+int cs_surf_buffers_get(const cs_surf* sf, cs_surf_buffers* out);
+int cs_surf_download(cs_surf* sf, void* hip_stream, const void* d_src, void* h_dst, size_t bytes);
 
 /* CoSLAM::mapPointsClassify (src/app/SL_CoSLAM.cpp:418-520) over the references: from the next call on cs_map_points_classify_dev and
  * cs_pose_update_classify_frame_dev read d_featRef ([nMap][nCams], the table cs_feat_ref_advance_dev keeps: as the END of the previous
