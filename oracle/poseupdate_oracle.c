@@ -26,6 +26,7 @@
  *   getFMat(iK1, iK2, E, F)                     F = iK2^T E iK1
  *   epipolarError(F, a, b)                      distance of a from the line F (b, 1)
  * A slot's feature of this frame: hand-back state 0 (tracked) or 1 (new).  Map flags: bit 0 dynamic, bit 1 false, bit 2 uncertain. */
+#include <assert.h>
 #include <math.h>
 #include <string.h>
 
@@ -347,6 +348,7 @@ static int update_points_core(int nCams, int N, int nHist, const double* Ks, con
         int numView = 0, firstE[64], second[64];
         if (locStatic) { /* updateStaticPointPosition */
             for (int c = 0; c < nCams; c++) {
+                assert(c < 64); /* firstE / second: one entry per camera */
                 second[c] = -2;
                 int ref[4];
                 chain_ref(featRef, pointFeat, trackSpan, nCams, N, X.curFrame, m, c, ref);
@@ -374,6 +376,7 @@ static int update_points_core(int nCams, int N, int nHist, const double* Ks, con
         } else if (locDynamic && cur) { /* updateDynamicPointPosition; :266-269 never reaches it for the active list */
             int nDynamic = 0;
             for (int c = 0; c < nCams; c++) {
+                assert(c < 64); /* firstE / second: one entry per camera */
                 second[c] = -2;
                 int ref[4];
                 chain_ref(featRef, pointFeat, trackSpan, nCams, N, X.curFrame, m, c, ref);
@@ -666,6 +669,7 @@ static int cls_is_static(const opu_cls_ctx* X, const int* pf, int m, const doubl
     for (int c = 0; c < X->nCams; c++) {
         int s, j0, f, ff, seg;
         if (c == exclude || !cls_feature_seg(X, pf, m, c, &s, &j0, &f, &ff, &seg) || f < firstFrame) continue;
+        assert(nv + 2 <= 64); /* this view and its second */
         v[nv].c = c, v[nv].j = j0, v[nv].s = s, nv++;
         double C0[3];
         cam_center(cls_R(X, c, j0), cls_t(X, c, j0), C0);
@@ -698,6 +702,7 @@ static int cls_is_dynamic(const opu_cls_ctx* X, const int* pf, const unsigned ch
     for (int c = 0; c < X->nCams; c++) {
         int s, j0, f, ff;
         if (!cls_feature(X, pf, m, c, &s, &j0, &f, &ff) || f != X->curFrame) continue;
+        assert(nv < 32);
         v[nv].c = c, v[nv].j = 0, v[nv].s = s, nv++;
     }
     (void)featStatic; /* (:269-270 count the dynamic features and never use the count) */
@@ -915,6 +920,7 @@ static int check_unify_core(int nCams, int N, int nHist, const double* Ks, const
             const double* Mold = which ? M2 : M1;
             const double* hR = histR + (size_t)c * nHist * 9;
             const double* hT = histT + (size_t)c * nHist * 3;
+            assert(nv + 2 <= 128); /* this view and its second */
             v[nv].c = c, v[nv].j = j0, slotv[nv] = s, nv++;
             double C0[3];
             cam_center(hR + 9 * (size_t)j0, hT + 3 * (size_t)j0, C0);

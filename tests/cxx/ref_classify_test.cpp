@@ -13,6 +13,8 @@
 // and certain static ones that are not looked at.
 //   ref_classify_test golden <out.bin>
 //   ref_classify_test golden_relink <out.bin>
+//   ref_classify_test golden_wide <out.bin>
+//   ref_classify_test golden_wide_relink <out.bin>
 // golden_relink: the features as the registration loops and lost tracks leave MapPoint::pFeatures over time (src/app/SL_CoSLAM.cpp:775-779,
 // :997-1000: `pFeat->preFrame = p->pFeatures[iCam]`): per point and camera 1-3 segments of consecutive frames, newest first, gaps in
 // between, the newest at the current frame or a few frames back (a stale head; also in the camera whose view is off, so that the view
@@ -22,7 +24,16 @@
 // and history entry (newest first) R[9], t[3]; per point: M[3], cov[9], int32 localType, uncertain, newPt, staticFrameNum,
 // firstFrame, per camera int32 L (0 = no feature), int32 back (the feature's frame = curFrame - back), int32 featDynamic,
 // L x m[2] (newest first); then per point what the reference left: M[3], cov[9], int32 localType, uncertain, newPt, staticFrameNum,
-// per camera int32 hasFeature, int32 featDynamic.   TEST INFRASTRUCTURE; built into oracle/_ref/ where the reference tree exists.
+// per camera int32 hasFeature, int32 featDynamic.
+// golden_wide / golden_wide_relink: the same recipes and file layout at the camera counts the device lays its lanes out differently
+// for -- 8, 9 and 13 cameras (relink: 8 and 13; the reference holds SLAM_MAX_NUM = 13), own RNG seeds, 48 points.  The per-camera
+// offset and yaw are scaled by 4 / (nCams - 1) (the rig spans what the 5-camera rig spans; every feature is asserted to lie in front of
+// its camera), every fourth point (p % 4 == 1: kinds 1, 5, 9) has a feature in every camera, and in the second scene every third camera
+// stands still for the older half of its history with bit-identical poses (equal angles: the first in the backward walk wins).  The wide
+// modes return non-zero unless every outcome was reached 3 times and half of the chains are longer than 8 nodes.
+// TEST INFRASTRUCTURE; built into oracle/_ref/ where the reference tree exists.
+#undef NDEBUG
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -58,20 +69,26 @@ template <class T> static void put(FILE* f, const T* p, size_t n) { fwrite(p, si
 static void puti(FILE* f, int v) { fwrite(&v, 4, 1, f); }
 
 int main(int argc, char** argv) {
-    if (argc < 3 || (strcmp(argv[1], "golden") && strcmp(argv[1], "golden_relink"))) {
-        fprintf(stderr, "usage: %s golden|golden_relink <out.bin>\n", argv[0]);
+    if (argc < 3 || (strcmp(argv[1], "golden") && strcmp(argv[1], "golden_relink") && strcmp(argv[1], "golden_wide") && strcmp(argv[1], "golden_wide_relink"))) {
+        fprintf(stderr, "usage: %s golden|golden_relink|golden_wide|golden_wide_relink <out.bin>\n", argv[0]);
         return 2;
     }
-    const bool relink = !strcmp(argv[1], "golden_relink");
+    const bool relink = !strcmp(argv[1], "golden_relink") || !strcmp(argv[1], "golden_wide_relink");
+    const bool wide = !strncmp(argv[1], "golden_wide", 11);
     if (relink) g_rng = 0xD1B54A32D192ED03ull;
+    if (wide) g_rng = relink ? 0x8EBC6AF09C88C6E3ull : 0x589965CC75374CC3ull;
+    static const int wideCams[3] = {8, 9, 13}, wideRelinkCams[2] = {8, 13};
+    int nNonEmpty = 0, nLong = 0, nFullPts = 0;   // chains with a node | longer than 8 nodes; points with a feature in every camera
     int nChains = 0, nStale = 0, nLinked = 0, nStaleOff = 0;
     FILE* f = fopen(argv[2], "wb");
     if (!f) return 1;
-    const int nScenes = 3;
+    const int nScenes = (wide && relink) ? 2 : 3;
     puti(f, nScenes);
     int outcome[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // 0 untouched certain, 1 -> static, 2 -> dynamic, 3 -> false, 4 stays uncertain, 5 detached, 6 counter++, 7 back to static
     for (int sc = 0; sc < nScenes; ++sc) {
-        const int nCams = 3 + sc % 3, H = relink ? 70 : 64, nPts = 72, curFrame = 300 + 7 * sc;
+        const int nCams = wide ? (relink ? wideRelinkCams[sc] : wideCams[sc]) : 3 + sc % 3;
+        const int H = relink ? 70 : 64, nPts = wide ? 48 : 72, curFrame = 300 + 7 * sc;
+        const double rig = wide ? 4.0 / (nCams - 1) : 1.0;   // the wide rigs span what the 5-camera rig spans
         const double pixelVar = 12.0;  // CoSLAM::poseUpdate: mapPointsClassify(12.0) (src/app/SL_CoSLAM.cpp:385)
         CoSLAM* co = new CoSLAM();
         co->numCams = nCams;
@@ -89,11 +106,14 @@ int main(int argc, char** argv) {
         std::vector<std::vector<CamPoseItem*> > cams(nCams, std::vector<CamPoseItem*>(H));
         for (int c = 0; c < nCams; ++c)
             for (int j = 0; j < H; ++j) {  // j = 0: the current frame
-                double w[3] = {0.01 * c + 0.001 * nrand(), 0.10 * c - 0.0015 * j, 0.0005 * j}, R[9];
+                const double cs = wide ? c * rig : c;
+                double w[3] = {0.01 * cs + 0.001 * nrand(), 0.10 * cs - 0.0015 * j, 0.0005 * j}, R[9];
                 rodrigues(w, R);
-                const double pos[3] = {1.6 * c - 0.035 * j + 0.002 * nrand(), 0.05 * c + 0.004 * j, -0.01 * j};
+                const double pos[3] = {1.6 * cs - 0.035 * j + 0.002 * nrand(), 0.05 * cs + 0.004 * j, -0.01 * j};
                 double t[3];
                 for (int r = 0; r < 3; ++r) t[r] = -(R[3 * r] * pos[0] + R[3 * r + 1] * pos[1] + R[3 * r + 2] * pos[2]);
+                // (wide, second scene) every third camera stood still for the older half of its history: bit-identical poses
+                if (wide && sc == 1 && c % 3 == 1 && j > H / 2) memcpy(R, cams[c][H / 2]->R, 72), memcpy(t, cams[c][H / 2]->t, 24);
                 cams[c][j] = new CamPoseItem();
                 cams[c][j]->f = curFrame - j, cams[c][j]->camId = c;
                 memcpy(cams[c][j]->R, R, 72), memcpy(cams[c][j]->t, t, 24);
@@ -106,7 +126,8 @@ int main(int argc, char** argv) {
             // 5 uncertain old moving | 6 uncertain old, one camera off | 7 uncertain old garbage | 8 dynamic moving | 9 dynamic still, counter low
             // 10 dynamic still, counter at 50 | 11 one camera only (uncertain)
             const bool moving = kind == 3 || kind == 5 || kind == 8;
-            const bool garbage = kind == 4 || kind == 7;
+            // (wide: every other dynamic moving point has garbage pixels too -- dynamic -> false, which the 3-5 camera scenes reach by chance)
+            const bool garbage = kind == 4 || kind == 7 || (wide && p % 24 == 20);
             const double X0[3] = {-1.5 + 6 * urand(), -1.5 + 3 * urand(), 8 + 5 * urand()};
             const double vel[3] = {moving ? 0.05 * (urand() < 0.5 ? -1 : 1) : 0, moving ? 0.02 * nrand() : 0, moving ? 0.02 * nrand() : 0};
             MapPoint* mp = new MapPoint(X0[0] + 0.03 * nrand(), X0[1] + 0.03 * nrand(), X0[2] + 0.06 * nrand(), curFrame - 45);
@@ -128,6 +149,7 @@ int main(int argc, char** argv) {
             for (int c = 0; c < nCams; ++c) {
                 // which cameras see the point: kind 11 one camera; kind 6 all (the removable test needs more than two); else most
                 bool has = kind == 11 ? (c == p % nCams) : (kind == 6 ? true : (urand() < 0.85 || c < 2));
+                if (wide && p % 4 == 1) has = true;   // every fourth point: a feature in every camera
                 int back = (has && kind != 11 && c >= 2 && urand() < 0.2) ? 1 + (int)(urand() * 8) : 0;   // a camera that lost the point
                 if (relink && has && kind == 6 && c == offCam && c >= 2 && urand() < 0.5) back = 1 + (int)(urand() * 8);
                 int L = has ? 2 + (int)(urand() * (H - 2 - back)) : 0;
@@ -164,6 +186,7 @@ int main(int argc, char** argv) {
                         const double X[3] = {X0[0] - vel[0] * j, X0[1] - vel[1] * j, X0[2] - vel[2] * j};
                         double Xc[3], m[2];
                         for (int r = 0; r < 3; ++r) Xc[r] = R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2] + t[r];
+                        assert(!wide || Xc[2] > 0);
                         m[0] = (K[0] * Xc[0] + K[1] * Xc[1] + K[2] * Xc[2]) / Xc[2] + 0.4 * nrand();
                         m[1] = (K[4] * Xc[1] + K[5] * Xc[2]) / Xc[2] + 0.4 * nrand();
                         if (garbage) m[0] += 60 * nrand(), m[1] += 60 * nrand();
@@ -181,7 +204,13 @@ int main(int argc, char** argv) {
                     }
                 }
                 if (L > 0 && back == 0) ++nCur;
+                int nodes = 0;
+                for (size_t sg = 0; sg < segs.size(); ++sg) nodes += segs[sg].second;
+                nNonEmpty += nodes > 0, nLong += nodes > 8;
             }
+            int seenBy = 0;
+            for (int c = 0; c < nCams; ++c) seenBy += mp->pFeatures[c] != nullptr;
+            nFullPts += seenBy == nCams;
             mp->numVisCam = nCur;   // MapPoint::updateVisCamNum(curFrame), as mapStateUpdate leaves it (:1183)
             pts[p] = mp;
             if (nCur > 0) co->curMapPts.add(mp);   // (a point no camera sees in this frame has left the current list)
@@ -210,7 +239,9 @@ int main(int argc, char** argv) {
     if (relink) printf("ref_classify_test golden_relink: %d chains, %d with a stale head (%d of them the view that is off), %d with linked segments\n", nChains, nStale, nStaleOff, nLinked);
     printf("ref_classify_test: certain %d, -> static %d, -> dynamic %d, -> false %d, still uncertain %d, view detached %d, dynamic kept %d, back to static %d\n",
            outcome[0], outcome[1], outcome[2], outcome[3], outcome[4], outcome[5], outcome[6], outcome[7]);
+    if (wide) printf("  wide: %d points with a feature in every camera, %d non-empty chains, %d longer than 8 nodes\n", nFullPts, nNonEmpty, nLong);
+    if (wide && 2 * nLong < nNonEmpty) return 1;
     for (int q = 0; q < 8; ++q)
-        if (outcome[q] < 5) return 1;   // every branch must have been walked
+        if (outcome[q] < (wide ? 3 : 5)) return 1;   // every branch must have been walked
     return 0;
 }

@@ -11,6 +11,8 @@
 // part of the history (equal angles: the first in the backward walk wins), cameras that only rotate (angle 0: no second view).
 //   ref_update_points_test golden <out.bin>
 //   ref_update_points_test golden_relink <out.bin>
+//   ref_update_points_test golden_wide <out.bin>
+//   ref_update_points_test golden_wide_relink <out.bin>
 // golden_relink: chains as the registration loops leave them (src/app/SL_CoSLAM.cpp:775-779, :997-1000: `pFeat->preFrame =
 // p->pFeatures[iCam]` hangs the point's OLD chain behind the feature of a new track, whose own earlier frames drop out) and as a lost
 // track leaves them (nothing clears MapPoint::pFeatures[c]: the feature of an OLDER frame stays, and every loop here takes it as a
@@ -23,7 +25,18 @@
 // refined, and CoSLAM::refineMapPoint's M[3], cov[9] for a copy of the point as it stood before (refined = 0: not called, unchanged);
 // then int32 nPairs and per pair of temporary points handed to CoSLAM::checkUnify: int32 p1, p2, per camera int32 has1, has2, M1[3],
 // M2[3], int32 ok, M[3], cov[9].
+// golden_wide / golden_wide_relink: the same recipes and file layout at the camera counts the device lays its lanes out differently
+// for (the reference holds SLAM_MAX_NUM = 13 cameras; its local arrays take all 4 * 13 views of a checkUnify pair), own RNG seeds,
+// 48 points.  golden_wide: 7 cameras moving, 8 and 9 standing still for the older half, 12 rotation only, 13 moving, 16 frames of
+// history; golden_wide_relink: 8 cameras moving and 13 standing still for the older half, 40 / 70 frames.  The per-camera offset and yaw are scaled by 4 / (nCams - 1) (the rig
+// spans what the 5-camera rig spans; every feature is asserted to lie in front of its camera), every fourth point has a feature in
+// every camera, longer chains are likelier, and checkUnify also gets pairs of two different fully seen points (4 * nCams candidate
+// views).  The wide modes return non-zero unless: checkUnify says yes for a quarter of the pairs and no for a quarter, half of the
+// non-empty chains are longer than 8 nodes, every scene has 6 pairs of two fully seen points and 6 of the halves of one, and in each
+// stand-still scene 10 points take the FIRST node of the repeated pose as a second view.
 // TEST INFRASTRUCTURE; built into oracle/_ref/ where the reference tree exists.
+#undef NDEBUG
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -60,21 +73,29 @@ template <class T> static void put(FILE* f, const T* p, size_t n) { fwrite(p, si
 static void puti(FILE* f, int v) { fwrite(&v, 4, 1, f); }
 
 int main(int argc, char** argv) {
-    if (argc < 3 || (strcmp(argv[1], "golden") && strcmp(argv[1], "golden_relink"))) {
-        fprintf(stderr, "usage: %s golden|golden_relink <out.bin>\n", argv[0]);
+    if (argc < 3 || (strcmp(argv[1], "golden") && strcmp(argv[1], "golden_relink") && strcmp(argv[1], "golden_wide") && strcmp(argv[1], "golden_wide_relink"))) {
+        fprintf(stderr, "usage: %s golden|golden_relink|golden_wide|golden_wide_relink <out.bin>\n", argv[0]);
         return 2;
     }
-    const bool relink = !strcmp(argv[1], "golden_relink");
+    const bool relink = !strcmp(argv[1], "golden_relink") || !strcmp(argv[1], "golden_wide_relink");
+    const bool wide = !strncmp(argv[1], "golden_wide", 11);
+    if (wide) g_rng = relink ? 0xA0761D6478BD642Full : 0xE7037ED1A0B428DBull;
+    static const int wideCams[5] = {7, 8, 9, 12, 13}, wideMotion[5] = {0, 1, 1, 2, 0}, wideRelinkCams[2] = {8, 13};
     int nStale = 0, nLinked = 0, nChains = 0;
+    int nNonEmpty = 0, nLong = 0, nFullPts = 0;   // chains with a node | longer than 8 nodes; points with a feature in every camera
+    bool scenesOk = true;                         // the per-scene conditions of the wide modes
     FILE* f = fopen(argv[2], "wb");
     if (!f) return 1;
-    const int nScenes = relink ? 4 : 6;
+    const int nScenes = wide ? (relink ? 2 : 5) : (relink ? 4 : 6);
     puti(f, nScenes);
     int nTouched = 0, nTotal = 0, nMoved2 = 0, nRefined = 0, nUnify = 0, nUnifyAll = 0;
     for (int sc = 0; sc < nScenes; ++sc) {
-        const int nCams = 2 + sc % 4, H = relink ? 40 + 30 * (sc % 2) : 6 + 5 * (sc % 3), nPts = 60, curFrame = 200 + sc, firstKey = curFrame - 12;
+        const int nCams = wide ? (relink ? wideRelinkCams[sc] : wideCams[sc]) : 2 + sc % 4;
+        const int H = relink ? 40 + 30 * (sc % 2) : (wide ? 16 : 6 + 5 * (sc % 3)), nPts = wide ? 48 : 60, curFrame = 200 + sc, firstKey = curFrame - 12;
         // kind of motion: 0 moving rig, 1 stands still for the older half of the history, 2 rotation only
-        const int motion = sc == 3 ? 1 : (sc == 4 ? 2 : 0);
+        const int motion = wide ? (relink ? sc % 2 : wideMotion[sc]) : (sc == 3 ? 1 : (sc == 4 ? 2 : 0));
+        const double rig = wide ? 4.0 / (nCams - 1) : 1.0;   // the wide rigs span what the 5-camera rig spans
+        int nStandFirst = 0, nPairFull = 0, nPairHalves = 0;
         CoSLAM* co = new CoSLAM();
         co->numCams = nCams;
         const double sigma = Const::PIXEL_ERR_VAR;
@@ -92,11 +113,12 @@ int main(int argc, char** argv) {
         for (int c = 0; c < nCams; ++c)
             for (int j = 0; j < H; ++j) {   // j = 0: the newest frame
                 const int jj = (motion == 1 && j >= H / 2) ? H / 2 : j;   // the older half repeats one pose
-                double w[3] = {0.01 * c, 0.12 * c - 0.006 * jj, 0.002 * jj}, R[9];
+                const double cs = wide ? c * rig : c;
+                double w[3] = {0.01 * cs, 0.12 * cs - 0.006 * jj, 0.002 * jj}, R[9];
                 if (motion != 1) w[0] += 0.002 * nrand(), w[2] += 0.002 * nrand();
                 rodrigues(w, R);
-                double pos[3] = {1.5 * c - 0.09 * jj, 0.05 * c + 0.01 * jj, -0.03 * jj};
-                if (motion == 2) pos[0] = 1.5 * c, pos[1] = 0.05 * c, pos[2] = 0;
+                double pos[3] = {1.5 * cs - 0.09 * jj, 0.05 * cs + 0.01 * jj, -0.03 * jj};
+                if (motion == 2) pos[0] = 1.5 * cs, pos[1] = 0.05 * cs, pos[2] = 0;
                 if (motion == 0) pos[0] += 0.004 * nrand(), pos[1] += 0.004 * nrand(), pos[2] += 0.004 * nrand();
                 double t[3];
                 for (int r = 0; r < 3; ++r) t[r] = -(R[3 * r] * pos[0] + R[3 * r + 1] * pos[1] + R[3 * r + 2] * pos[2]);
@@ -126,19 +148,24 @@ int main(int argc, char** argv) {
             puti(f, mp->iLocalType), puti(f, mp->bUncertain ? 1 : 0), puti(f, mp->lastFrame), puti(f, isCur);
             for (int c = 0; c < nCams && relink; ++c) {
                 const double u2 = urand();
-                const int want = u2 < 0.2 ? 0 : (u2 < 0.4 ? 1 : (u2 < 0.8 ? 2 : 3));
+                int want = u2 < 0.2 ? 0 : (u2 < 0.4 ? 1 : (u2 < 0.8 ? 2 : 3));
+                if (wide && p % 4 == 0 && want == 0) want = 2;   // every fourth point: a feature in every camera
                 const int dyn = urand() < 0.35;
                 int j = (want > 0 && urand() < 0.3) ? 1 + (int)(urand() * 6) : 0;   // a stale head: the camera lost the point j frames ago
                 std::vector<std::pair<int, int> > segs;   // (newest entry, nodes)
                 for (int q = 0; q < want && j < H; ++q) {
                     int L = 1 + (int)(urand() * (q == 0 && want > 1 ? 10 : 25));   // (a freshly re-linked head is 1 node long)
                     if (q == 0 && want > 1 && urand() < 0.3) L = 1;
+                    if (wide && p % 4 == 0 && q == 0 && L < 2) L = 2;   // (a fully seen point: a node behind every feature)
                     if (j + L > H) L = H - j;
                     segs.push_back(std::make_pair(j, L));
                     j += L + 1 + (int)(urand() * 12);   // the frames in which the camera did not see the point
                 }
                 puti(f, (int)segs.size()), puti(f, dyn);
                 if (!segs.empty()) ++nChains, nStale += segs[0].first > 0, nLinked += segs.size() > 1;
+                int nodes = 0;
+                for (size_t q = 0; q < segs.size(); ++q) nodes += segs[q].second;
+                nNonEmpty += nodes > 0, nLong += nodes > 8;
                 FeaturePoint* newer = nullptr;
                 for (size_t q = 0; q < segs.size(); ++q) {
                     puti(f, segs[q].first), puti(f, segs[q].second);
@@ -148,6 +175,7 @@ int main(int argc, char** argv) {
                         const double* K = Ks[c].data();
                         double Xc[3], m[2];
                         for (int r = 0; r < 3; ++r) Xc[r] = R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2] + t[r];
+                        assert(!wide || Xc[2] > 0);
                         m[0] = (K[0] * Xc[0] + K[1] * Xc[1] + K[2] * Xc[2]) / Xc[2] + 0.6 * nrand();
                         m[1] = (K[4] * Xc[1] + K[5] * Xc[2]) / Xc[2] + 0.6 * nrand();
                         put(f, m, 2);
@@ -164,9 +192,12 @@ int main(int argc, char** argv) {
                 }
             }
             for (int c = 0; c < nCams && !relink; ++c) {
-                const int L = (urand() < 0.3) ? 0 : 1 + (int)(urand() * H);
+                int L = (urand() < 0.3) ? 0 : 1 + (int)(urand() * H);
+                if (wide && L > 0 && urand() < 0.4) L = 9 + (int)(urand() * (H - 8));   // longer chains are likelier
+                if (wide && p % 4 == 0 && L < 2) L = 2 + (int)(urand() * (H - 1));       // every fourth point: a feature (and a track) in every camera
                 const int dyn = urand() < 0.35;
                 puti(f, L), puti(f, dyn);
+                nNonEmpty += L > 0, nLong += L > 8;
                 FeaturePoint* newer = nullptr;
                 for (int j = 0; j < L; ++j) {
                     const double* R = cams[c][j]->R;
@@ -174,6 +205,7 @@ int main(int argc, char** argv) {
                     const double* K = Ks[c].data();
                     double Xc[3], m[2];
                     for (int r = 0; r < 3; ++r) Xc[r] = R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2] + t[r];
+                    assert(!wide || Xc[2] > 0);
                     m[0] = (K[0] * Xc[0] + K[1] * Xc[1] + K[2] * Xc[2]) / Xc[2] + 0.6 * nrand();
                     m[1] = (K[4] * Xc[1] + K[5] * Xc[2]) / Xc[2] + 0.6 * nrand();
                     put(f, m, 2);
@@ -189,6 +221,29 @@ int main(int argc, char** argv) {
                 }
             }
             pts[p] = mp;
+            int seenBy = 0;
+            for (int c = 0; c < nCams; ++c) seenBy += mp->pFeatures[c] != nullptr;
+            nFullPts += seenBy == nCams;
+            // a rig that stood still: does some camera's backward walk meet its widest angle FIRST at the first node of the repeated
+            // pose, with equal angles behind it?  (the walk of updateStaticPointPosition, angles by cosine: identical poses, identical values)
+            bool standFirst = false;
+            for (int c = 0; c < nCams && motion == 1; ++c) {
+                const FeaturePoint* fp = mp->pFeatures[c];
+                if (!fp) continue;
+                double C0[3], best = 0;
+                int bestJ = -1, nodes = 1;
+                for (int r = 0; r < 3; ++r) C0[r] = -(fp->cam->R[r] * fp->cam->t[0] + fp->cam->R[3 + r] * fp->cam->t[1] + fp->cam->R[6 + r] * fp->cam->t[2]);
+                for (fp = fp->preFrame; fp; fp = fp->preFrame, ++nodes) {
+                    double C[3], a[3], b[3];
+                    for (int r = 0; r < 3; ++r) C[r] = -(fp->cam->R[r] * fp->cam->t[0] + fp->cam->R[3 + r] * fp->cam->t[1] + fp->cam->R[6 + r] * fp->cam->t[2]);
+                    for (int r = 0; r < 3; ++r) a[r] = C0[r] - mp->M[r], b[r] = C[r] - mp->M[r];
+                    const double dot = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+                    const double ang = acos(dot / sqrt((a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) * (b[0] * b[0] + b[1] * b[1] + b[2] * b[2])));
+                    if (ang > best) best = ang, bestJ = curFrame - fp->f;
+                }
+                if (bestJ == H / 2 && nodes > H / 2 + 1) standFirst = true;
+            }
+            nStandFirst += standFirst;
             if (isCur) co->curMapPts.add(mp); else co->actMapPts.add(mp);
         }
         // CoSLAM::refineMapPoint (src/app/SL_CoSLAM.cpp:666-713: what the registration loops call on a point that just gained a feature,
@@ -222,12 +277,19 @@ int main(int argc, char** argv) {
         for (int p = 0; p + 1 < nPts; ++p) {
             int seen = 0;
             for (int c = 0; c < nCams; ++c) seen += pts[p]->pFeatures[c] != nullptr;
-            for (int mode = 0; mode < 2; ++mode) {
+            for (int mode = 0; mode < (wide ? 3 : 2); ++mode) {
                 if (mode == 0 && seen < 2) continue;
-                MapPoint A(*pts[p]), B(mode == 0 ? *pts[p] : *pts[p + 1]);
+                int other = mode == 0 ? p : p + 1;
+                if (mode == 2) {   // (wide) two different points that every camera sees: 4 * nCams candidate views
+                    int seen4 = 0;
+                    for (int c = 0; c < nCams && p + 4 < nPts; ++c) seen4 += pts[p + 4]->pFeatures[c] != nullptr;
+                    if (seen != nCams || seen4 != nCams) continue;
+                    other = p + 4;
+                }
+                MapPoint A(*pts[p]), B(*pts[other]);
                 UnifyRec r;
                 memset(&r, 0, sizeof(r));
-                r.p1 = p, r.p2 = mode == 0 ? p : p + 1;
+                r.p1 = p, r.p2 = other;
                 if (mode == 0) {   // the cameras that see the point dealt out alternately
                     int k = 0;
                     for (int c = 0; c < nCams; ++c)
@@ -248,6 +310,7 @@ int main(int argc, char** argv) {
                 for (int q = 0; q < 3; ++q) fin = fin && fabs(r.M[q]) < 1e6;
                 if (!fin) continue;   // (a degenerate union -- rotation-only rig -- is not a test vector)
                 uni.push_back(r);
+                nPairFull += mode != 0 && nA == nCams && nB == nCams, nPairHalves += mode == 0 && seen == nCams;
                 nUnify += r.ok, ++nUnifyAll;
             }
         }
@@ -274,10 +337,22 @@ int main(int argc, char** argv) {
             puti(f, r.ok), put(f, r.M, 3), put(f, r.cov, 9);
         }
         co->curMapPts.clearWithoutRelease(), co->actMapPts.clearWithoutRelease();
+        if (wide) {
+            printf("  scene %d: %d cameras, motion %d: %d pairs of two fully seen points, %d of the halves of one", sc, nCams, motion, nPairFull, nPairHalves);
+            if (motion == 1) printf(", %d points take the first node of the repeated pose", nStandFirst);
+            printf("\n");
+            // (the rotation-only rig has no parallax: its unions are degenerate and are not test vectors)
+            scenesOk = scenesOk && (motion == 2 || (nPairFull >= 6 && nPairHalves >= 6)) && (motion != 1 || nStandFirst >= 10);
+        }
     }
     fclose(f);
     printf("ref_update_points_test: %d scenes, %d of %d points re-triangulated, %d wild coordinates; refineMapPoint on %d points; checkUnify: %d of %d pairs unify\n",
            nScenes, nTouched, nTotal, nMoved2, nRefined, nUnify, nUnifyAll);
+    if (wide) {
+        printf("  wide: %d points with a feature in every camera, %d non-empty chains, %d longer than 8 nodes\n", nFullPts, nNonEmpty, nLong);
+        if (relink) printf("  chains: %d, with a stale head %d, with an older segment linked behind %d\n", nChains, nStale, nLinked);
+        return (scenesOk && nMoved2 == 0 && 4 * nUnify >= nUnifyAll && 4 * (nUnifyAll - nUnify) >= nUnifyAll && 2 * nLong >= nNonEmpty) ? 0 : 1;
+    }
     if (relink) {
         printf("  chains: %d, with a stale head %d, with an older segment linked behind %d\n", nChains, nStale, nLinked);
         return (nTouched > nTotal / 5 && nMoved2 == 0 && nRefined > nTotal / 5 && nStale > 40 && nLinked > 100 && nUnify > 10) ? 0 : 1;

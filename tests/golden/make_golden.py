@@ -647,10 +647,11 @@ def mergability_long_case():
     return dict(sigma=np.float64(sigma), K=K, R=R, t=t, M=M, cov=cov, f1=f1, bad_frame=bad, verdict=verdict, xy=xy.astype(np.float64))
 
 
-def update_points_case():
+def update_points_case(mode="golden"):
     """the reference's own RobustBundleRTS::updateNewPosesPoints over updateStaticPointPosition / updateDynamicPointPosition
     (oracle/_ref/ref_update_points_test golden, CPU): 6 scenes of 60 map points, re-laid out the way the device holds them (slot =
-    point index, ring entry 0 = the current frame), and the reference's points / covariances afterwards."""
+    point index, ring entry 0 = the current frame), and the reference's points / covariances afterwards.  mode="golden_wide": the
+    driver's 7 / 8 / 9 / 12 / 13-camera scenes of 48 points, same layout."""
     import struct
     import subprocess
     import tempfile
@@ -660,7 +661,7 @@ def update_points_case():
         raise SystemExit("oracle/_ref/ref_update_points_test missing: run `make -C oracle` where /root/reference exists")
     with tempfile.TemporaryDirectory() as td:
         path = os.path.join(td, "u.bin")
-        subprocess.run([exe, "golden", path], check=True, stdout=subprocess.DEVNULL)
+        subprocess.run([exe, mode, path], check=True, stdout=subprocess.DEVNULL)
         raw = open(path, "rb").read()
     o = 0
 
@@ -740,11 +741,12 @@ def update_points_case():
     return out
 
 
-def update_points_relink_case():
+def update_points_relink_case(mode="golden_relink"):
     """re-linked and stale feature chains (oracle/_ref/ref_update_points_test golden_relink, CPU): the reference's own
     updateNewPosesPoints / refineMapPoint / checkUnify over chains as `pFeat->preFrame = p->pFeatures[iCam]` (SL_CoSLAM.cpp:775-779) and a
     lost track leave them, re-laid out the way the device holds them: every segment of consecutive frames on a slot of its own (slot =
-    running number per camera), featRef [nP][nC][4] = {slot, frame, first, seg}, segPool [nC][cap][4] = {slot, last, first, next}."""
+    running number per camera), featRef [nP][nC][4] = {slot, frame, first, seg}, segPool [nC][cap][4] = {slot, last, first, next}.
+    mode="golden_wide_relink": the driver's 8 / 13-camera scenes of 48 points, same layout."""
     import subprocess
     import tempfile
 
@@ -753,7 +755,7 @@ def update_points_relink_case():
         raise SystemExit("oracle/_ref/ref_update_points_test missing: run `make -C oracle` where /root/reference exists")
     with tempfile.TemporaryDirectory() as td:
         path = os.path.join(td, "u.bin")
-        subprocess.run([exe, "golden_relink", path], check=True, stdout=subprocess.DEVNULL)
+        subprocess.run([exe, mode, path], check=True, stdout=subprocess.DEVNULL)
         raw = open(path, "rb").read()
     o = 0
 
@@ -967,10 +969,11 @@ def intracam_newpts_case():
     return out
 
 
-def classify_case():
+def classify_case(mode="golden"):
     """the reference's own CoSLAM::mapPointsClassify over isStaticPoint / isStaticPointExclude / isDynamicPoint / isLittleMove /
     isStaticRemovable (oracle/_ref/ref_classify_test golden, CPU): 3 scenes of 72 map points walking every branch, re-laid out the
-    way the device holds them (slot = point index, ring entry 0 = the current frame), and the points' states afterwards."""
+    way the device holds them (slot = point index, ring entry 0 = the current frame), and the points' states afterwards.
+    mode="golden_wide": the driver's 8 / 9 / 13-camera scenes of 48 points, same layout."""
     import subprocess
     import tempfile
 
@@ -979,7 +982,7 @@ def classify_case():
         raise SystemExit("oracle/_ref/ref_classify_test missing: run `make -C oracle` where /root/reference exists")
     with tempfile.TemporaryDirectory() as td:
         path = os.path.join(td, "c.bin")
-        subprocess.run([exe, "golden", path], check=True, stdout=subprocess.DEVNULL)
+        subprocess.run([exe, mode, path], check=True, stdout=subprocess.DEVNULL)
         raw = open(path, "rb").read()
     o = 0
 
@@ -1053,11 +1056,12 @@ def classify_case():
     return out
 
 
-def classify_relink_case():
+def classify_relink_case(mode="golden_relink"):
     """the reference's own mapPointsClassify over re-linked and stale feature chains (oracle/_ref/ref_classify_test golden_relink, CPU),
     re-laid out the way the device holds them: every segment of consecutive frames on a slot of its own (running number per camera),
     featRef [nP][nC][4] = {slot, frame, first, seg}, segPool [nC][cap][4] = {slot, last, first, next}; pointFeat names the heads that are
-    of this frame.  featDyn_ref [nP][nC]: the type the reference left on the feature each pointer names (live or stale)."""
+    of this frame.  featDyn_ref [nP][nC]: the type the reference left on the feature each pointer names (live or stale).
+    mode="golden_wide_relink": the driver's 8 / 13-camera scenes of 48 points, same layout."""
     import subprocess
     import tempfile
 
@@ -1066,7 +1070,7 @@ def classify_relink_case():
         raise SystemExit("oracle/_ref/ref_classify_test missing: run `make -C oracle` where /root/reference exists")
     with tempfile.TemporaryDirectory() as td:
         path = os.path.join(td, "c.bin")
-        subprocess.run([exe, "golden_relink", path], check=True, stdout=subprocess.DEVNULL)
+        subprocess.run([exe, mode, path], check=True, stdout=subprocess.DEVNULL)
         raw = open(path, "rb").read()
     o = 0
 
@@ -1262,7 +1266,7 @@ def cgklt_cases():
 if __name__ == "__main__":
     if not oracle.have_ref():
         raise SystemExit("oracle/_ref/libintracam_ref.so missing: run `make -C oracle` where /root/reference exists")
-    which = sys.argv[1:] or ["pose", "klt", "ba", "register", "ncc", "posegraph", "export", "mergability", "mergability_long", "update_points", "update_points_relink", "keyframe", "intracam_newpts", "classify", "classify_relink", "intercam", "decide_relink", "newpts", "decide", "cgklt"]
+    which = sys.argv[1:] or ["pose", "klt", "ba", "register", "ncc", "posegraph", "export", "mergability", "mergability_long", "update_points", "update_points_relink", "keyframe", "intracam_newpts", "classify", "classify_relink", "update_points_wide", "update_points_wide_relink", "classify_wide", "classify_wide_relink", "intercam", "decide_relink", "newpts", "decide", "cgklt"]
     if "pose" in which:
         np.savez_compressed(os.path.join(HERE, "pose_golden.npz"), **pose_cases())
     if "klt" in which:
@@ -1297,6 +1301,14 @@ if __name__ == "__main__":
         np.savez_compressed(os.path.join(HERE, "update_points_relink_golden.npz"), **update_points_relink_case())
     if "classify" in which:
         np.savez_compressed(os.path.join(HERE, "classify_golden.npz"), **classify_case())
+    if "update_points_wide" in which:
+        np.savez_compressed(os.path.join(HERE, "update_points_wide_golden.npz"), **update_points_case("golden_wide"))
+    if "update_points_wide_relink" in which:
+        np.savez_compressed(os.path.join(HERE, "update_points_wide_relink_golden.npz"), **update_points_relink_case("golden_wide_relink"))
+    if "classify_wide" in which:
+        np.savez_compressed(os.path.join(HERE, "classify_wide_golden.npz"), **classify_case("golden_wide"))
+    if "classify_wide_relink" in which:
+        np.savez_compressed(os.path.join(HERE, "classify_wide_relink_golden.npz"), **classify_relink_case("golden_wide_relink"))
     if "decide" in which:
         np.savez_compressed(os.path.join(HERE, "decide_golden.npz"), **decide_case())
     if "newpts" in which:
