@@ -35,7 +35,7 @@ class Config(C.Structure):
 def build(force=False):
     """make -C oracle (liboracle.so, and _ref/ when /root/reference exists)."""
     if force or not os.path.exists(LIB_PATH):
-        subprocess.check_call(["make", "-C", _HERE, "-s", "all"])
+        subprocess.check_call(["make", "-C", _HERE, "-s", "-j8", "all"])
     return LIB_PATH
 
 

@@ -16,7 +16,7 @@ void sparseSolveLin(const Triplets& T, const double* b, double* x) {
     const int m = T.m, n = T.n;
     std::vector<double> A((size_t)m * n, 0.0), rhs(b, b + m);
     for (size_t k = 0; k < T.val.size(); ++k) A[(size_t)T.ri[k] * n + T.ci[k]] += T.val[k];
-    std::vector<double> v(m);
+    std::vector<double> v(m), w(n);
     for (int j = 0; j < n; ++j) {  // Householder reflection that zeroes column j below the diagonal
         double nrm = 0;
         for (int i = j; i < m; ++i) nrm += A[(size_t)i * n + j] * A[(size_t)i * n + j];
@@ -28,12 +28,13 @@ void sparseSolveLin(const Triplets& T, const double* b, double* x) {
         double vtv = 0;
         for (int i = j; i < m; ++i) vtv += v[i] * v[i];
         if (vtv == 0) continue;
-        for (int c = j; c < n; ++c) {
-            double s = 0;
-            for (int i = j; i < m; ++i) s += v[i] * A[(size_t)i * n + c];
-            s = 2 * s / vtv;
-            for (int i = j; i < m; ++i) A[(size_t)i * n + c] -= s * v[i];
-        }
+        // row by row (A is row-major): per column the same sums in the same order as a column-by-column sweep, bit for bit
+        for (int c = j; c < n; ++c) w[c] = 0;
+        for (int i = j; i < m; ++i)
+            for (int c = j; c < n; ++c) w[c] += v[i] * A[(size_t)i * n + c];
+        for (int c = j; c < n; ++c) w[c] = 2 * w[c] / vtv;
+        for (int i = j; i < m; ++i)
+            for (int c = j; c < n; ++c) A[(size_t)i * n + c] -= w[c] * v[i];
         double s = 0;
         for (int i = j; i < m; ++i) s += v[i] * rhs[i];
         s = 2 * s / vtv;

@@ -15,11 +15,8 @@
 //          list (0 cur, 1 act, 2 iact); per camera int32 nSeg, per segment (newest first) int32 last, first, then (last - first + 1) x m[2]
 //          newest first.
 // out.bin: per scene: int32 nSelected; per point int32 selected, M[3], cov[9].
-// The one compile line (from oracle/, where the reference tree exists; oracle/Makefile:138-142 with the driver swapped -- the two objects
-// are those of :138-139, SL_CoSLAMHelper.cpp and SL_CoSLAM.cpp compiled in place with -DREF_SHIM_TRIANGULATE_ON_PATH):
-//   $(DROPIN_CXX) $(DROPIN_INC) ../tests/cxx/ref_mergeapply_test.cpp _ref/coslam_ref_tri.o _ref/coslam_helper_ref.o $(BA_SRCS) $(MODEL_SRCS) \
-//      ref_shim/ref_glue_impl.cpp ref_shim/shim_impl.cpp ref_shim/ref_posegraph_standin.cpp ref_shim/ref_coslam_standin.cpp \
-//      ref_shim/ref_triangulate_impl.cpp $(DROPIN_LD) -lpthread -o _ref/ref_mergeapply_test
+// Built by oracle/Makefile, target _ref/ref_mergeapply_test (where the reference tree exists): ref_update_points_test's link line with
+// the driver swapped -- SL_CoSLAMHelper.cpp and SL_CoSLAM.cpp compiled in place with -DREF_SHIM_TRIANGULATE_ON_PATH.
 // LibVisualSLAM's triangulation helpers are OUR definitions (ref_shim/ref_triangulate_impl.cpp): the vectors pin which rows are taken,
 // which views, and in which order.
 // TEST INFRASTRUCTURE; the binary goes to oracle/_ref/ (untracked), nothing on the GPU side needs it.

@@ -18,18 +18,8 @@
 // Un-vendored on the path and OUR definitions: sortWithInd (stable, descending), matEyes, matZeros, and -- already in oracle/ref_shim --
 // project, dist2 (the Euclidean distance of two pixels), getRigidTransFromTo, formEMat.
 //   ref_mergeconstraints_test golden <in.bin> <out.bin>          CPU only
-// The compile lines (from oracle/, where the reference tree exists; DROPIN_CXX / DROPIN_INC / DROPIN_LD / SRC / MODEL_SRCS as in
-// oracle/Makefile).  Three expressions of functions OFF the path (:142 an image constructed with its size, :158 a pointer compared with > 0, :1238 a
-// measurement read as an array) do not compile against the stand-ins and are rewritten in the pipe by line number, as the Makefile does
-// for SL_CoSLAM.cpp; no copy of the source is written anywhere:
-//   sed -e '158s/> 0/!= 0/' -e '142s/mask(\(.*\));/mask; mask.resize(\1);/' -e '1238s/, \([a-z0-9]*\[i\]\[j\]\)\.m)/, \&\1.x)/' \
-//       $(SRC)/app/SL_MergeCameraGroup.cpp | \
-//     $(DROPIN_CXX) -I../tests/cxx/ref_shim_merge $(DROPIN_INC) -DCOSLAMTHREAD_H_ -include ../tests/cxx/ref_shim_merge/ref_merge_offpath.h \
-//       -x c++ -c - -o _ref/mergecamgroup_ref.o
-//   $(DROPIN_CXX) -I../tests/cxx/ref_shim_merge $(DROPIN_INC) -DCOSLAMTHREAD_H_ -include ../tests/cxx/ref_shim_merge/ref_merge_offpath.h \
-//       ../tests/cxx/ref_mergeconstraints_test.cpp _ref/mergecamgroup_ref.o $(MODEL_SRCS) $(SRC)/slam/SL_KeyPoseList.cpp \
-//       $(SRC)/slam/SL_MapPointList.cpp ref_shim/ref_glue_impl.cpp ref_shim/shim_impl.cpp ref_shim/ref_posegraph_standin.cpp \
-//       $(DROPIN_LD) -lpthread -o _ref/ref_mergeconstraints_test && rm -f _ref/mergecamgroup_ref.o
+// Built by oracle/Makefile, target _ref/ref_mergeconstraints_test (where the reference tree exists; the Makefile's header lists the
+// three expressions of SL_MergeCameraGroup.cpp that are rewritten in the compile pipe).
 // TEST INFRASTRUCTURE; the binary goes to oracle/_ref/ (untracked), nothing on the GPU side needs it.
 #include <cstdio>
 #include <cstdlib>

@@ -17,9 +17,7 @@
 // the well-defined id2-fixed branch) and writes the graph with the edge as given.
 //   ref_mergegraph_test golden <out.bin>    CPU only.  tests/golden/make_mergegraph_golden.py turns the file into
 //                                            tests/golden/mergegraph_golden.npz.
-// The one compile line (from oracle/, where the reference tree exists; oracle/Makefile:122-123 with the driver swapped):
-//   $(DROPIN_CXX) $(DROPIN_INC) ../tests/cxx/ref_mergegraph_test.cpp $(SRC)/slam/SL_GlobalPoseEstimation.cpp \
-//      ref_shim/ref_posegraph_impl.cpp ref_shim/ref_glue_impl.cpp ref_shim/shim_impl.cpp $(DROPIN_LD) -o _ref/ref_mergegraph_test
+// Built by oracle/Makefile, target _ref/ref_mergegraph_test (where the reference tree exists).
 // Sparse QR, the polar factor and mat33* are un-vendored LibVisualSLAM: the stand-ins of ref_shim/ref_posegraph_impl.cpp.
 // TEST INFRASTRUCTURE; the binary goes to oracle/_ref/ (untracked), nothing on the GPU side needs it.
 #include <cmath>

@@ -11,17 +11,8 @@
 // entry the loop would match, so that the matches of EVERY job are recorded (the loop keeps them in a local array), and forms F with the
 // functions matchFeaturePointsNCC forms it with (F is a local there).
 //   ref_mergematch_test golden <in.bin> <out.bin>          CPU only
-// The compile lines (from oracle/, where the reference tree exists; DROPIN_CXX / DROPIN_INC / DROPIN_LD / SRC / MODEL_SRCS as in
-// oracle/Makefile; the first three rewrites are ref_mergeconstraints_test.cpp's, the fourth redirects :416; no copy of the source is written):
-//   sed -e '158s/> 0/!= 0/' -e '142s/mask(\(.*\));/mask; mask.resize(\1);/' -e '1238s/, \([a-z0-9]*\[i\]\[j\]\)\.m)/, \&\1.x)/' \
-//       -e '416s/genMergeInfoVer2(/refRecordGenMergeInfo(/' $(SRC)/app/SL_MergeCameraGroup.cpp | \
-//     $(DROPIN_CXX) -I../tests/cxx/ref_shim_merge $(DROPIN_INC) -DCOSLAMTHREAD_H_ -include ../tests/cxx/ref_shim_merge/ref_mergematch_offpath.h \
-//       -x c++ -c - -o _ref/mergematch_ref.o
-//   $(DROPIN_CXX) -I../tests/cxx/ref_shim_merge $(DROPIN_INC) -DCOSLAMTHREAD_H_ -include ../tests/cxx/ref_shim_merge/ref_mergematch_offpath.h \
-//       ../tests/cxx/ref_mergematch_test.cpp _ref/mergematch_ref.o $(MODEL_SRCS) $(SRC)/slam/SL_KeyPoseList.cpp $(SRC)/slam/SL_MapPointList.cpp \
-//       $(SRC)/slam/SL_NCCBlock.cpp $(SRC)/slam/SL_FeatureMatching.cpp ref_shim/ref_glue_impl.cpp ref_shim/shim_impl.cpp \
-//       ref_shim/ref_posegraph_standin.cpp $(DROPIN_LD) -L. -loracle '-Wl,-rpath,$$ORIGIN/..' -lpthread -o _ref/ref_mergematch_test && \
-//     rm -f _ref/mergematch_ref.o
+// Built by oracle/Makefile, target _ref/ref_mergematch_test (where the reference tree exists; SL_MergeCameraGroup.cpp goes through
+// ref_mergeconstraints_test's three rewrites and a fourth that redirects :416).
 // TEST INFRASTRUCTURE; the binary goes to oracle/_ref/ (untracked), nothing on the GPU side needs it.
 #include <cmath>
 #include <cstdio>

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Generates tests/golden/*.npz.
+"""Generates tests/golden/*.npz: `python tests/golden/make_golden.py [names...]` writes the named fixtures of tests/golden/fixtures.py
+(all 28 without names) with the makers below and those of the make_merge*_golden.py files.
 
 pose_golden.npz  -- inputs and outputs of the REFERENCE's own intraCamEstimate (src/slam/SL_IntraCamPose.cpp compiled in
                     place into oracle/_ref/libintracam_ref.so by oracle/Makefile).  Needs /root/reference; run in the build
@@ -34,6 +35,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 
 import oracle  # noqa: E402
+from tests.golden.fixtures import BY_NAME, FIXTURES, driver_output, make, missing_binaries, run_driver  # noqa: E402
+from tests.golden.fixtures import path as fixture_path  # noqa: E402
 from coslam_amd.klt import KLT_SequenceTrackerConfig  # noqa: E402
 from coslam_amd.synth import Scene, make_ba_problem, rodrigues  # noqa: E402
 
@@ -97,16 +100,7 @@ def ba_case():
 
 
 def register_case():
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_register_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_register_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "reg.bin")
-        subprocess.run([exe, "golden", path], check=True)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_register_test", "golden")
     N, Q, none, _ = np.frombuffer(raw, dtype=np.int32, count=4)
     o = 16
     xy = np.frombuffer(raw, dtype=np.float64, count=2 * N, offset=o)
@@ -122,16 +116,7 @@ def register_case():
 
 def ncc_case():
     """the reference's own NCCBlock::computeScaled / getEpiNccMat (oracle/_ref/ref_ncc_test golden, CPU)"""
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_ncc_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_ncc_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "ncc.bin")
-        subprocess.run([exe, "golden", path], check=True)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_ncc_test", "golden")
     W, H, M, N = np.frombuffer(raw, dtype=np.int32, count=4)
     o = 16
     F = np.frombuffer(raw, dtype=np.float64, count=9, offset=o)
@@ -163,16 +148,7 @@ def posegraph_case():
     (oracle/_ref/ref_posegraph_test golden, CPU).  Flat arrays: graph g owns nodes [node_ptr[g], node_ptr[g+1]) and edges
     [edge_ptr[g], edge_ptr[g+1]); id1 / id2 are local to the graph."""
     import struct
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_posegraph_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_posegraph_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "pg.bin")
-        subprocess.run([exe, "golden", path], check=True)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_posegraph_test", "golden")
     ng, _ = struct.unpack_from("ii", raw, 0)
     o = 8
     node_ptr, edge_ptr = [0], [0]
@@ -201,15 +177,11 @@ def export_case():
     """the reference's own CoSLAM::exportResults (oracle/_ref/ref_export_test golden, CPU): the six files it writes and the
     arrays cs_export_results_v1 needs to write them again.  Map point ids are the addresses of that run's objects."""
     import struct
-    import subprocess
     import tempfile
 
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_export_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_export_test missing: run `make -C oracle` where /root/reference exists")
     out = {}
     with tempfile.TemporaryDirectory() as td:
-        subprocess.run([exe, "golden", td], check=True, stdout=subprocess.DEVNULL)
+        run_driver("ref_export_test", "golden", td)
         raw = open(os.path.join(td, "inputs.bin"), "rb").read()
         for n in ("input_videos.txt", "mappts.txt", "0_campose.txt", "1_campose.txt", "0_featpts.txt", "1_featpts.txt"):
             out["file_" + n] = np.frombuffer(open(os.path.join(td, "slam_results", "ref", n), "rb").read(), dtype=np.uint8).copy()
@@ -243,16 +215,7 @@ def intercam_case():
     """the reference's own InterCamPoseEstimator::addMapPoints (oracle/_ref/ref_intercam_test golden, CPU): three scenes of cameras'
     records and the flattened vecPts3D / vecMeas2D it built from them."""
     import struct
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_intercam_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_intercam_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "ic.bin")
-        subprocess.run([exe, "golden", path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_intercam_test", "golden")
     o = [0]
 
     def ints(n):
@@ -297,16 +260,7 @@ def newpts_case():
     """the reference's own featTracksFromMatches + NewMapPtsNCC::reconstructTracks + decidePointType (oracle/_ref/ref_newpts_test golden,
     CPU): four scenes of cameras, candidate features, given matches, dynamic points' features (the last one of twelve cameras close
     together: tracks of nine and more views); the tracks in the reference's numbering and the new map points it made of them."""
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_newpts_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_newpts_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "np.bin")
-        subprocess.run([exe, "golden", path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_newpts_test", "golden")
     o = [0]
 
     def ints(n):
@@ -364,16 +318,7 @@ def decide_case():
     """the reference's own CoSLAM::curStaticPointsRegInGroup -- and, in the last two scenes, curDynamicPointsRegInGroup behind it, the
     order of currentMapPointsRegister -- (oracle/_ref/ref_decide_test golden, CPU): five scenes of cameras, pose histories, feature
     tracks and map points; which feature carries which point afterwards, every point's position / covariance."""
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_decide_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_decide_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "d.bin")
-        subprocess.run([exe, "golden", path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_decide_test", "golden")
     o = [0]
 
     def ints(n):
@@ -443,16 +388,7 @@ def decide_relink_case():
     first, seg}, segPool [nC][cap][4] = {slot, last, first, next}, refStatic; deadOwner [nC][Ntot] = the point that owned a dead slot's chain.
     Afterwards per (point, camera): ref_staleOwner (whose stale feature the point holds there, -1 none), ref_preOwner (whose dead-track chain
     hangs directly behind the live feature it holds there, -1 none)."""
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_decide_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_decide_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "d.bin")
-        subprocess.run([exe, "golden_relink", path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_decide_test", "golden_relink")
     o = [0]
 
     def ints(n):
@@ -577,16 +513,7 @@ def mergability_case():
     """the reference's own CoSLAM::staticCheckMergability (oracle/_ref/ref_mergability_test golden, CPU): 150 tracks of 1..24
     frames, newest first, and its verdicts."""
     import struct
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_mergability_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_mergability_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "m.bin")
-        subprocess.run([exe, "golden", path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_mergability_test", "golden")
     (n,) = struct.unpack_from("i", raw, 0)
     o = 4
     Ls, sig, K, M, cov, rec, verdict = [], [], [], [], [], [], []
@@ -609,16 +536,7 @@ def mergability_long_case():
     x 420 frames of poses, 48 tracks per camera (most 200-420 frames long, a few inside the 64-frame window), each with its own map
     point, laid out frame by frame the way the device's history is fed; pixels of frames before a track's first are NaN."""
     import struct
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_mergability_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_mergability_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "m.bin")
-        subprocess.run([exe, "golden_long", path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_mergability_test", "golden_long")
     nC, T, nT = struct.unpack_from("iii", raw, 0)
     (sigma,) = struct.unpack_from("d", raw, 12)
     o = 20
@@ -653,16 +571,7 @@ def update_points_case(mode="golden"):
     point index, ring entry 0 = the current frame), and the reference's points / covariances afterwards.  mode="golden_wide": the
     driver's 7 / 8 / 9 / 12 / 13-camera scenes of 48 points, same layout."""
     import struct
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_update_points_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_update_points_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "u.bin")
-        subprocess.run([exe, mode, path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_update_points_test", mode)
     o = 0
 
     def ints(n):
@@ -747,16 +656,7 @@ def update_points_relink_case(mode="golden_relink"):
     lost track leave them, re-laid out the way the device holds them: every segment of consecutive frames on a slot of its own (slot =
     running number per camera), featRef [nP][nC][4] = {slot, frame, first, seg}, segPool [nC][cap][4] = {slot, last, first, next}.
     mode="golden_wide_relink": the driver's 8 / 13-camera scenes of 48 points, same layout."""
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_update_points_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_update_points_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "u.bin")
-        subprocess.run([exe, mode, path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_update_points_test", mode)
     o = 0
 
     def ints(n):
@@ -848,16 +748,7 @@ def update_points_relink_case(mode="golden_relink"):
 def keyframe_case():
     """the reference's own key-frame decision (oracle/_ref/ref_keyframe_test golden, CPU): CoSLAM::IsReadyForKeyFrame with its helpers,
     compiled in place, on 6 scenes of 3-6 cameras x 400 slots; the device's tables (state, slot2map) and the reference's answers"""
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_keyframe_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_keyframe_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "k.bin")
-        subprocess.run([exe, "golden", path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_keyframe_test", "golden")
     o = 0
 
     def ints(n):
@@ -908,16 +799,7 @@ def keyframe_case():
 def intracam_newpts_case():
     """the reference's own SingleSLAM::newMapPoints (oracle/_ref/ref_intracam_newpts_test golden, CPU): three one-camera scenes of 160 slots;
     the device's tables (history, state, slot2map, trackSpan, isStatic) and the reference's new points in slot order"""
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_intracam_newpts_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_intracam_newpts_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "n.bin")
-        subprocess.run([exe, "golden", path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_intracam_newpts_test", "golden")
     o = 0
 
     def ints(n):
@@ -974,16 +856,7 @@ def classify_case(mode="golden"):
     isStaticRemovable (oracle/_ref/ref_classify_test golden, CPU): 3 scenes of 72 map points walking every branch, re-laid out the
     way the device holds them (slot = point index, ring entry 0 = the current frame), and the points' states afterwards.
     mode="golden_wide": the driver's 8 / 9 / 13-camera scenes of 48 points, same layout."""
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_classify_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_classify_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "c.bin")
-        subprocess.run([exe, mode, path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_classify_test", mode)
     o = 0
 
     def ints(n):
@@ -1062,16 +935,7 @@ def classify_relink_case(mode="golden_relink"):
     featRef [nP][nC][4] = {slot, frame, first, seg}, segPool [nC][cap][4] = {slot, last, first, next}; pointFeat names the heads that are
     of this frame.  featDyn_ref [nP][nC]: the type the reference left on the feature each pointer names (live or stale).
     mode="golden_wide_relink": the driver's 8 / 13-camera scenes of 48 points, same layout."""
-    import subprocess
-    import tempfile
-
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_classify_test")
-    if not os.path.exists(exe):
-        raise SystemExit("oracle/_ref/ref_classify_test missing: run `make -C oracle` where /root/reference exists")
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "c.bin")
-        subprocess.run([exe, mode, path], check=True, stdout=subprocess.DEVNULL)
-        raw = open(path, "rb").read()
+    raw = driver_output("ref_classify_test", mode)
     o = 0
 
     def ints(n):
@@ -1264,55 +1128,11 @@ def cgklt_cases():
 
 
 if __name__ == "__main__":
-    if not oracle.have_ref():
-        raise SystemExit("oracle/_ref/libintracam_ref.so missing: run `make -C oracle` where /root/reference exists")
-    which = sys.argv[1:] or ["pose", "klt", "ba", "register", "ncc", "posegraph", "export", "mergability", "mergability_long", "update_points", "update_points_relink", "keyframe", "intracam_newpts", "classify", "classify_relink", "update_points_wide", "update_points_wide_relink", "classify_wide", "classify_wide_relink", "intercam", "decide_relink", "newpts", "decide", "cgklt"]
-    if "pose" in which:
-        np.savez_compressed(os.path.join(HERE, "pose_golden.npz"), **pose_cases())
-    if "klt" in which:
-        np.savez_compressed(os.path.join(HERE, "klt_golden.npz"), **klt_cases())
-    if "ba" in which:
-        np.savez_compressed(os.path.join(HERE, "ba_golden.npz"), **ba_case())
-    if "register" in which:
-        np.savez_compressed(os.path.join(HERE, "register_golden.npz"), **register_case())
-    if "ncc" in which:
-        np.savez_compressed(os.path.join(HERE, "ncc_golden.npz"), **ncc_case())
-    if "posegraph" in which:
-        np.savez_compressed(os.path.join(HERE, "posegraph_golden.npz"), **posegraph_case())
-    if "export" in which:
-        np.savez_compressed(os.path.join(HERE, "export_golden.npz"), **export_case())
-    if "intercam" in which:
-        np.savez_compressed(os.path.join(HERE, "intercam_golden.npz"), **intercam_case())
-    if "mergability" in which:
-        np.savez_compressed(os.path.join(HERE, "mergability_golden.npz"), **mergability_case())
-    if "mergability_long" in which:
-        np.savez_compressed(os.path.join(HERE, "mergability_long_golden.npz"), **mergability_long_case())
-    if "update_points" in which:
-        np.savez_compressed(os.path.join(HERE, "update_points_golden.npz"), **update_points_case())
-    if "intracam_newpts" in which:
-        np.savez_compressed(os.path.join(HERE, "intracam_newpts_golden.npz"), **intracam_newpts_case())
-    if "keyframe" in which:
-        np.savez_compressed(os.path.join(HERE, "keyframe_golden.npz"), **keyframe_case())
-    if "classify_relink" in which:
-        np.savez_compressed(os.path.join(HERE, "classify_relink_golden.npz"), **classify_relink_case())
-    if "decide_relink" in which:
-        np.savez_compressed(os.path.join(HERE, "decide_relink_golden.npz"), **decide_relink_case())
-    if "update_points_relink" in which:
-        np.savez_compressed(os.path.join(HERE, "update_points_relink_golden.npz"), **update_points_relink_case())
-    if "classify" in which:
-        np.savez_compressed(os.path.join(HERE, "classify_golden.npz"), **classify_case())
-    if "update_points_wide" in which:
-        np.savez_compressed(os.path.join(HERE, "update_points_wide_golden.npz"), **update_points_case("golden_wide"))
-    if "update_points_wide_relink" in which:
-        np.savez_compressed(os.path.join(HERE, "update_points_wide_relink_golden.npz"), **update_points_relink_case("golden_wide_relink"))
-    if "classify_wide" in which:
-        np.savez_compressed(os.path.join(HERE, "classify_wide_golden.npz"), **classify_case("golden_wide"))
-    if "classify_wide_relink" in which:
-        np.savez_compressed(os.path.join(HERE, "classify_wide_relink_golden.npz"), **classify_relink_case("golden_wide_relink"))
-    if "decide" in which:
-        np.savez_compressed(os.path.join(HERE, "decide_golden.npz"), **decide_case())
-    if "newpts" in which:
-        np.savez_compressed(os.path.join(HERE, "newpts_golden.npz"), **newpts_case())
-    if "cgklt" in which:
-        np.savez_compressed(os.path.join(HERE, "cgklt_golden.npz"), **cgklt_cases())
-    print("golden fixtures written")
+    unknown = [n for n in sys.argv[1:] if n not in BY_NAME]
+    if unknown:
+        raise SystemExit("unknown fixture(s) %s; the names are: %s" % (", ".join(unknown), " ".join(f.name for f in FIXTURES)))
+    for fx in [BY_NAME[n] for n in sys.argv[1:]] or FIXTURES:
+        if missing_binaries(fx):
+            raise SystemExit("oracle/_ref/%s missing: run `make -C oracle` where the reference tree exists" % missing_binaries(fx)[0])
+        np.savez_compressed(fixture_path(fx), **make(fx))
+        print("wrote %s: %d bytes" % (fixture_path(fx), os.path.getsize(fixture_path(fx))))

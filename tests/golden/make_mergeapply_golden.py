@@ -1,9 +1,9 @@
 """Writes tests/golden/mergeapply_golden.npz: the reference's OWN CoSLAM::getMapPts + updateStaticPointPositionAtKeyFrms (what
 MergeCameraGroup::recomputeMapPoints runs per point) on four scenes of chains built with its classes -- the fixture of
-cs_recompute_map_points_keyfrms_dev.  Needs oracle/_ref/ref_mergeapply_test (tests/cxx/ref_mergeapply_test.cpp; its compile
-line is in its header); run once where the reference tree exists:
+cs_recompute_map_points_keyfrms_dev.  Needs oracle/_ref/ref_mergeapply_test (tests/cxx/ref_mergeapply_test.cpp, built by
+oracle/Makefile); where the reference tree exists:
 
-    python tests/golden/make_mergeapply_golden.py
+    python tests/golden/make_golden.py mergeapply
 
 Scenes: 3, 4, 6 and 12 cameras, 80-160 frames of poses, a key frame every 3-9 frames at irregular spacing, ~150 points each, per point and
 camera a chain of 0-3 segments with gaps and stale heads.  Some cameras stand still for the older half of the run (bit-identical poses:
@@ -12,7 +12,6 @@ second view).  The file holds data only (tests/mergeapply_golden_util.py says ho
 import math
 import os
 import struct
-import subprocess
 import sys
 import tempfile
 
@@ -22,10 +21,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 from tests import mergeapply_ref as ref  # noqa: E402
-from tests.mergeapply_golden_util import GOLDEN, chain_nodes, expand  # noqa: E402
+from tests.golden.fixtures import run_driver  # noqa: E402
+from tests.mergeapply_golden_util import chain_nodes, expand  # noqa: E402
 
 SEED = 20
-EXE = os.path.join(ROOT, "oracle", "_ref", "ref_mergeapply_test")
 MIN_EACH = 30
 
 
@@ -234,8 +233,7 @@ def categories(S, E, M_ref):
     return c, cnt
 
 
-def main():
-    assert os.path.exists(EXE), f"{EXE} is missing: compile tests/cxx/ref_mergeapply_test.cpp (the line is in its header)"
+def mergeapply_case():
     rng = np.random.default_rng(SEED)
     scenes = [make_scene(sc, rng) for sc in range(4)]
     for sc, S in enumerate(scenes):
@@ -246,7 +244,7 @@ def main():
             f.write(struct.pack("i", len(scenes)))
             for S in scenes:
                 write_input(f, S)
-        print(subprocess.run([EXE, "golden", pin, pout], check=True, capture_output=True, text=True).stdout.strip())
+        print(run_driver("ref_mergeapply_test", "golden", pin, pout).strip())
         raw = open(pout, "rb").read()
     off, total = 0, {}
     out = dict(n_scenes=np.int32(len(scenes)), seed=np.int32(SEED))
@@ -272,10 +270,4 @@ def main():
     for k, v in total.items():
         assert v >= MIN_EACH, f"only {v} of {k}"
     assert sum(len(S["filter_points"]) for S in scenes) >= MIN_EACH
-    np.savez_compressed(GOLDEN, **out)
-    print(f"wrote {GOLDEN}: {os.path.getsize(GOLDEN)} bytes")
-    assert os.path.getsize(GOLDEN) < 300 * 1024
-
-
-if __name__ == "__main__":
-    main()
+    return out

@@ -1,15 +1,14 @@
 """Writes tests/golden/mergeconstraints_golden.npz: the reference's OWN MergeCameraGroup::genMergeInfoVer2 (with a solver stand-in that records
 its arguments and changes nothing) on six scenes built with its classes -- the fixture of cs_merge_first_constrain,
 cs_merge_constraints_assemble_dev and cs_merge_info_dev.  Needs oracle/_ref/ref_mergeconstraints_test
-(tests/cxx/ref_mergeconstraints_test.cpp; its compile lines are in its header); run once where the reference tree exists:
+(tests/cxx/ref_mergeconstraints_test.cpp, built by oracle/Makefile); where the reference tree exists:
 
-    python tests/golden/make_mergeconstraints_golden.py
+    python tests/golden/make_golden.py mergeconstraints
 
 Every case the fixture has to hold is ASSERTED below (COVER), counted with the restatement tests/mergeconstraints_ref.py after it has been
 checked against the reference's output, so a scene cannot silently stop covering its case.  The file holds data only."""
 import os
 import struct
-import subprocess
 import sys
 import tempfile
 
@@ -19,11 +18,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 from tests import mergeconstraints_ref as ref  # noqa: E402
-from tests.mergeconstraints_golden_util import GOLDEN, RESULT_KEYS, SCENE_KEYS, expand  # noqa: E402
+from tests.golden.fixtures import run_driver  # noqa: E402
+from tests.mergeconstraints_golden_util import RESULT_KEYS, SCENE_KEYS, expand  # noqa: E402
 from tests.mergeconstraints_scenes import make_scene, write_input  # noqa: E402
 
 SEED = 22
-EXE = os.path.join(ROOT, "oracle", "_ref", "ref_mergeconstraints_test")
 
 # groups (discovery order, not ascending), the two groups, maxiCam / maxjCam, frames held, key-frame gaps back from the current frame,
 # self-motion per older key frame (newest first) as the set of cameras that moved, points per side, matches, what the matches plant
@@ -146,8 +145,7 @@ def ref_cur(S, m, c):
     return int(r[0]) >= 0 and int(r[1]) == S["frame0"] + S["nF"] - 1
 
 
-def main():
-    assert os.path.exists(EXE), f"{EXE} is missing: compile tests/cxx/ref_mergeconstraints_test.cpp (the lines are in its header)"
+def mergeconstraints_case():
     rng = np.random.default_rng(SEED)
     raws = [make_scene(sc, spec, rng) for sc, spec in enumerate(SPECS)]
     scenes = [expand(r) for r in raws]
@@ -157,7 +155,7 @@ def main():
             f.write(struct.pack("i", len(scenes)))
             for S in scenes:
                 write_input(f, S)
-        print(subprocess.run([EXE, "golden", pin, pout], check=True, capture_output=True, text=True).stdout.strip())
+        print(run_driver("ref_mergeconstraints_test", "golden", pin, pout).strip())
         rd = Reader(open(pout, "rb").read())
     out = dict(n_scenes=np.int32(len(scenes)), seed=np.int32(SEED))
     cover = {k: 0 for k in COVER}
@@ -175,10 +173,4 @@ def main():
     print("covered:", cover)
     for k, v in cover.items():
         assert v > 0, f"no scene covers {k}"
-    np.savez_compressed(GOLDEN, **out)
-    print(f"wrote {GOLDEN}: {os.path.getsize(GOLDEN)} bytes")
-    assert os.path.getsize(GOLDEN) < 700 * 1024
-
-
-if __name__ == "__main__":
-    main()
+    return out

@@ -1,25 +1,18 @@
 """tests/golden/mergegraph_golden.npz from the reference's own computeNewCameraRotations + computeNewCameraTranslations4
-(oracle/_ref/ref_mergegraph_test golden; the driver and its compile line: tests/cxx/ref_mergegraph_test.cpp).  Data only.
+(oracle/_ref/ref_mergegraph_test golden; the driver: tests/cxx/ref_mergegraph_test.cpp; tests/golden/fixtures.py lists the maker).  Data only.
 Flat arrays as in posegraph_golden.npz: graph g owns nodes [node_ptr[g], node_ptr[g+1]) and edges [edge_ptr[g],
 edge_ptr[g+1]); id1 / id2 are local to the graph; scale_id < 0 is a plain edge; edgeS is CamPoseEdge::s."""
-import os
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+from tests.golden.fixtures import driver_output
+
 NAMES = ["merge_2x3", "merge_3x4", "merge_8x6", "merge_16x4", "merge_8x24", "two_scales", "shared_scale", "fixed_id2", "fixed_id1"]
 
 
-def mergegraph_case(exe):
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "mg.bin")
-        subprocess.run([exe, "golden", path], check=True)
-        raw = open(path, "rb").read()
+def mergegraph_case():
+    raw = driver_output("ref_mergegraph_test", "golden")
     ng, _ = struct.unpack_from("ii", raw, 0)
     assert ng == len(NAMES)
     o = 8
@@ -49,10 +42,3 @@ def mergegraph_case(exe):
                 fixed=np.array(fixed, np.uint8), node_constraint=np.array(ncons, np.uint8), frame=i32(frame), cam=i32(cam),
                 nodeR=np.array(R), nodeT=np.array(t), newR=np.array(nR), newT=np.array(nt), id1=i32(id1), id2=i32(id2),
                 scale_id=i32(sid), edge_constraint=np.array(econs, np.uint8), edgeR=np.array(eR), edgeT=np.array(eT), edgeS=np.array(eS))
-
-
-if __name__ == "__main__":
-    exe = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "oracle", "_ref", "ref_mergegraph_test")
-    if not os.path.exists(exe):
-        raise SystemExit(f"{exe} missing: build it with the compile line in tests/cxx/ref_mergegraph_test.cpp")
-    np.savez_compressed(os.path.join(HERE, "mergegraph_golden.npz"), **mergegraph_case(exe))

@@ -1,12 +1,11 @@
 #!/usr/bin/env python
 """Writes tests/golden/mergematch_golden.npz: the scenes of tests/mergematch_scenes.py with what the reference's OWN
 MergeCameraGroup::storeFeaturePoints / matchFeaturePointsNCC / matchMergableCameras give on them (oracle/_ref/ref_mergematch_test, built
-by the compile lines in tests/cxx/ref_mergematch_test.cpp where the reference tree exists).  Run from the repository's root:
-    python tests/golden/make_mergematch_golden.py
+by oracle/Makefile where the reference tree exists).  Run from the repository's root:
+    python tests/golden/make_golden.py mergematch
 Scene 2 is scene 1 again with the driver's own calls at nccMin = the score of one of its candidates (found with the restatement; the
 reference then decides what a candidate exactly at nccMin does).  COVER lists the cases the fixture must hold; each is asserted here."""
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -15,6 +14,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from tests import mergematch_ref as R           # noqa: E402
+from tests.golden.fixtures import run_driver    # noqa: E402
 from tests import mergematch_scenes as MS       # noqa: E402
 
 COVER = ["two group pairs, three matched entries, the i != k quirk changes the winner", "an entry with fewer than 25 SURF matches",
@@ -42,7 +42,7 @@ def flatten(k, S, G):
     return out
 
 
-def main():
+def mergematch_case():
     s1 = MS.scene_edges()
     (e, job), = MS.jobs_of(s1)
     ref = R.match_job(s1["cams"], MS.WS, MS.HS, job, *s1["par"])
@@ -50,11 +50,10 @@ def main():
     assert len(mid) >= 3, mid
     ncc_min = mid[len(mid) // 2]
     scenes = [MS.scene_quirk(), s1, MS.scene_edges(ncc_min=ncc_min)]
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_mergematch_test")
     with tempfile.TemporaryDirectory() as d:
         with open(os.path.join(d, "in.bin"), "wb") as f:
             MS.write_input(f, scenes)
-        print(subprocess.run([exe, "golden", os.path.join(d, "in.bin"), os.path.join(d, "out.bin")], check=True, capture_output=True, text=True).stdout)
+        print(run_driver("ref_mergematch_test", "golden", os.path.join(d, "in.bin"), os.path.join(d, "out.bin")))
         G = MS.read_output(open(os.path.join(d, "out.bin"), "rb").read(), scenes)
     covered = set()
     # ---- scene 0: the loop's quirk, the skips, the else orientation
@@ -115,10 +114,4 @@ def main():
     out = dict(n_scenes=np.array(len(scenes), np.int32))
     for k, (S, g) in enumerate(zip(scenes, G)):
         out.update(flatten(k, S, g))
-    path = os.path.join(ROOT, "tests", "golden", "mergematch_golden.npz")
-    np.savez_compressed(path, **out)
-    print(path, os.path.getsize(path), "bytes")
-
-
-if __name__ == "__main__":
-    main()
+    return out

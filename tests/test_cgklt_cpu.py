@@ -8,7 +8,8 @@ detect / redetect / redetect sequences with and without gain.  The oracle must r
 sample through and the host's pass schedule -- is stated in oracle/ref_shim/cg/cg_shim.h.
 
 Where the compiled shaders are present (the build container; they also travel to the GPU box), the same comparison runs live
-on seeded inputs at the bench's sizes, and the committed fixture is regenerated and compared."""
+on seeded inputs at the bench's sizes; the committed fixture is regenerated and compared with every other one in
+tests/test_oracle_cpu.py (test_committed_fixture_is_what_its_maker_produces_now[cgklt])."""
 import hashlib
 import os
 
@@ -114,18 +115,6 @@ def test_gain_pass_with_dead_slots_and_thresholds(g):
 
 
 # ------------------------------------------------------------------------------------------------- live, where the shaders are built
-
-@needs_cgref
-def test_committed_fixture_is_what_the_shaders_produce_now():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(os.path.dirname(GOLD), "make_golden.py"))
-    mg = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mg)
-    fresh, old = mg.cgklt_cases(), np.load(GOLD)
-    assert sorted(fresh.keys()) == sorted(old.files)
-    for k in old.files:
-        assert np.ascontiguousarray(fresh[k]).tobytes() == np.ascontiguousarray(old[k]).tobytes(), k
-
 
 LIVE = [  # name, W, H, L, skip, window, iterations, fw, fh, minDistance
     ("cfg2", 640, 480, 4, 1, 7, 10, 50, 40, 5),

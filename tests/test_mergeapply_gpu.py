@@ -12,6 +12,7 @@ from coslam_amd.synth import make_merge_pose_graph
 from tests import mergeapply_e2e as e2e
 from tests import mergeapply_planted as planted
 from tests import mergeapply_ref as ref
+from tests.cxx_build import build_shim_test
 from tests.mergeapply_dev import load_history, recompute_dev, recompute_ref
 from tests.mergeapply_golden_util import GOLDEN, inv_k, scene
 
@@ -312,18 +313,12 @@ def test_end_to_end_run_recompute_groups(hip):
 def test_cxx_shim_merge_apply(hip, tmp_path):
     """include/shim/app/CoSLAMMergeApply.h driven like CoSLAM::mergeCamGroups (tests/cxx/mergeapply_shim_test.cpp) against MergeApply on the same
     history: the same kernels on the same inputs, bit for bit; the merged groups against the restatement"""
-    import os
     import struct
     import subprocess
 
     from coslam_amd.merge import _camera_groups_record
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src, exe = os.path.join(root, "tests", "cxx", "mergeapply_shim_test.cpp"), str(tmp_path / "mergeapply_shim_test")
-    libdir = os.path.join(root, "coslam_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "include", "shim"),
-                           "-I/opt/rocm/include", src, "-L", libdir, "-lcoslam_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib",
-                           "-lamdhip64", "-o", exe])
+    exe = build_shim_test("mergeapply_shim_test.cpp", tmp_path)
     dev = _dev()
     m, S, _plan, key_frames = _pose_scene(3, 4, extra_cam=False, pre=0)
     kf_of = {f: int(key_frames[k]) for k, f in enumerate(m["frames"])}

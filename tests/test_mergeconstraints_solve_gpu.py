@@ -12,6 +12,7 @@ import coslam_amd
 import oracle
 
 from tests import mergeconstraints_ref as ref
+from tests.cxx_build import build_shim_test
 from tests.mergeconstraints_dev import DeviceScene, assemble_dev
 from tests.mergeconstraints_golden_util import expand, load
 from tests.mergeconstraints_scenes import make_scene, write_input
@@ -248,16 +249,10 @@ def test_cxx_shim_gen_merge_info(hip, tmp_path, sc):
     """include/shim/app/CoSLAMMergeConstraints.h driven like matchMergableCameras (tests/cxx/mergeconstraints_shim_test.cpp: the matches as
     the reference's list indices) against MergeConstraints on the same scene: first-constrained frame, verdict, avgErr, counts and the
     MergeInfo list behind the two solves, bit for bit; a rejected verdict returns false with no info"""
-    import os
     import struct
     import subprocess
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src, exe = os.path.join(root, "tests", "cxx", "mergeconstraints_shim_test.cpp"), str(tmp_path / "mergeconstraints_shim_test")
-    libdir = os.path.join(root, "coslam_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "include", "shim"),
-                           "-I/opt/rocm/include", src, "-L", libdir, "-lcoslam_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib",
-                           "-lamdhip64", "-o", exe])
+    exe = build_shim_test("mergeconstraints_shim_test.cpp", tmp_path)
     S, G = SCENES[sc]
     with open(tmp_path / "in.bin", "wb") as f:
         f.write(struct.pack("i", 1))

@@ -1,7 +1,6 @@
 """include/shim/app/CoSLAMMergeFront.h (tests/cxx/mergefront_shim_test.cpp): matchSURFPoints and computeEMat with the reference's argument
 shapes -- Mat_d point lists, vector<float> descriptors, Matching in and out -- against the restatement tests/mergefront_ref.py on one scene
 (a noisy RANSAC case of tests/mergefront_scenes.py, whose cover conditions make the comparison exact)."""
-import os
 import struct
 import subprocess
 
@@ -9,17 +8,13 @@ import numpy as np
 import pytest
 
 from tests import mergefront_scenes as S
+from tests.cxx_build import build_shim_test
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cxx_shim_match_surf_points_and_compute_emat(hip, tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src, exe = os.path.join(root, "tests", "cxx", "mergefront_shim_test.cpp"), str(tmp_path / "mergefront_shim_test")
-    libdir = os.path.join(root, "coslam_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "include", "shim"),
-                           "-I/opt/rocm/include", src, "-L", libdir, "-lcoslam_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib",
-                           "-lamdhip64", "-o", exe])
+    exe = build_shim_test("mergefront_shim_test.cpp", tmp_path)
     nt, no, noise, seed, nr, gs = S.NOISY[0]
     sc, exp = S.ransac_case(nt, no, noise, seed, nr, gs)
     a, b = sc["cam1"], sc["cam2"]

@@ -7,7 +7,6 @@ system with a QR, the kernel its normal equations (L D L^T of the node matrix, t
 golden systems have full column rank (asserted in tests/test_mergegraph_cpu.py) and cond(A^T A) <= 1.3e4.  The scales are
 unknowns of the translation system: TOL_T."""
 import ctypes as C
-import os
 import struct
 import subprocess
 
@@ -19,11 +18,11 @@ import oracle
 from coslam_amd._lib import check
 from coslam_amd.synth import make_merge_pose_graph, make_pose_graphs
 from tests import mergegraph_ref as ref
+from tests.cxx_build import build_shim_test
 from tests.test_mergegraph_cpu import golden_graphs
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL_R, TOL_T = 1e-10, 1e-9
 INVALID, NUMERIC = -1, -5
 
@@ -240,10 +239,7 @@ def test_merge_pose_correction(hip):
 
 def test_cxx_shim_relax_scaled_pose_graph(hip, gold, tmp_path):
     d = gold[0]
-    src, exe = os.path.join(ROOT, "tests", "cxx", "mergegraph_shim_test.cpp"), str(tmp_path / "mergegraph_shim_test")
-    libdir = os.path.join(ROOT, "coslam_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "include", "shim"), src,
-                           "-L", libdir, "-lcoslam_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-o", exe])
+    exe = build_shim_test("mergegraph_shim_test.cpp", tmp_path, hip_runtime=False)
     n, e = len(d["fixed"]), len(d["id1"])
     with open(tmp_path / "in.bin", "wb") as f:
         f.write(struct.pack("ii", n, e))

@@ -1,7 +1,6 @@
 """include/shim/app/CoSLAMMergeConstraints.h through mergeMapPoints (tests/cxx/mergemap_shim_test.cpp) against coslam_amd.MergeCamGroups on the
 same scene: the same kernels and solves on the same inputs, so the tables, the counts and the solved coordinates agree bit for bit; a
 rejected verdict leaves every table as it was."""
-import os
 import struct
 import subprocess
 
@@ -10,6 +9,7 @@ import pytest
 
 import coslam_amd
 from tests import mergemap_ref as mref
+from tests.cxx_build import build_shim_test
 from tests.mergeconstraints_golden_util import load
 from tests.mergeconstraints_scenes import write_input
 from tests.mergemap_dev import Live
@@ -21,12 +21,7 @@ SCENES = load()
 
 @pytest.mark.parametrize("sc", (3, 2))
 def test_cxx_shim_merge_map_points(hip, tmp_path, sc):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src, exe = os.path.join(root, "tests", "cxx", "mergemap_shim_test.cpp"), str(tmp_path / "mergemap_shim_test")
-    libdir = os.path.join(root, "coslam_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "include", "shim"),
-                           "-I/opt/rocm/include", src, "-L", libdir, "-lcoslam_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib",
-                           "-lamdhip64", "-o", exe])
+    exe = build_shim_test("mergemap_shim_test.cpp", tmp_path)
     S, G = SCENES[sc]
     with open(tmp_path / "in.bin", "wb") as f:
         f.write(struct.pack("i", 1))

@@ -1,6 +1,5 @@
 """include/shim/app/CoSLAMMergeMatch.h (tests/cxx/mergematch_shim_test.cpp): matchFeaturePointsNCC with the reference's argument shapes --
 SURF positions and the inlier Matching in, a Matching of LIST indices out -- against the restatement tests/mergematch_ref.py, bit for bit."""
-import os
 import struct
 import subprocess
 
@@ -8,17 +7,13 @@ import numpy as np
 import pytest
 
 from tests import mergematch_ref as R
+from tests.cxx_build import build_shim_test
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cxx_shim_match_feature_points_ncc(hip, tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src, exe = os.path.join(root, "tests", "cxx", "mergematch_shim_test.cpp"), str(tmp_path / "mergematch_shim_test")
-    libdir = os.path.join(root, "coslam_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "include", "shim"),
-                           "-I/opt/rocm/include", src, "-L", libdir, "-lcoslam_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib",
-                           "-lamdhip64", "-o", exe])
+    exe = build_shim_test("mergematch_shim_test.cpp", tmp_path)
     N, WS, HS = 70, 192, 144
     cams, job, _ = R.shifted_pair_scene(N=N, n_cams=3, pair=(2, 0), seed=21)
     ref = R.match_job(cams, WS, HS, job)

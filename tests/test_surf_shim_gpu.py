@@ -1,6 +1,5 @@
 """include/shim/app/CoSLAMSurf.h (tests/cxx/surf_shim_test.cpp): detectSURFPoints(ImgG, Mat_d, vector<float>) with the reference's argument
 shapes -- through the handle cached per image size and through a caller-held cs_surf* -- against coslam_amd.Surf on one 160 x 120 texture."""
-import os
 import struct
 import subprocess
 
@@ -9,18 +8,14 @@ import pytest
 
 import coslam_amd
 from tests import surf_scenes as S
+from tests.cxx_build import build_shim_test
 from tests.test_surf_gpu import upload
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cxx_shim_detect_surf_points(hip, tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src, exe = os.path.join(root, "tests", "cxx", "surf_shim_test.cpp"), str(tmp_path / "surf_shim_test")
-    libdir = os.path.join(root, "coslam_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "include", "shim"),
-                           "-I/opt/rocm/include", src, "-L", libdir, "-lcoslam_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib",
-                           "-lamdhip64", "-o", exe])
+    exe = build_shim_test("surf_shim_test.cpp", tmp_path)
     W, H = 160, 120
     img = S.scene(W, H)[0]
     with open(tmp_path / "in.bin", "wb") as f:
