@@ -176,6 +176,11 @@ __device__ __forceinline__ int cs_wave_sum_i(int v) {
 // halves the number of values a lane still carries (the lower lane of a pair keeps the first half of the list, the
 // upper lane the second half), so N values need N/2 + N/4 + ... ~ N exchanges in total and each total ends up in ONE
 // lane: value q in lane cs_reduce_owner<N>(q).  Fixed tree, deterministic.
+// No exchange goes through LDS (no ds_bpermute).  Distances 32 and 16 take the pair (first half's value, second half's value)
+// through ONE lane swap per dword (v_permlane32_swap / v_permlane16_swap, as cs_swap32_add / cs_swap16_add above) and ONE add:
+// after the swap the lower lane holds its own and its partner's first-half value, the upper lane both second-half values --
+// the two addends of the select-and-shuffle form, no select.  Distances 8, 4, 2, 1 keep the selects and fetch the partner's
+// value by DPP: xor 8 = row_ror:8, xor 4 = quad_perm [3,2,1,0] then row_half_mirror, xor 2 and xor 1 = quad_perm.
 __device__ __forceinline__ double cs_shfl_xor_d(double v, int d) {
     int lo = __shfl_xor(__double2loint(v), d, 64), hi = __shfl_xor(__double2hiint(v), d, 64);
     return __hiloint2double(hi, lo);
@@ -184,6 +189,28 @@ __device__ __forceinline__ double cs_readlane_d(double v, int l) {
     int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
     int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
     return __hiloint2double(hi, lo);
+}
+template <int DIST>
+__device__ __forceinline__ double cs_swap_add_d(double x, double y) {   // DIST 32 or 16: lower lane x + x', upper lane y' + y
+    const unsigned xl = (unsigned)__double2loint(x), xh = (unsigned)__double2hiint(x);
+    const unsigned yl = (unsigned)__double2loint(y), yh = (unsigned)__double2hiint(y);
+    if constexpr (DIST == 32) {
+        const auto l = __builtin_amdgcn_permlane32_swap(xl, yl, false, false);
+        const auto h = __builtin_amdgcn_permlane32_swap(xh, yh, false, false);
+        return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
+    } else {
+        const auto l = __builtin_amdgcn_permlane16_swap(xl, yl, false, false);
+        const auto h = __builtin_amdgcn_permlane16_swap(xh, yh, false, false);
+        return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
+    }
+}
+template <int DIST>
+__device__ __forceinline__ double cs_dpp_xor_d(double v) {   // DIST 8, 4, 2 or 1: the value of lane (l ^ DIST)
+    static_assert(DIST == 8 || DIST == 4 || DIST == 2 || DIST == 1, "a distance inside a 16-lane row");
+    if constexpr (DIST == 8) return cs_dpp_d<0x128, 0xf>(v);                            // row_ror:8
+    else if constexpr (DIST == 4) return cs_dpp_d<0x141, 0xf>(cs_dpp_d<0x1B, 0xf>(v));  // quad_perm [3,2,1,0], row_half_mirror
+    else if constexpr (DIST == 2) return cs_dpp_d<0x4E, 0xf>(v);                        // quad_perm [2,3,0,1]
+    else return cs_dpp_d<0xB1, 0xf>(v);                                                 // quad_perm [1,0,3,2]
 }
 template <int M, int DIST>
 __device__ __forceinline__ void cs_reduce_step(double* v, int lane) {
@@ -194,8 +221,12 @@ __device__ __forceinline__ void cs_reduce_step(double* v, int lane) {
         for (int t = 0; t < H; ++t) {
             const double lo = v[t];
             const double hi = (H + t < M) ? v[H + t] : 0.0;
-            const double recv = cs_shfl_xor_d(up ? lo : hi, DIST);
-            v[t] = (up ? hi : lo) + recv;
+            if constexpr (DIST >= 16) {
+                v[t] = cs_swap_add_d<DIST>(lo, hi);
+            } else {
+                const double recv = cs_dpp_xor_d<DIST>(up ? lo : hi);
+                v[t] = (up ? hi : lo) + recv;
+            }
         }
         cs_reduce_step<H, DIST / 2>(v, lane);
     }

@@ -8,15 +8,19 @@
 // workgroup per camera (a batch of cameras = a grid of workgroups).  The reference is a serial loop
 // over <= 192 points with 7 projections each; here lane i owns point i, the 21+6 entries of the
 // weighted normal equations AND the weighted error of the same pose are folded together with one
-// transposed 64-lane butterfly per wave and one LDS exchange between the waves (one barrier), and
-// every lane then runs the 6x6 Gauss-Jordan and the LM accept/reject logic redundantly on identical
-// inputs, so the control flow stays uniform with no host round trip per iteration.  An LM step is ONE
+// transposed 64-lane butterfly per wave (lane swaps and DPP, cs_common.h) and one LDS exchange between
+// the waves (one barrier); every wave then runs the 6x6 Gauss-Jordan with a column of [A | B] per lane
+// (pose_solve_dev.h) and every lane the LM accept/reject logic redundantly on identical inputs, so the
+// control flow stays uniform with no host round trip per iteration.  Nothing in an LM step goes through
+// the LDS crossbar (no ds_bpermute).  An LM step is ONE
 // pass over the points: the reference projects every point at a tentative pose for its error and, once
 // it has accepted the pose, again for the next step's Jacobians -- the same numbers; here the pass at
 // the tentative pose yields both (lm_pass), and a round's Tukey weights are computed inside its first pass.
 // The arithmetic per point is the reference's, operation for operation (numeric Jacobians included):
 // only the order of the sum over points differs from the serial CPU loop.
 #include "cs_common.h"
+#include "pose_math.h"
+#include "pose_solve_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -28,63 +32,6 @@ constexpr int SMALL_NPTS = 64;    // up to here ONE wave owns the problem (no LD
                                   // seven projections per point, and three points per lane made it 73.6 vs 64.1 us at 192
                                   // points
 
-__device__ __forceinline__ void so3_exp(const double w[3], double R[9]) {  // SL_IntraCamPose.cpp:10-39
-    double theta = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    if (theta == 0) {
-        R[0] = 1, R[1] = 0, R[2] = 0, R[3] = 0, R[4] = 1, R[5] = 0, R[6] = 0, R[7] = 0, R[8] = 1;
-        return;
-    }
-    double hw0 = w[0] / theta, hw1 = w[1] / theta, hw2 = w[2] / theta;
-    double st, ct;
-    if (theta < 0.5) {
-        // an LM step's rotation is a fraction of a degree: sin and cos from their Taylor series (truncation below 2^-56 of the
-        // value for theta < 0.5; the library's routines carry a range reduction for arguments this never sees)
-        const double x2 = theta * theta;
-        double ps = 1.0 / 355687428096000.0;   // 1 / 17!
-        ps = ps * x2 - 1.0 / 1307674368000.0;
-        ps = ps * x2 + 1.0 / 6227020800.0;
-        ps = ps * x2 - 1.0 / 39916800.0;
-        ps = ps * x2 + 1.0 / 362880.0;
-        ps = ps * x2 - 1.0 / 5040.0;
-        ps = ps * x2 + 1.0 / 120.0;
-        ps = ps * x2 - 1.0 / 6.0;
-        st = theta + theta * (x2 * ps);
-        double pc = 1.0 / 20922789888000.0;    // 1 / 16!
-        pc = pc * x2 - 1.0 / 87178291200.0;
-        pc = pc * x2 + 1.0 / 479001600.0;
-        pc = pc * x2 - 1.0 / 3628800.0;
-        pc = pc * x2 + 1.0 / 40320.0;
-        pc = pc * x2 - 1.0 / 720.0;
-        pc = pc * x2 + 1.0 / 24.0;
-        const double c = 1.0 - (0.5 * x2 - x2 * x2 * pc);   // cos(theta), rounded: the reference forms 1 - cos(theta) from that (:20)
-        ct = 1 - c;
-    } else {
-        st = sin(theta);
-        ct = 1 - cos(theta);
-    }
-    double hw0hw0 = hw0 * hw0, hw0hw1 = hw0 * hw1, hw0hw2 = hw0 * hw2;
-    double hw1hw1 = hw1 * hw1, hw1hw2 = hw1 * hw2, hw2hw2 = hw2 * hw2;
-    R[0] = -ct * hw1hw1 - ct * hw2hw2 + 1;
-    R[1] = ct * hw0hw1 - st * hw2;
-    R[2] = st * hw1 + ct * hw0hw2;
-    R[3] = st * hw2 + ct * hw0hw1;
-    R[4] = -ct * hw0hw0 - ct * hw2hw2 + 1;
-    R[5] = ct * hw1hw2 - st * hw0;
-    R[6] = ct * hw0hw2 - st * hw1;
-    R[7] = st * hw0 + ct * hw1hw2;
-    R[8] = -ct * hw0hw0 - ct * hw1hw1 + 1;
-}
-
-__device__ __forceinline__ void mat33AB(const double* A, const double* B, double* C) {
-    double T[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) T[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) C[i] = T[i];
-}
-
 __device__ __forceinline__ void project(const double* K, const double* R, const double* t, const double* M, double* m) {
     double X = R[0] * M[0] + R[1] * M[1] + R[2] * M[2] + t[0];
     double Y = R[3] * M[0] + R[4] * M[1] + R[5] * M[2] + t[1];
@@ -94,44 +41,6 @@ __device__ __forceinline__ void project(const double* K, const double* R, const 
     double w = K[6] * X + K[7] * Y + K[8] * Z;
     m[0] = u / w;
     m[1] = v / w;
-}
-
-// (A + lambda I) p = B by Gauss-Jordan elimination with partial pivoting on [A | B] (the reference forms the LAPACK inverse and
-// multiplies: same solution), ONE MATRIX ENTRY PER LANE: lane 7 r + j holds M[r][j] (r < 6, j < 7; column 6 = B).  Every lane of a
-// wave running all 42 entries' arithmetic redundantly cost ~800 wave instructions per LM step, issued at 4 cycles each -- a third of
-// the step; here a pivot step is one divide and one multiply-subtract across the lanes plus the exchanges that feed them (the pivot
-// column through v_readlane, the row swap and the two factors through ds_bpermute).  Element for element the same operations as
-// the register version: the pivot of column c is the first row >= c with the largest |M[r][c]|, the pivot row is divided by it,
-// every other row loses f times the pivot row, columns <= c are left as they are.
-__device__ __forceinline__ double cs_shfl_d(double v, int srcLane) {
-    int lo = __shfl(__double2loint(v), srcLane, 64), hi = __shfl(__double2hiint(v), srcLane, 64);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ void solve66_lanes(double m, int lane, double* param) {
-    const int r = lane / 7, j = lane - 7 * r;   // lanes >= 42 (r >= 6) carry nothing
-    const bool in = r < 6;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double best = fabs(cs_readlane_d(m, 7 * c + c));
-        int p = c;
-#pragma unroll
-        for (int rr = c + 1; rr < 6; ++rr) {
-            const double v = fabs(cs_readlane_d(m, 7 * rr + c));
-            if (v > best) best = v, p = rr;
-        }
-        const int srcRow = r == c ? p : (r == p ? c : r);
-        const double sw = cs_shfl_d(m, in ? 7 * srcRow + j : lane);
-        m = sw;
-        const double d = cs_readlane_d(m, 7 * c + c);
-        const double q = m / d;
-        if (r == c && j > c) m = q;
-        const double f = cs_shfl_d(m, in ? 7 * r + c : lane);
-        const double pr = cs_shfl_d(m, in ? 7 * c + j : lane);
-        const double e = m - f * pr;
-        if (in && r != c && j > c) m = e;
-    }
-#pragma unroll
-    for (int rr = 0; rr < 6; ++rr) param[rr] = cs_readlane_d(m, 7 * rr + 6);
 }
 
 __device__ __forceinline__ double tukey(double e, double tau) {  // :646-653
@@ -147,50 +56,39 @@ struct PoseCtx {
     const double* ms;
     double* Ws;  // LDS or global scratch, npts
     int npts;
-    double* red;          // LDS [PB/64][27]
+    double* red;          // LDS [2][PB/64][NSUM]: the waves' totals, double-buffered (both templates)
     double pM[3], pm[2];  // the lane's FIRST point (i = threadIdx.x), read once instead of in every LM pass (170 points per camera: one
                           // point per lane; 2193-2200 against 2184-2186 frames/s in the loop, three alternating runs each)
-    double dR[3][9];      // exp(eps e_k): independent of the iterate (SL_IntraCamPose.cpp:57-58)
-    int myEntry;          // which of the 28 sums this lane holds in the lane-parallel solve
+    int myEntry[6];       // which of the 28 sums are the lane's column of [A | B] in the lane-parallel solve (solve66_lanes)
 };
 
 // The 27 sums of the weighted normal equations and the weighted squared error over the workgroup: the waves' transposed butterflies
-// leave each total in ONE lane, which stores it; ONE barrier; then a lane fetches what IT needs -- the entry of [A | B] it holds in
-// the lane-parallel solve (`mine`) and the error -- adding the waves' totals in wave order.  The scratch is double-buffered (`par`
-// flips per call), so no second barrier protects it from the next call's stores.
+// leave each total in ONE lane, which stores it; ONE barrier (none in the one-wave template: a wave reads what it wrote); then a lane
+// fetches what IT needs -- the column of [A | B] it holds in the lane-parallel solve (`mine`: six independent reads per wave's totals,
+// one latency) and the error -- adding the waves' totals in wave order.  The scratch is double-buffered (`par` flips per call), so no
+// second barrier protects it from the next call's stores.
 constexpr int NSUM = 28;
-// which of the 28 sums lane 7 r + j of the solve needs: A[r][j] = upper-triangle entry (min, max), B[r] = 21 + r
-__device__ __forceinline__ int solve_entry_of_lane(int lane) {
-    const int r = lane / 7, j = lane - 7 * r;
-    if (r >= 6) return 27;
-    if (j == 6) return 21 + r;
-    const int a = r < j ? r : j, b = r < j ? j : r;
-    return a * 6 - (a * (a - 1)) / 2 + (b - a);
-}
 template <int PB>
-__device__ __forceinline__ void block_sum28(double (&v)[NSUM], double* lds /* [2][PB/64][NSUM] */, int& par, int myEntry, double& mine,
-                                            double& err) {
+__device__ __forceinline__ void block_sum28(double (&v)[NSUM], double* lds /* [2][PB/64][NSUM] */, int& par, const int (&myEntry)[6],
+                                            double (&mine)[6], double& err) {
     constexpr int NW = PB / 64;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     cs_reduce_many<NSUM>(v, lane);
-    if (NW == 1) {
-        constexpr CsOwnerTable<NSUM> T{};
-        int owner = 0;   // the lane that holds the total of entry myEntry
-#pragma unroll
-        for (int q = 0; q < NSUM; ++q) owner = myEntry == q ? T.lane[q] : owner;
-        mine = cs_shfl_d(v[0], owner);
-        err = cs_readlane_d(v[0], T.lane[27]);
-        return;
-    }
     const int have = cs_reduce_index<NSUM>(lane);
     double* buf = lds + par * (NW * NSUM);
     par ^= 1;
     if (have >= 0) buf[wv * NSUM + have] = v[0];
     __syncthreads();
-    double s = buf[myEntry], e = buf[27];
+    double e = buf[27];
 #pragma unroll
-    for (int w = 1; w < NW; ++w) s += buf[w * NSUM + myEntry], e += buf[w * NSUM + 27];
-    mine = s, err = e;
+    for (int r = 0; r < 6; ++r) mine[r] = buf[myEntry[r]];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+#pragma unroll
+        for (int r = 0; r < 6; ++r) mine[r] += buf[w * NSUM + myEntry[r]];
+        e += buf[w * NSUM + 27];
+    }
+    err = e;
 }
 
 // ONE pass over the points at the pose (R, t): acc[0..20] the upper triangle of sum J^T J, acc[21..26] sum J^T r
@@ -201,7 +99,7 @@ __device__ __forceinline__ void block_sum28(double (&v)[NSUM], double* lds /* [2
 // step is ONE pass and ONE reduction.  reweight: first the Tukey weights from the residuals at (R, t) (:687-701), which is where
 // the reference computes them: at the pose the next round starts from.
 template <int PB>
-__device__ void lm_pass(const PoseCtx& c, const double* R, const double* t, bool reweight, double tau, int& par, double& mine, double& err) {
+__device__ void lm_pass(const PoseCtx& c, const double* R, const double* t, bool reweight, double tau, int& par, double (&mine)[6], double& err) {
     const double eps = 1e-8;
     // The forward differences are SCALED by 1e8 where the reference divides by 1e-8 (:271-287): 12 of a point's 26 f64 divisions per pass
     // (each ~30 instructions with a quarter-rate reciprocal) become multiplications -- at most 1 ulp per Jacobian entry, the size of what
@@ -209,8 +107,9 @@ __device__ void lm_pass(const PoseCtx& c, const double* R, const double* t, bool
     const double ieps = 1e8;
     // the perturbed rotations R * exp(eps e_k) do not depend on the point (:57-59)
     double R1[3][9];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) mat33AB(R, c.dR[a], R1[a]);
+    mat33_perturbed<0>(R, R1[0]);
+    mat33_perturbed<1>(R, R1[1]);
+    mat33_perturbed<2>(R, R1[2]);
     double acc[NSUM];
 #pragma unroll
     for (int q = 0; q < NSUM; ++q) acc[q] = 0;
@@ -260,10 +159,13 @@ __device__ void lm_pass(const PoseCtx& c, const double* R, const double* t, bool
     block_sum28<PB>(acc, c.red, par, c.myEntry, mine, err);
 }
 
-// (sum J^T J + lambda I) p = sum J^T r, the lane's entry of [A | B] in `mine`
-__device__ __forceinline__ void lm_solve(double mine, double lambda, double* param) {
-    const int lane = threadIdx.x & 63, r = lane / 7, j = lane - 7 * r;
-    solve66_lanes(r == j ? mine + lambda : mine, lane, param);
+// (sum J^T J + lambda I) p = sum J^T r, the lane's column of [A | B] in `mine`
+__device__ __forceinline__ void lm_solve(const double (&mine)[6], double lambda, double* param) {
+    const int lane = threadIdx.x & 63;
+    double col[6];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) col[r] = r == lane ? mine[r] + lambda : mine[r];
+    solve66_lanes(col, lane, param);
 }
 
 __device__ __forceinline__ void update_pose(const double* R, const double* t, const double* p, double* Rn, double* tn) {
@@ -279,7 +181,7 @@ template <int PB>
 __device__ bool weighted_lm(const PoseCtx& c, const double* R0, const double* t0, double* R_opt, double* t_opt,
                             cs_pose_option& opt, bool reweight, double tau, int& par) {  // :475-549
     double param[6];
-    double ne, cand, err;   // this lane's entry of the normal equations at the accepted pose / at the tentative one
+    double ne[6], cand[6], err;   // this lane's column of the normal equations at the accepted pose / at the tentative one
     opt.npts = c.npts;
     opt.lambda = opt.lambda0;
     lm_pass<PB>(c, R0, t0, reweight, tau, par, ne, err);
@@ -311,7 +213,8 @@ __device__ bool weighted_lm(const PoseCtx& c, const double* R0, const double* t0
             for (int q = 0; q < 9; ++q) R[q] = R_tmp[q] = R_opt[q];
 #pragma unroll
             for (int q = 0; q < 3; ++q) t[q] = t_tmp[q] = t_opt[q];
-            ne = cand;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) ne[q] = cand[q];
             opt.err = err;
             opt.lambda /= 10;
         } else {
@@ -366,14 +269,9 @@ __global__ __launch_bounds__(PB) CS_IC_ATTR void k_intracam(int ptsStride, const
     c.ms = msAll + (size_t)2 * ptsStride * pb;
     c.npts = npts;
     c.red = red;
-    c.myEntry = solve_entry_of_lane(threadIdx.x & 63);
-    c.Ws = wsScratch ? (wsScratch + (size_t)ptsStride * pb) : WsL;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        double w[3] = {0, 0, 0};
-        w[a] = 1e-8;
-        so3_exp(w, c.dR[a]);
-    }
+    for (int r = 0; r < 6; ++r) c.myEntry[r] = solve66_entry(r, min((int)(threadIdx.x & 63), 6));   // (lanes >= 7: any valid entry)
+    c.Ws = wsScratch ? (wsScratch + (size_t)ptsStride * pb) : WsL;
     if ((int)threadIdx.x < npts) {
         const int i = threadIdx.x;
         c.pM[0] = c.Ms[3 * i], c.pM[1] = c.Ms[3 * i + 1], c.pM[2] = c.Ms[3 * i + 2], c.pm[0] = c.ms[2 * i], c.pm[1] = c.ms[2 * i + 1];
