@@ -45,6 +45,7 @@ struct MmJob {
     const double *xy1, *xy2;   // 2N each: x[N] then y[N]
     const double* seeds;       // [nSeeds][4], device
     int nSeeds, out;           // out: the job's row of the outputs
+    int flags;                 // CS_MERGE_MATCH_SKIPPED | CS_MERGE_MATCH_SEEDS_OVERFLOW (k_mm_front_jobs): the job has no candidates
 };
 struct MmArgs {
     const MmJob* jobs;
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(MM_T) void k_merge_match(MmArgs A) {
     unsigned* const ij0 = A.liveIJ + jb * 2 * A.pairCap;
     __shared__ int sCnt[4];            // entries of list 0, of list 1, winners
 
-    const int total = *J.pairCount;
+    const int total = J.flags ? 0 : *J.pairCount;
     const int n = total < 0 ? 0 : (total < A.pairCap ? total : A.pairCap);
     for (int i = tid; i < N; i += MM_T) {
         rowBest[i] = 0, colBest[i] = 0, rowTie[i] = INT_MAX, colTie[i] = INT_MAX, rowMatch[i] = -1, colMatch[i] = -1, rowSeed[i] = -2;
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(MM_T) void k_merge_match(MmArgs A) {
     if (tid == 0) {
         int* c = A.counts + 4 * (size_t)J.out;
         c[0] = nWin < A.maxMatches ? nWin : A.maxMatches;
-        c[1] = (total > A.pairCap ? CS_MERGE_MATCH_PAIRS_OVERFLOW : 0) | (nWin > A.maxMatches ? CS_MERGE_MATCH_MATCHES_OVERFLOW : 0);
+        c[1] = J.flags | (total > A.pairCap ? CS_MERGE_MATCH_PAIRS_OVERFLOW : 0) | (nWin > A.maxMatches ? CS_MERGE_MATCH_MATCHES_OVERFLOW : 0);
         c[2] = total, c[3] = rounds;
     }
 }
@@ -276,6 +277,59 @@ __global__ __launch_bounds__(256) void k_mm_prep(MmPrepArgs A) {
     A.valid[(size_t)c * A.N + i] = ok ? 1 : 0;
 }
 
+// ---- the jobs of cs_merge_match_run_front_dev: from the front's result records and seed rows, all in device memory ------------------
+// A thread per job.  Skipped (surfNum < minSurfNum or no E) or more inliers than seed rows the handle or the front's block holds: the
+// flag, no seeds, and an F of NaN -- k_ncc_epi_mat's `epiErr <= epiMax` is then false for every pair, so the job has no candidates.
+// Otherwise F = iK1^T E^T iK2 in cs_merge_match_fmat's operation order (this file is compiled with contraction off), and the seed rows
+// are read where the front left them.
+struct MmFrontArgs {
+    const cs_merge_front_result* results;
+    const double* seeds;          // [..][seedRows][4]
+    const int2* cams;             // [nJobs] {iCam, jCam}
+    const double* iK;             // [nCams][9]
+    cs_merge_match_front_job* rec;   // [CS_MERGE_MATCH_MAX_JOBS]
+    MmJob* jobs;                  // [CS_MERGE_MATCH_MAX_JOBS]
+    const cs_ncc_pair* pairs;
+    const int* pairCount;
+    const double* xs;
+    int nJobs, seedRows, minSurfNum, maxSeeds, maxJobs, pairCap, N;
+};
+__global__ __launch_bounds__(256) void k_mm_front_jobs(MmFrontArgs A) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= A.nJobs) return;
+    const cs_merge_front_result r = A.results[k];
+    const int2 cam = A.cams[k];
+    int flags = 0;
+    if (r.surfNum < A.minSurfNum || !r.ematOk)
+        flags = CS_MERGE_MATCH_SKIPPED;
+    else if (r.inlierNum > A.maxSeeds || r.inlierNum > A.seedRows)
+        flags = CS_MERGE_MATCH_SEEDS_OVERFLOW;
+    double F[9];
+    if (flags) {
+        for (int q = 0; q < 9; ++q) F[q] = __longlong_as_double(0x7ff8000000000000ll);
+    } else {
+        const double *iK1 = A.iK + 9 * cam.x, *iK2 = A.iK + 9 * cam.y;
+        double T[9];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                double t = 0;
+                for (int q = 0; q < 3; ++q) t += iK1[3 * q + i] * r.E[3 * j + q];
+                T[3 * i + j] = t;
+            }
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) F[3 * i + j] = (T[3 * i] * iK2[j] + T[3 * i + 1] * iK2[3 + j]) + T[3 * i + 2] * iK2[6 + j];
+    }
+    const int nSeeds = flags || r.inlierNum < 0 ? 0 : r.inlierNum, slot = k % A.maxJobs;
+    cs_merge_match_front_job& R = A.rec[k];
+    for (int q = 0; q < 9; ++q) R.F[q] = F[q];
+    R.nSeeds = nSeeds, R.flags = flags;
+    MmJob J;
+    J.pairs = A.pairs + (size_t)slot * A.pairCap, J.pairCount = A.pairCount + slot;
+    J.xy1 = A.xs + (size_t)cam.x * 2 * A.N, J.xy2 = A.xs + (size_t)cam.y * 2 * A.N;
+    J.seeds = A.seeds + (size_t)k * A.seedRows * 4, J.nSeeds = nSeeds, J.out = k, J.flags = flags;
+    A.jobs[k] = J;
+}
+
 }  // namespace
 
 struct cs_merge_match {
@@ -286,6 +340,10 @@ struct cs_merge_match {
     double* xs;
     double* seeds;   // [maxJobs][maxSeeds][4]
     MmJob* jobs;     // [maxJobs]
+    MmJob* frontJobs;                      // [CS_MERGE_MATCH_MAX_JOBS]: k_mm_front_jobs' table
+    cs_merge_match_front_job* frontRec;    // [CS_MERGE_MATCH_MAX_JOBS]
+    int2* frontCams;                       // [CS_MERGE_MATCH_MAX_JOBS]
+    double* iK;                            // [nCams][9]
     MmArgs args;     // the tables (jobs / maxDisp are set per launch)
     CsStage stage;
 };
@@ -301,6 +359,7 @@ static void mm_layout(cs_merge_match* mm, CsArena& ar) {
     ar.take(A.rowBest, nT), ar.take(A.colBest, nT), ar.take(A.winKey, nT);
     ar.take(A.rowTie, nT), ar.take(A.colTie, nT), ar.take(A.rowMatch, nT), ar.take(A.colMatch, nT), ar.take(A.rowSeed, nT), ar.take(A.winIJ, nT);
     ar.take(mm->seeds, nJ * (size_t)(mm->maxSeeds > 0 ? mm->maxSeeds : 1) * 4), ar.take(mm->jobs, nJ);
+    ar.take(mm->frontJobs, nO), ar.take(mm->frontRec, nO), ar.take(mm->frontCams, nO), ar.take(mm->iK, (size_t)mm->nCams * 9);
     ar.take(A.matches, nO * mm->maxMatches * 2), ar.take(A.scores, nO * mm->maxMatches), ar.take(A.counts, nO * 4);
 }
 
@@ -404,6 +463,45 @@ extern "C" int cs_merge_match_from_pairs_dev(cs_merge_match* mm, void* hip_strea
     return mm_launch(mm, s, nJobs, jobs.data(), ns.data(), seeds, maxDisp);
 }
 
+// the cameras of a call: refused when a table is missing, else the cutter's / candidate kernel's view of them
+static int mm_cams(cs_merge_match* mm, const char* who, const cs_merge_match_cam* cams, cs_ncc_cam* nc) {
+    const int nC = mm->nCams, N = mm->N;
+    memset(nc, 0, sizeof(cs_ncc_cam) * MM_MAX_CAMS);
+    for (int c = 0; c < nC; ++c) {
+        if (!cams[c].xy || !cams[c].state || !cams[c].K || !cams[c].imgSmall || !(cams[c].imgScale > 0)) {
+            cs_set_error("%s: camera %d: null xy / state / K / imgSmall, or imgScale %g", who, c, cams[c].imgScale);
+            return CS_ERR_INVALID;
+        }
+        nc[c].img = cams[c].imgSmall, nc[c].x = mm->xs + (size_t)c * 2 * N, nc[c].y = nc[c].x + N;
+        nc[c].blocks = (unsigned char*)mm->b.blocks + (size_t)c * N * 128, nc[c].abc = (double*)mm->b.abc + (size_t)c * N * 4;
+        nc[c].valid = (int*)mm->b.valid + (size_t)c * N;
+    }
+    return CS_OK;
+}
+
+// the mask and the positions, then every slot's block
+static int mm_blocks(cs_merge_match* mm, void* hip_stream, const cs_merge_match_cam* cams, const cs_ncc_cam* nc, int Ws, int Hs) {
+    const int nC = mm->nCams, N = mm->N;
+    hipStream_t s = (hipStream_t)hip_stream;
+    MmPrepArgs P;
+    memset(&P, 0, sizeof(P));
+    for (int c = 0; c < nC; ++c) P.xy[c] = cams[c].xy, P.state[c] = cams[c].state;
+    P.xs = mm->xs, P.valid = (int*)mm->b.valid, P.N = N;
+    hipLaunchKernelGGL(k_mm_prep, dim3((N + 255) / 256, nC), dim3(256), 0, s, P);
+    CS_CHECK_LAUNCH();
+    bool cut[MM_MAX_CAMS] = {false};
+    for (int c = 0; c < nC; ++c) {   // the cutter takes one scale a launch: one launch per DISTINCT imgScale (KeyPose::imgScale is per camera)
+        if (cut[c]) continue;
+        cs_ncc_cam sub[MM_MAX_CAMS];
+        int nSub = 0;
+        for (int d = c; d < nC; ++d)
+            if (!cut[d] && cams[d].imgScale == cams[c].imgScale) sub[nSub++] = nc[d], cut[d] = true;
+        const int rc = cs_ncc_get_scaled_blocks_group_dev(mm->device, hip_stream, nSub, sub, Ws, Hs, N, cams[c].imgScale);
+        if (rc != CS_OK) return rc;
+    }
+    return CS_OK;
+}
+
 extern "C" int cs_merge_match_run_dev(cs_merge_match* mm, void* hip_stream, const cs_merge_match_cam* cams, int Ws, int Hs, int nJobs,
                                       const cs_merge_match_job* jobs, double epiMax, double nccMin, double maxDisp) {
     const char* who = "cs_merge_match_run_dev";
@@ -412,20 +510,8 @@ extern "C" int cs_merge_match_run_dev(cs_merge_match* mm, void* hip_stream, cons
         return CS_ERR_INVALID;
     }
     const int nC = mm->nCams, N = mm->N;
-    MmPrepArgs P;
-    memset(&P, 0, sizeof(P));
     cs_ncc_cam nc[MM_MAX_CAMS];
-    memset(nc, 0, sizeof(nc));
-    for (int c = 0; c < nC; ++c) {
-        if (!cams[c].xy || !cams[c].state || !cams[c].K || !cams[c].imgSmall || !(cams[c].imgScale > 0)) {
-            cs_set_error("%s: camera %d: null xy / state / K / imgSmall, or imgScale %g", who, c, cams[c].imgScale);
-            return CS_ERR_INVALID;
-        }
-        P.xy[c] = cams[c].xy, P.state[c] = cams[c].state;
-        nc[c].img = cams[c].imgSmall, nc[c].x = mm->xs + (size_t)c * 2 * N, nc[c].y = nc[c].x + N;
-        nc[c].blocks = (unsigned char*)mm->b.blocks + (size_t)c * N * 128, nc[c].abc = (double*)mm->b.abc + (size_t)c * N * 4;
-        nc[c].valid = (int*)mm->b.valid + (size_t)c * N;
-    }
+    if (mm_cams(mm, who, cams, nc) != CS_OK) return CS_ERR_INVALID;
     std::vector<cs_ncc_pair_job> pj((size_t)nJobs);
     for (int k = 0; k < nJobs; ++k) {
         const cs_merge_match_job& q = jobs[k];
@@ -444,19 +530,8 @@ extern "C" int cs_merge_match_run_dev(cs_merge_match* mm, void* hip_stream, cons
     CS_HIP(hipSetDevice(mm->device));
     int rc = mm->stage.begin(s);
     if (rc != CS_OK) return rc;
-    P.xs = mm->xs, P.valid = (int*)mm->b.valid, P.N = N;
-    hipLaunchKernelGGL(k_mm_prep, dim3((N + 255) / 256, nC), dim3(256), 0, s, P);
-    CS_CHECK_LAUNCH();
-    bool cut[MM_MAX_CAMS] = {false};
-    for (int c = 0; c < nC; ++c) {   // the cutter takes one scale a launch: one launch per DISTINCT imgScale (KeyPose::imgScale is per camera)
-        if (cut[c]) continue;
-        cs_ncc_cam sub[MM_MAX_CAMS];
-        int nSub = 0;
-        for (int d = c; d < nC; ++d)
-            if (!cut[d] && cams[d].imgScale == cams[c].imgScale) sub[nSub++] = nc[d], cut[d] = true;
-        rc = cs_ncc_get_scaled_blocks_group_dev(mm->device, hip_stream, nSub, sub, Ws, Hs, N, cams[c].imgScale);
-        if (rc != CS_OK) return rc;
-    }
+    rc = mm_blocks(mm, hip_stream, cams, nc, Ws, Hs);
+    if (rc != CS_OK) return rc;
     const size_t seedDoubles = (size_t)(mm->maxSeeds > 0 ? mm->maxSeeds : 1) * 4;
     for (int k0 = 0; k0 < nJobs; k0 += mm->maxJobs) {   // a batch: its candidate lists, then its matcher
         const int nb = nJobs - k0 < mm->maxJobs ? nJobs - k0 : mm->maxJobs;
@@ -476,6 +551,86 @@ extern "C" int cs_merge_match_run_dev(cs_merge_match* mm, void* hip_stream, cons
         rc = mm_launch(mm, s, nb, mj.data(), ns.data(), sp.data(), maxDisp);
         if (rc != CS_OK) return rc;
     }
+    return CS_OK;
+}
+
+extern "C" int cs_merge_match_run_front_dev(cs_merge_match* mm, void* hip_stream, const cs_merge_match_cam* cams, int Ws, int Hs, int nJobs,
+                                            const cs_merge_front_job* pairs, const cs_merge_front_result* d_results, const double* d_seeds,
+                                            int seedRowsPerJob, int minSurfNum, double epiMax, double nccMin, double maxDisp) {
+    const char* who = "cs_merge_match_run_front_dev";
+    if (!mm || !cams || Ws < 1 || Hs < 1 || nJobs < 0 || nJobs > CS_MERGE_MATCH_MAX_JOBS ||
+        (nJobs > 0 && (!pairs || !d_results || !d_seeds || seedRowsPerJob < 1))) {
+        cs_set_error("%s: bad arguments (%d jobs of at most %d, small image %d x %d, %d seed rows per job)", who, nJobs, CS_MERGE_MATCH_MAX_JOBS, Ws,
+                     Hs, seedRowsPerJob);
+        return CS_ERR_INVALID;
+    }
+    const int nC = mm->nCams, N = mm->N;
+    cs_ncc_cam nc[MM_MAX_CAMS];
+    if (mm_cams(mm, who, cams, nc) != CS_OK) return CS_ERR_INVALID;
+    std::vector<double> iK((size_t)nC * 9, 0.0);   // of the cameras a job names: host-computed, as cs_merge_match_fmat inverts them
+    std::vector<char> have((size_t)nC, 0);
+    std::vector<int2> jc((size_t)nJobs);
+    std::vector<cs_ncc_pair_job> pj((size_t)nJobs);
+    for (int k = 0; k < nJobs; ++k) {
+        const int a = pairs[k].iCam, b = pairs[k].jCam;
+        if (a < 0 || a >= nC || b < 0 || b >= nC || a == b) {
+            cs_set_error("%s: job %d: cameras %d / %d of %d", who, k, a, b, nC);
+            return CS_ERR_INVALID;
+        }
+        for (int c : {a, b})
+            if (!have[c]) {
+                if (!cs_host_inv33(cams[c].K, &iK[9 * (size_t)c])) {
+                    cs_set_error("%s: job %d: singular K of camera %d", who, k, c);
+                    return CS_ERR_INVALID;
+                }
+                have[c] = 1;
+            }
+        jc[k] = make_int2(a, b);
+        const int slot = k % mm->maxJobs;
+        memset(&pj[k], 0, sizeof(pj[k]));
+        pj[k].camA = a, pj[k].camB = b, pj[k].dF = mm->frontRec[k].F;   // (an address: the record is in device memory)
+        pj[k].pairs = (cs_ncc_pair*)mm->b.pairs + (size_t)slot * mm->pairCap, pj[k].count = (int*)mm->b.pairCount + slot;
+    }
+    if (nJobs == 0) return CS_OK;
+    hipStream_t s = (hipStream_t)hip_stream;
+    CS_HIP(hipSetDevice(mm->device));
+    int rc = mm->stage.begin(s);
+    if (rc != CS_OK) return rc;
+    if ((rc = mm->stage.upload(s, mm->iK, iK.data(), sizeof(double) * iK.size())) != CS_OK) return rc;
+    if ((rc = mm->stage.upload(s, mm->frontCams, jc.data(), sizeof(int2) * jc.size())) != CS_OK) return rc;
+    MmFrontArgs FA;
+    FA.results = d_results, FA.seeds = d_seeds, FA.cams = mm->frontCams, FA.iK = mm->iK, FA.rec = mm->frontRec, FA.jobs = mm->frontJobs;
+    FA.pairs = (const cs_ncc_pair*)mm->b.pairs, FA.pairCount = (const int*)mm->b.pairCount, FA.xs = mm->xs;
+    FA.nJobs = nJobs, FA.seedRows = seedRowsPerJob, FA.minSurfNum = minSurfNum, FA.maxSeeds = mm->maxSeeds, FA.maxJobs = mm->maxJobs;
+    FA.pairCap = mm->pairCap, FA.N = N;
+    hipLaunchKernelGGL(k_mm_front_jobs, dim3((nJobs + 255) / 256), dim3(256), 0, s, FA);
+    CS_CHECK_LAUNCH();
+    rc = mm_blocks(mm, hip_stream, cams, nc, Ws, Hs);
+    if (rc != CS_OK) return rc;
+    for (int k0 = 0; k0 < nJobs; k0 += mm->maxJobs) {   // a batch: its candidate lists, then its matcher on the device-filled table
+        const int nb = nJobs - k0 < mm->maxJobs ? nJobs - k0 : mm->maxJobs;
+        for (int e0 = 0; e0 < nb; e0 += MM_EPI_JOBS) {
+            const int ne = nb - e0 < MM_EPI_JOBS ? nb - e0 : MM_EPI_JOBS;
+            rc = cs_ncc_epi_pairs_group_dev(mm->device, hip_stream, nC, nc, N, ne, pj.data() + k0 + e0, epiMax, nccMin, mm->pairCap);
+            if (rc != CS_OK) return rc;
+        }
+        MmArgs A = mm->args;
+        A.jobs = mm->frontJobs + k0, A.maxDisp = maxDisp;
+        hipLaunchKernelGGL(k_merge_match, dim3(nb), dim3(MM_T), 0, s, A);
+        CS_CHECK_LAUNCH();
+    }
+    return CS_OK;
+}
+
+extern "C" int cs_merge_match_front_jobs(cs_merge_match* mm, void* hip_stream, int nJobs, cs_merge_match_front_job* h_out) {
+    if (!mm || nJobs < 0 || nJobs > CS_MERGE_MATCH_MAX_JOBS || (nJobs > 0 && !h_out)) {
+        cs_set_error("cs_merge_match_front_jobs: bad arguments");
+        return CS_ERR_INVALID;
+    }
+    CS_HIP(hipSetDevice(mm->device));
+    if (nJobs > 0)
+        CS_HIP(hipMemcpyAsync(h_out, mm->frontRec, sizeof(cs_merge_match_front_job) * (size_t)nJobs, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
+    CS_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
     return CS_OK;
 }
 

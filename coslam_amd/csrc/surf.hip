@@ -18,6 +18,12 @@ constexpr int SF_ORI = CS_SURF_ORI_SAMPLES, SF_WIN = CS_SURF_ORI_WINDOWS;
 constexpr double SF_TWO_PI = 2.0 * 3.141592653589793;
 constexpr double SF_WIN_STEP = 3.141592653589793 / 36.0, SF_WIN_WIDTH = 3.141592653589793 / 3.0;
 typedef unsigned long long sf_u64;
+constexpr int SF_SEL_PASSES = 8;          // a 64-bit key, 8 bits a pass, from the top
+struct SfSel {
+    sf_u64 prefix;   // the cut's digits so far, in place
+    int need;        // keys to keep among those that share the prefix; <= 0: the camera keeps everything (total <= maxPts)
+    int bin;         // keys in the digit the last pass chose
+};
 
 struct SurfArgs {
     const unsigned char* img[SF_MAX_CAMS];
@@ -38,6 +44,14 @@ struct SurfArgs {
     int mapW[CS_SURF_MAX_OCTAVES], mapH[CS_SURF_MAX_OCTAVES], mapOff[SF_NL], layerSize[SF_NL], layerFits[SF_NL];
     int grpStart[SF_MAX_GROUPS + 1], grpO[SF_MAX_GROUPS], grpM[SF_MAX_GROUPS], grpMargin[SF_MAX_GROUPS];
     double thr;
+    // the strongest-first choice (CS_SURF_KEEP_STRONGEST); dropped is null in CS_SURF_KEEP_FIRST and nothing below is touched then
+    unsigned* selHist;        // [nCams][SF_SEL_PASSES][256]: digit counts of the candidates' keys, zeroed by the call
+    struct SfSel* selState;   // [nCams][SF_SEL_PASSES + 1]: the select in front of pass p (entry 0 is never stored: {0, maxPts})
+    int* nWork;               // [nCams]: blocks that hold a candidate, zeroed by the call
+    int* tieCnt;              // [nCams][nBlocks]: candidates AT the cut per block, zeroed by the call (selHist, nWork and this are one range)
+    int* tieOff;              // [nCams][nBlocks]: ... and in front of the block
+    int* workList;            // [nCams][nBlocks]: those blocks, in no order
+    int* dropped;             // [nCams]: total - maxPts where the select ran, else 0
 };
 
 __device__ __forceinline__ const unsigned* sf_integral(const SurfArgs& A, int c) {
@@ -195,17 +209,157 @@ __global__ __launch_bounds__(SF_T) void k_surf_maxima(SurfArgs A) {
     if (tid == 0) A.blockCnt[(size_t)c * A.nBlocks + blk] = (sCnt[0] + sCnt[1]) + (sCnt[2] + sCnt[3]);
 }
 
+// ---- the strongest-first choice (CS_SURF_KEEP_STRONGEST), between the maxima and the scan ---------------------------------------------
+// A radix select over the candidates' responses, all cameras in each launch.  The first pass runs over every block: it counts the top 8
+// bits of the keys and lists the blocks that hold a candidate (the WORK LIST; its order is the order of arrival and nothing reads it as
+// an order).  The seven passes behind it, SF_SEL_GRID workgroups a camera over the work list, count the next 8 bits of the keys that share
+// the cut's digits so far (integer atomics: the counts do not depend on the order of arrival); every workgroup reads the previous pass's
+// 256 counts and settles that digit itself, so no pass waits for a deciding launch, and workgroup 0 of a camera stores what it settled for
+// the next launch to start from.  Then the candidates AT the cut are counted per block, scanned, and the flags and block counts are
+// rewritten: above the cut, or at it and among the first `need` in list order.  k_surf_scan / k_surf_scatter see a list of exactly
+// maxPts.  A camera with total <= maxPts is left alone (need = 0 after the first pass).
+constexpr int SF_SEL_GRID = 64;
+
+// larger response <-> larger key, as unsigned integers (a candidate's response is above the threshold >= 0; the rule holds for any double)
+__device__ __forceinline__ sf_u64 sf_key(double v) {
+    const sf_u64 b = (sf_u64)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+
+// the key of the thread's sample when it is flagged
+__device__ __forceinline__ bool sf_candidate(const SurfArgs& A, int c, int blk, int tid, sf_u64& key) {
+    SfSample S;
+    if (!A.flag[(size_t)c * A.nFlat + (size_t)blk * SF_T + tid] || !sf_sample(A, c, blk, tid, S)) return false;
+    key = sf_key(S.N1[S.i * S.mw + S.j]);
+    return true;
+}
+
+__global__ __launch_bounds__(SF_T) void k_surf_sel_first(SurfArgs A) {
+    const int c = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
+    if (!A.img[c] || A.blockCnt[(size_t)c * A.nBlocks + blk] == 0) return;   // (uniform)
+    if (tid == 0) A.workList[(size_t)c * A.nBlocks + atomicAdd(&A.nWork[c], 1)] = blk;
+    sf_u64 key;
+    if (sf_candidate(A, c, blk, tid, key)) atomicAdd(&A.selHist[((size_t)c * SF_SEL_PASSES) * 256 + (int)(key >> 56)], 1u);
+}
+
+// The digit of pass p - 1 from its counts and the select in front of it: the digit d with fewer than `need` keys above it and at least
+// `need` with its own.  The whole workgroup calls this (thread t owns digit t); every thread gets the result, workgroup 0 stores it.
+__device__ SfSel sf_sel_decide(const SurfArgs& A, int c, int p) {
+    __shared__ int sW[SF_T / 64];
+    __shared__ SfSel sOut;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    SfSel st;
+    if (p == 1)
+        st.prefix = 0, st.need = A.maxPts, st.bin = 0;
+    else
+        st = A.selState[(size_t)c * (SF_SEL_PASSES + 1) + (p - 1)];
+    if (st.need > 0) {   // (uniform)
+        const int h = (int)A.selHist[((size_t)c * SF_SEL_PASSES + (p - 1)) * 256 + tid];
+        int inc = h;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += o;
+        }
+        if (lane == 63) sW[w] = inc;
+        __syncthreads();
+        for (int k = 0; k < w; ++k) inc += sW[k];
+        const int total = (sW[0] + sW[1]) + (sW[2] + sW[3]), above = total - inc;
+        if (tid == 0) sOut.prefix = st.prefix, sOut.need = 0, sOut.bin = 0;   // the first pass of a camera with total <= maxPts: no digit
+        __syncthreads();
+        if (!(p == 1 && total <= st.need) && above < st.need && above + h >= st.need)   // one thread
+            sOut.prefix = st.prefix | ((sf_u64)tid << (64 - 8 * p)), sOut.need = st.need - above, sOut.bin = h;
+        __syncthreads();
+        st = sOut;
+        if (p == 1 && tid == 0 && blockIdx.x == 0) A.dropped[c] = st.need > 0 ? total - A.maxPts : 0;
+    }
+    if (blockIdx.x == 0 && tid == 0) A.selState[(size_t)c * (SF_SEL_PASSES + 1) + p] = st;
+    return st;
+}
+
+__global__ __launch_bounds__(SF_T) void k_surf_sel_hist(SurfArgs A, int p) {   // p = 1 .. SF_SEL_PASSES - 1
+    const int c = blockIdx.y, tid = threadIdx.x;
+    if (!A.img[c]) return;
+    const SfSel st = sf_sel_decide(A, c, p);
+    if (st.need <= 0) return;   // (uniform)
+    const int nWork = A.nWork[c], shift = 56 - 8 * p;
+    for (int w = blockIdx.x; w < nWork; w += SF_SEL_GRID) {
+        sf_u64 key;
+        if (sf_candidate(A, c, A.workList[(size_t)c * A.nBlocks + w], tid, key) && (key >> (shift + 8)) == (st.prefix >> (shift + 8)))
+            atomicAdd(&A.selHist[((size_t)c * SF_SEL_PASSES + p) * 256 + (int)((key >> shift) & 255)], 1u);
+    }
+}
+
+// the last digit, and the candidates AT the cut per block, only where some of them have to go (the other blocks' counts are the call's zeros)
+__global__ __launch_bounds__(SF_T) void k_surf_sel_ties(SurfArgs A) {
+    __shared__ int sCnt[SF_T / 64];
+    const int c = blockIdx.y, tid = threadIdx.x;
+    if (!A.img[c]) return;
+    const SfSel st = sf_sel_decide(A, c, SF_SEL_PASSES);
+    if (st.need <= 0 || st.bin == st.need) return;   // (uniform)
+    const int nWork = A.nWork[c];
+    for (int w = blockIdx.x; w < nWork; w += SF_SEL_GRID) {
+        const int blk = A.workList[(size_t)c * A.nBlocks + w];
+        sf_u64 key;
+        const bool tie = sf_candidate(A, c, blk, tid, key) && key == st.prefix;
+        const sf_u64 bal = __ballot(tie);
+        if ((tid & 63) == 0) sCnt[tid >> 6] = __popcll(bal);
+        __syncthreads();
+        if (tid == 0) A.tieCnt[(size_t)c * A.nBlocks + blk] = (sCnt[0] + sCnt[1]) + (sCnt[2] + sCnt[3]);
+        __syncthreads();
+    }
+}
+
+__device__ int sf_scan_blocks(const int* cnt, int* off, int nB);   // (below, with k_surf_scan)
+
+__global__ __launch_bounds__(SF_T) void k_surf_sel_tiescan(SurfArgs A) {
+    const int c = blockIdx.x;
+    if (!A.img[c]) return;
+    const SfSel st = A.selState[(size_t)c * (SF_SEL_PASSES + 1) + SF_SEL_PASSES];
+    if (st.need <= 0 || st.bin == st.need) return;   // (uniform)
+    sf_scan_blocks(A.tieCnt + (size_t)c * A.nBlocks, A.tieOff + (size_t)c * A.nBlocks, A.nBlocks);
+}
+
+// the flags and block counts of the kept candidates: above the cut, or at it and among the first `need` of those in list order
+__global__ __launch_bounds__(SF_T) void k_surf_sel_reflag(SurfArgs A) {
+    __shared__ int sTie[SF_T / 64], sKeep[SF_T / 64];
+    const int c = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (!A.img[c]) return;
+    const SfSel st = A.selState[(size_t)c * (SF_SEL_PASSES + 1) + SF_SEL_PASSES];
+    if (st.need <= 0) return;   // (uniform)
+    const int nWork = A.nWork[c];
+    for (int w = blockIdx.x; w < nWork; w += SF_SEL_GRID) {
+        const int blk = A.workList[(size_t)c * A.nBlocks + w];
+        sf_u64 key = 0;
+        const bool cand = sf_candidate(A, c, blk, tid, key), tie = cand && key == st.prefix;
+        const sf_u64 balT = __ballot(tie);
+        if (lane == 0) sTie[wv] = __popcll(balT);
+        __syncthreads();
+        bool keep = cand && key > st.prefix;
+        if (tie) {
+            int rank = __popcll(balT & ((1ull << lane) - 1));
+            for (int k = 0; k < wv; ++k) rank += sTie[k];
+            keep = st.bin == st.need || A.tieOff[(size_t)c * A.nBlocks + blk] + rank < st.need;
+        }
+        if (cand && !keep) A.flag[(size_t)c * A.nFlat + (size_t)blk * SF_T + tid] = 0;
+        const sf_u64 balK = __ballot(keep);
+        if (lane == 0) sKeep[wv] = __popcll(balK);
+        __syncthreads();
+        if (tid == 0) A.blockCnt[(size_t)c * A.nBlocks + blk] = (sKeep[0] + sKeep[1]) + (sKeep[2] + sKeep[3]);
+        __syncthreads();
+    }
+}
+
 // ---- the order: an exclusive scan of the block counts per camera (one workgroup each), then every block places its own key points -----
-__global__ __launch_bounds__(SF_T) void k_surf_scan(SurfArgs A) {
+// off[b] = cnt[0] + .. + cnt[b - 1] for the nB blocks of a camera, by one workgroup -> the total (in every thread)
+__device__ int sf_scan_blocks(const int* cnt, int* off, int nB) {
     __shared__ int sW[SF_T / 64];
     __shared__ int sBase;
-    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if (tid == 0) sBase = 0;
     __syncthreads();
-    const int nB = A.img[c] ? A.nBlocks : 0;
     for (int b0 = 0; b0 < nB; b0 += SF_T) {
         const int b = b0 + tid;
-        const int v = b < nB ? A.blockCnt[(size_t)c * A.nBlocks + b] : 0;
+        const int v = b < nB ? cnt[b] : 0;
         int inc = v;
         for (int d = 1; d < 64; d <<= 1) {
             const int o = __shfl_up(inc, d, 64);
@@ -215,14 +369,20 @@ __global__ __launch_bounds__(SF_T) void k_surf_scan(SurfArgs A) {
         __syncthreads();
         int pre = sBase;
         for (int k = 0; k < w; ++k) pre += sW[k];
-        if (b < nB) A.blockOff[(size_t)c * A.nBlocks + b] = pre + inc - v;
+        if (b < nB) off[b] = pre + inc - v;
         __syncthreads();
         if (tid == 0) sBase += (sW[0] + sW[1]) + (sW[2] + sW[3]);
         __syncthreads();
     }
-    if (tid == 0) {
-        const int total = sBase, n = total < A.maxPts ? total : A.maxPts;
-        A.count[c] = n, A.overflow[c] = total - n;
+    return sBase;
+}
+
+__global__ __launch_bounds__(SF_T) void k_surf_scan(SurfArgs A) {
+    const int c = blockIdx.x;
+    const int total = sf_scan_blocks(A.blockCnt + (size_t)c * A.nBlocks, A.blockOff + (size_t)c * A.nBlocks, A.img[c] ? A.nBlocks : 0);
+    if (threadIdx.x == 0) {
+        const int n = total < A.maxPts ? total : A.maxPts;
+        A.count[c] = n, A.overflow[c] = (total - n) + (A.dropped && A.img[c] ? A.dropped[c] : 0);
     }
 }
 
@@ -375,6 +535,7 @@ struct cs_surf {
     SurfArgs args;      // the tables; img, pitch and thr are the call's
     double *oriW, *oriGrid, *descW;
     int maxMap;         // samples of the largest layer map
+    int keep;           // CS_SURF_KEEP_FIRST | CS_SURF_KEEP_STRONGEST
     CsStage stage;
 };
 
@@ -387,6 +548,8 @@ static void sf_layout(cs_surf* sf, CsArena& ar) {
     ar.take(A.flag, nC * A.nFlat), ar.take(A.blockCnt, nC * A.nBlocks), ar.take(A.blockOff, nC * A.nBlocks);
     ar.take(A.pts, nP * 2), ar.take(A.desc, nP * A.dim), ar.take(A.size, nP), ar.take(A.angle, nP), ar.take(A.response, nP);
     ar.take(A.laplacian, nP), ar.take(A.octave, nP), ar.take(A.layer, nP), ar.take(A.cell, nP * 2), ar.take(A.count, nC), ar.take(A.overflow, nC);
+    ar.take(A.selHist, nC * SF_SEL_PASSES * 256), ar.take(A.nWork, nC), ar.take(A.tieCnt, nC * A.nBlocks);   // (zeroed as one range)
+    ar.take(A.tieOff, nC * A.nBlocks), ar.take(A.workList, nC * A.nBlocks), ar.take(A.selState, nC * (SF_SEL_PASSES + 1)), ar.take(A.dropped, nC);
 }
 
 extern "C" cs_surf* cs_surf_create(int device, int nCams, int W, int H, int maxPts, int nOctaves, int nOctaveLayers, int dimDesc) {
@@ -401,7 +564,7 @@ extern "C" cs_surf* cs_surf_create(int device, int nCams, int W, int H, int maxP
         return nullptr;
     }
     cs_surf* sf = new cs_surf();
-    sf->device = device, sf->base = nullptr, sf->bytes = 0, sf->maxMap = 0;
+    sf->device = device, sf->base = nullptr, sf->bytes = 0, sf->maxMap = 0, sf->keep = CS_SURF_KEEP_FIRST;
     SurfArgs& A = sf->args;
     memset(&A, 0, sizeof(A));
     cs_surf_buffers& B = sf->b;
@@ -484,6 +647,8 @@ int sf_run(const char* who, cs_surf* sf, void* hip_stream, const unsigned char* 
     }
     SurfArgs A = sf->args;
     const int nC = sf->b.nCams;
+    const bool strongest = sf->keep == CS_SURF_KEEP_STRONGEST && A.nBlocks > 0;
+    if (!strongest) A.dropped = nullptr;   // what k_surf_scan adds to the overflow
     for (int c = 0; c < nC; ++c) A.img[c] = d_img[c];
     A.pitch = pitch, A.thr = thr;
     hipStream_t s = (hipStream_t)hip_stream;
@@ -498,6 +663,21 @@ int sf_run(const char* who, cs_surf* sf, void* hip_stream, const unsigned char* 
     if (upTo == SF_LAYERS) return CS_OK;
     if (A.nBlocks > 0) {
         hipLaunchKernelGGL(k_surf_maxima, dim3(A.nBlocks, nC), dim3(SF_T), 0, s, A);
+        CS_CHECK_LAUNCH();
+    }
+    if (strongest) {
+        CS_HIP(hipMemsetAsync(A.selHist, 0, (size_t)((char*)(A.tieCnt + (size_t)nC * A.nBlocks) - (char*)A.selHist), s));
+        hipLaunchKernelGGL(k_surf_sel_first, dim3(A.nBlocks, nC), dim3(SF_T), 0, s, A);
+        CS_CHECK_LAUNCH();
+        for (int p = 1; p < SF_SEL_PASSES; ++p) {
+            hipLaunchKernelGGL(k_surf_sel_hist, dim3(SF_SEL_GRID, nC), dim3(SF_T), 0, s, A, p);
+            CS_CHECK_LAUNCH();
+        }
+        hipLaunchKernelGGL(k_surf_sel_ties, dim3(SF_SEL_GRID, nC), dim3(SF_T), 0, s, A);
+        CS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_surf_sel_tiescan, dim3(nC), dim3(SF_T), 0, s, A);
+        CS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_surf_sel_reflag, dim3(SF_SEL_GRID, nC), dim3(SF_T), 0, s, A);
         CS_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(k_surf_scan, dim3(nC), dim3(SF_T), 0, s, A);
@@ -538,6 +718,15 @@ extern "C" int cs_surf_layers_dev(cs_surf* sf, void* hip_stream, const unsigned 
 
 extern "C" int cs_surf_detect_dev(cs_surf* sf, void* hip_stream, const unsigned char* const* d_img, int pitch, double hessianThreshold) {
     return sf_run("cs_surf_detect_dev", sf, hip_stream, d_img, pitch, hessianThreshold, 1, SF_DETECT);
+}
+
+extern "C" int cs_surf_keep_set(cs_surf* sf, int keep) {
+    if (!sf || (keep != CS_SURF_KEEP_FIRST && keep != CS_SURF_KEEP_STRONGEST)) {
+        cs_set_error("cs_surf_keep_set: null handle, or keep %d is neither CS_SURF_KEEP_FIRST nor CS_SURF_KEEP_STRONGEST", keep);
+        return CS_ERR_INVALID;
+    }
+    sf->keep = keep;
+    return CS_OK;
 }
 
 extern "C" int cs_surf_counts(cs_surf* sf, void* hip_stream, int* count, int* overflow) {

@@ -623,14 +623,40 @@ class MergeCamGroups:
 
     def run_from_descriptors(self, front, front_cams, matcher, match_cams, Ws, Hs, infos, history, tables, groups, key_frames, self_motion,
                              key_groups, pixelErrVar, ratio=0.8, max_dist=0.6, n_ransac=200, max_epi_err=2.0, min_inlier_num=15, seed=0,
-                             epi_max=20.0, ncc_min=0.45, max_disp=150.0, last_release_frame=None, n_max_keyfrm=100, stream_ptr=None):
+                             epi_max=20.0, ncc_min=0.45, max_disp=150.0, last_release_frame=None, n_max_keyfrm=100, stream_ptr=None,
+                             device_jobs=False, min_surf_num=25):
         """mergeCamGroups from the gate's list and the key frames' key points + descriptors: MergeFront.run over every entry's camera pair
         (matchSURFPoints, computeEMat, getMatchedPts; DESIGN 3.25), then run_from_seeds with what it returned.  front: a MergeFront;
         front_cams: per camera dict(pts, desc: device pointers, n, K).  E and the seeds pass through the front's one read-back (the matcher's
-        job table takes them from host memory).  -> run_from_seeds' dict, plus front (MergeFront.run's list)."""
+        job table takes them from host memory).  -> run_from_seeds' dict, plus front (MergeFront.run's list).
+        device_jobs=True: front.enqueue -> matcher.run_front, the matcher's jobs filled on the device from the front's buffers, and ONE wait
+        (matcher.counts, then front.results without another): no seed rows come to the host.  Entry e is job e: match_counts is
+        [nEntries][4], job_of_entry[e] is e, or -1 for a skipped or seed-overflowed entry, and the front's records carry no `seeds`."""
         import torch
 
         s = _stream(self.device, stream_ptr)
+        if device_jobs:
+            pairs = [(int(inf[1]), int(inf[4])) for inf in infos]
+            front.enqueue(front_cams, pairs, ratio, max_dist, n_ransac, max_epi_err, min_inlier_num, seed, stream_ptr=s)
+            matcher.run_front(match_cams, Ws, Hs, pairs, front, min_surf_num, epi_max, ncc_min, max_disp, stream_ptr=s)
+            cnt = matcher.counts(len(infos), stream_ptr=s)          # the one wait
+            got = front.results(len(infos), stream_ptr=s)
+            skipped = [bool(cnt[e][1] & MERGE_MATCH_SKIPPED) for e in range(len(infos))]
+            job_of = [-1 if cnt[e][1] & (MERGE_MATCH_SKIPPED | MERGE_MATCH_SEEDS_OVERFLOW) else e for e in range(len(infos))]
+            ncc = [int(cnt[e][0]) for e in range(len(infos))]
+            elig = [1 if cnt[e][1] == 0 else 0 for e in range(len(infos))]
+            ok = [1 if (got[e]["emat_ok"] and not skipped[e]) else 0 for e in range(len(infos))]
+            rec = _camera_groups_record(groups)
+            choice = merge_match_select(infos, [g["surf_num"] for g in got], ok, ncc, [int(rec.num[g]) for g in range(MAX_CAMS)], elig)
+            if choice["status"] != 1:
+                return dict(status="no_pair", merged=False, choice=choice, match_counts=cnt, job_of_entry=job_of, front=got)
+            k = choice["entry"]
+            d_matches = torch.as_tensor(_DeviceInt32View(matcher.matches_ptr(k), int(cnt[k][0])), device=torch.device("cuda", self.device))
+            rep = self.run(history, tables, groups, key_frames, self_motion, key_groups,
+                           (choice["maxgId1"], choice["maxgId2"], choice["maxiCam"], choice["maxjCam"]), d_matches, pixelErrVar,
+                           last_release_frame=last_release_frame, n_max_keyfrm=n_max_keyfrm, stream_ptr=s)
+            rep.update(choice=choice, match_counts=cnt, job_of_entry=job_of, matches_ptr=matcher.matches_ptr(k), front=got)
+            return rep
         got = front.run(front_cams, [(int(inf[1]), int(inf[4])) for inf in infos], ratio, max_dist, n_ransac, max_epi_err, min_inlier_num, seed,
                         stream_ptr=s)
         rep = self.run_from_seeds(matcher, match_cams, Ws, Hs, infos, [g["surf_num"] for g in got], [g["emat_ok"] for g in got],
@@ -656,7 +682,7 @@ class MergeCamGroups:
 
 
 MERGE_MATCH_MAX_JOBS = 256
-MERGE_MATCH_PAIRS_OVERFLOW, MERGE_MATCH_MATCHES_OVERFLOW = 1, 2
+MERGE_MATCH_PAIRS_OVERFLOW, MERGE_MATCH_MATCHES_OVERFLOW, MERGE_MATCH_SKIPPED, MERGE_MATCH_SEEDS_OVERFLOW = 1, 2, 4, 8
 
 
 class MergeMatchCam(C.Structure):
@@ -669,6 +695,11 @@ class MergeMatchCam(C.Structure):
 class MergeMatchJob(C.Structure):
     _c_type_ = "cs_merge_match_job"
     _fields_ = [("iCam", C.c_int), ("jCam", C.c_int), ("E", C.c_double * 9), ("nSeeds", C.c_int), ("seeds", C.c_void_p)]
+
+
+class MergeMatchFrontJob(C.Structure):
+    _c_type_ = "cs_merge_match_front_job"
+    _fields_ = [("F", C.c_double * 9), ("nSeeds", C.c_int), ("flags", C.c_int)]
 
 
 class MergeMatchBuffers(C.Structure):
@@ -741,10 +772,7 @@ class MergeMatcher(_MergeHandle):
         self._create(device, self.n_cams, self.N, self.max_jobs, self.max_seeds, self.pair_cap, self.max_matches)
         self._keep = None
 
-    def run(self, cams, Ws, Hs, jobs, epi_max=20.0, ncc_min=0.45, max_disp=150.0, stream_ptr=None):
-        """cs_merge_match_run_dev.  cams: per camera a dict xy, state, imgSmall (device pointers), K (9 doubles, HOST array), imgScale;
-        jobs: [dict(iCam, jCam, E [9], seeds [n][4] = x1, y1, x2, y2)].  The defaults are the reference's call (20.0, 0.45, 150).
-        Enqueues only."""
+    def _cams(self, cams):
         import numpy as np
 
         ca = (MergeMatchCam * max(len(cams), 1))()
@@ -753,6 +781,41 @@ class MergeMatcher(_MergeHandle):
             K = np.ascontiguousarray(c["K"], dtype=np.float64).reshape(9)
             keep.append(K)
             a.xy, a.state, a.K, a.imgSmall, a.imgScale = int(c["xy"]) or None, int(c["state"]) or None, K.ctypes.data, int(c["imgSmall"]) or None, float(c["imgScale"])
+        return ca, keep
+
+    def run_front(self, cams, Ws, Hs, pairs, front, min_surf_num=25, epi_max=20.0, ncc_min=0.45, max_disp=150.0, stream_ptr=None):
+        """cs_merge_match_run_front_dev: run() with E, the seed count and the seed rows of job k taken ON THE DEVICE from what
+        front.enqueue left (front: a MergeFront, or a dict results / seeds (device pointers) / rows (seed rows per job)); pairs:
+        [(iCam, jCam)], entry k is job k.  A job with surf_num < min_surf_num or without E is skipped (counts row [0, 4, 0, 0]), one with
+        more inliers than max_seeds gets [0, 8, 0, 0].  Enqueues only."""
+        if len(cams) != self.n_cams:
+            raise ValueError(f"MergeMatcher.run_front: {len(cams)} cameras, the handle has {self.n_cams}")
+        ca, _keep = self._cams(cams)
+        ja = (MergeFrontJob * max(len(pairs), 1))()
+        for a, (i, j) in zip(ja, pairs):
+            a.iCam, a.jCam = int(i), int(j)
+        src = front if isinstance(front, dict) else dict(results=front.buf.results, seeds=front.buf.seeds, rows=front.max_pts)
+        check(self._L.cs_merge_match_run_front_dev(self._m, self._stream(stream_ptr), ca, int(Ws), int(Hs), len(pairs), ja if len(pairs) else None,
+                                                   int(src["results"]) or None, int(src["seeds"]) or None, int(src["rows"]), int(min_surf_num),
+                                                   epi_max, ncc_min, max_disp), "cs_merge_match_run_front_dev")
+
+    def front_jobs(self, n_jobs, stream_ptr=None):
+        """cs_merge_match_front_jobs: what the last run_front made of jobs 0 .. n_jobs - 1 -> dict(F float64 [n][9], n_seeds, flags); waits"""
+        import numpy as np
+
+        arr = (MergeMatchFrontJob * max(int(n_jobs), 1))()
+        check(self._L.cs_merge_match_front_jobs(self._m, self._stream(stream_ptr), int(n_jobs), arr), "cs_merge_match_front_jobs")
+        rows = arr[:int(n_jobs)]
+        return dict(F=np.array([list(r.F) for r in rows], dtype=np.float64).reshape(-1, 9), n_seeds=np.array([r.nSeeds for r in rows], np.int32),
+                    flags=np.array([r.flags for r in rows], np.int32))
+
+    def run(self, cams, Ws, Hs, jobs, epi_max=20.0, ncc_min=0.45, max_disp=150.0, stream_ptr=None):
+        """cs_merge_match_run_dev.  cams: per camera a dict xy, state, imgSmall (device pointers), K (9 doubles, HOST array), imgScale;
+        jobs: [dict(iCam, jCam, E [9], seeds [n][4] = x1, y1, x2, y2)].  The defaults are the reference's call (20.0, 0.45, 150).
+        Enqueues only."""
+        import numpy as np
+
+        ca, keep = self._cams(cams)
         ja = (MergeMatchJob * max(len(jobs), 1))()
         for a, j in zip(ja, jobs):
             sd = np.ascontiguousarray(np.asarray(j.get("seeds", np.zeros((0, 4))), dtype=np.float64).reshape(-1, 4))

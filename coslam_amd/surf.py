@@ -20,15 +20,23 @@ class SurfBuffers(C.Structure):
 
 class Surf(_MergeHandle):
     """cs_surf: integral image -> fast-Hessian layers -> maxima in ascending (octave, layer, row, column) -> orientation -> descriptors, for
-    all cameras of a call in each launch.  Rows beyond a camera's count hold NaN key points and zero descriptors, so front_cams() hands
+    all cameras of a call in each launch.  keep="strongest": a camera with more than max_pts maxima keeps those of the largest response
+    (still in ascending order) instead of the first max_pts.  Rows beyond a camera's count hold NaN key points and zero descriptors, so front_cams() hands
     {pts, desc, n = max_pts} on with no wait."""
 
     _prefix, _Buffers = "cs_surf", SurfBuffers
 
-    def __init__(self, n_cams, W, H, max_pts, n_octaves=4, n_octave_layers=2, dim_desc=64, device=0):
+    KEEP = {"first": 0, "strongest": 1}   # CS_SURF_KEEP_FIRST, CS_SURF_KEEP_STRONGEST
+
+    def __init__(self, n_cams, W, H, max_pts, n_octaves=4, n_octave_layers=2, dim_desc=64, device=0, keep="first"):
+        if keep not in self.KEEP:
+            raise ValueError(f"Surf: keep is 'first' or 'strongest', not {keep!r}")
         self.n_cams, self.W, self.H, self.max_pts = int(n_cams), int(W), int(H), int(max_pts)
         self.n_octaves, self.n_layers, self.dim = int(n_octaves), int(n_octave_layers), int(dim_desc)
         self._create(device, self.n_cams, self.W, self.H, self.max_pts, self.n_octaves, self.n_layers, self.dim)
+        self.keep = keep
+        if keep != "first":   # beyond max_pts: the strongest responses instead of the first of the list
+            check(self._L.cs_surf_keep_set(self._m, self.KEEP[keep]), "cs_surf_keep_set")
 
     def _table(self, images):
         """images: per camera a device pointer (int), a torch uint8 tensor, or None (camera skipped) -> the host pointer table"""

@@ -1237,7 +1237,8 @@ int cs_merge_constraints_apply_map_dev(cs_merge_constraints* mc, void* hip_strea
 #define CS_MERGE_MATCH_MAX_JOBS 256
 struct cs_ncc_pair;   /* below: the NCC section */
 struct cs_ncc_cam;
-enum { CS_MERGE_MATCH_PAIRS_OVERFLOW = 1, CS_MERGE_MATCH_MATCHES_OVERFLOW = 2 };
+enum { CS_MERGE_MATCH_PAIRS_OVERFLOW = 1, CS_MERGE_MATCH_MATCHES_OVERFLOW = 2,
+       CS_MERGE_MATCH_SKIPPED = 4, CS_MERGE_MATCH_SEEDS_OVERFLOW = 8 /* cs_merge_match_run_front_dev alone sets these two */ };
 typedef struct {
     const double* xy;                 /* device, 2N */
     const int* state;                 /* device, N */
@@ -1263,6 +1264,7 @@ typedef struct {
     int nCams, N, maxJobs, maxSeeds, pairCap, maxMatches;
 } cs_merge_match_buffers;
 typedef struct { int count, flags, candidates, rounds; } cs_merge_match_count;
+typedef struct { double F[9]; int nSeeds; int flags; } cs_merge_match_front_job;   /* what cs_merge_match_run_front_dev made of a job */
 typedef struct cs_merge_match cs_merge_match;
 cs_merge_match* cs_merge_match_create(int device, int nCams, int N, int maxJobs, int maxSeeds, int pairCap, int maxMatches);
 void cs_merge_match_destroy(cs_merge_match* mm);
@@ -1386,6 +1388,25 @@ int cs_merge_front_buffers_get(const cs_merge_front* mf, cs_merge_front_buffers*
 /* bytes of one of the handle's device buffers to the host; waits for hip_stream */
 int cs_merge_front_download(cs_merge_front* mf, void* hip_stream, const void* d_src, void* h_dst, size_t bytes);
 
+/* The matcher fed by the front ON THE DEVICE: cs_merge_match_run_dev with E, the seed count and the seed rows of job k
+ * read from d_results[k] and d_seeds + k seedRowsPerJob 4 -- cs_merge_front_buffers.results / .seeds with seedRowsPerJob = maxPts, or any
+ * device memory of that layout -- instead of host memory.  Entry k is job k (no compaction); pairs[k] (host) names its cameras.  One small
+ * launch in front of the candidate lists decides per job:
+ *   surfNum < minSurfNum (the reference: 25) or ematOk == 0   the job is SKIPPED: counts row {0, CS_MERGE_MATCH_SKIPPED, 0, 0}
+ *   inlierNum > maxSeeds (or > seedRowsPerJob)                counts row {0, CS_MERGE_MATCH_SEEDS_OVERFLOW, 0, 0} (cs_merge_match_run_dev
+ *                                                             refuses such a job before any launch; here the number is the device's)
+ *   otherwise   F = iK1^T E^T iK2 from the device E in cs_merge_match_fmat's operation order -- the same bits -- with the inverses of the
+ *               cameras' K computed on the host; nSeeds = inlierNum; the seed rows are read in place; the matcher's job table is
+ *               filled on the device.  Candidates, matches and counts as cs_merge_match_run_dev's.
+ * A flagged job's F is NaN, which no pair passes: it has no candidates and no matches.  Enqueues only; the caller's one wait is
+ * cs_merge_match_counts.  cs_merge_match_front_jobs downloads {F, nSeeds, flags} of jobs 0 .. nJobs - 1 (a wait: tests, diagnostics).
+ * CS_ERR_INVALID before any launch: null handle / table, camera ids outside the rig, iCam == jCam, a singular K, seedRowsPerJob < 1,
+ * more than CS_MERGE_MATCH_MAX_JOBS jobs. */
+int cs_merge_match_run_front_dev(cs_merge_match* mm, void* hip_stream, const cs_merge_match_cam* cams /* host [nCams] */, int Ws, int Hs,
+                                 int nJobs, const cs_merge_front_job* pairs /* host */, const cs_merge_front_result* d_results,
+                                 const double* d_seeds, int seedRowsPerJob, int minSurfNum, double epiMax, double nccMin, double maxDisp);
+int cs_merge_match_front_jobs(cs_merge_match* mm, void* hip_stream, int nJobs, cs_merge_match_front_job* h_out);
+
 /* ---- SURF key points and descriptors: ::detectSURFPoints(img, surfPts, surfDesc) of mergeCamGroups (src/app/SL_MergeCameraGroup.cpp:
  * 308-313), the primitive of NewMapPtsSURF::detectSURFPoints and InitMap::matchSurfBetween as well; DESIGN.md 3.26 ----
  * The reference's SURF is external (OpenCV nonfree / asrl GPU-SURF): the definition is OURS, restated in numpy by
@@ -1400,6 +1421,11 @@ int cs_merge_front_download(cs_merge_front* mf, void* hip_stream, const void* d_
  *               the filter window: half a pixel up-left of the interpolated sample where L is even (every octave above the first)
  *   order       ascending (octave, layer, row, column) from counts and prefix sums; the first maxPts are kept, overflow counts the
  *               rest; rows >= count: NaN pts / size / angle / response, zero descriptor, zero integers
+ *   choice      cs_surf_keep_set(CS_SURF_KEEP_STRONGEST): a camera with more than maxPts maxima keeps the maxPts of the largest response
+ *               (f64 values; equals at the cut: the earlier in the order), written in the same ascending order, count = maxPts and
+ *               overflow = total - maxPts; a camera with no more than maxPts is byte for byte what CS_SURF_KEEP_FIRST (a new handle's
+ *               mode) gives.  A radix select on the device in front of the prefix sums: integer counts, no host wait; KEEP_FIRST
+ *               launches none of it
  *   orientation 109 Haar samples of size 4 s, 72 windows of 60 degrees every 5 degrees, sums in sample order (upright: angle 0)
  *   descriptor  20 s window, 4 x 4 subregions of 5 x 5 samples, Haar size 2 s, sigma 3.3 s; 64: {sum dx, sum dy, sum |dx|, sum |dy|},
  *               128: each split by the sign of the other component; unit L2 norm, f32; a zero norm gives a zero descriptor and NaN pts
@@ -1437,6 +1463,9 @@ cs_surf* cs_surf_create(int device, int nCams, int W, int H, int maxPts, int nOc
 void cs_surf_destroy(cs_surf* sf);
 int cs_surf_run_dev(cs_surf* sf, void* hip_stream, const unsigned char* const* d_img /* host [nCams] */, int pitch, double hessianThreshold,
                     int upright);
+/* which maxima a camera with more than maxPts of them keeps, from the next call on; CS_ERR_INVALID for another value */
+enum { CS_SURF_KEEP_FIRST = 0, CS_SURF_KEEP_STRONGEST = 1 };
+int cs_surf_keep_set(cs_surf* sf, int keep);
 /* the first stages alone: the integral images; those and the layer maps; those and the key-point lists (angle 0, descriptors zero) */
 int cs_surf_integral_dev(cs_surf* sf, void* hip_stream, const unsigned char* const* d_img /* host [nCams] */, int pitch);
 int cs_surf_layers_dev(cs_surf* sf, void* hip_stream, const unsigned char* const* d_img /* host [nCams] */, int pitch);

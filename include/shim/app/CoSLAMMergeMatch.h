@@ -8,6 +8,9 @@
 //     matcher.setSmallImageSize(Ws, Hs);                  // KeyPose::imgSmall: one size for the rig
 //     matcher.storeFeaturePoints(c, h_state);             // m_featPoints[c]: the slots with a feature (state 0 / 1), in slot order
 //     int n = matcher.matchFeaturePointsNCC(iCam, jCam, surfPts1, surfPts2, newMatches, E, featMatches[k], 20.0, 0.45, 150);   // :381-383
+//     int n = matcher.matchFeaturePointsNCCFront(iCam, jCam, fb.results + k, fb.seeds + 4 * (size_t)fb.maxPts * k, fb.maxPts, featMatches[k], 20.0, 0.45, 150);
+//                                                         // the same with E, the seed count and the seed rows read ON THE DEVICE from job k of a
+//                                                         // cs_merge_front (fb: its cs_merge_front_buffers); 0 matches for a job the front gave up
 //     matcher.matches_ptr()                               // the same matches as SLOT pairs in device memory: cs_merge_constraints_assemble_dev's d_matches
 //     CoSLAMMergeMatch::select(...)                       // the loop's choice: cs_merge_match_select
 //
@@ -66,8 +69,31 @@ public:
         job.iCam = iCam, job.jCam = jCam, job.nSeeds = surfMatches.num, job.seeds = seeds.data();
         for (int q = 0; q < 9; ++q) job.E[q] = E[q];
         if (cs_merge_match_run_dev(_mm, _stream, _cams, _Ws, _Hs, 1, &job, maxEpiErr, minNcc, maxDisp) != CS_OK) fail();
+        return finish(iCam, jCam, featMatches);
+    }
+
+    // the job's E, seed count and seed rows from device memory (cs_merge_match_run_front_dev): d_result one cs_merge_front_result, d_seeds its
+    // [seedRows][4] rows.  A job with fewer than minSurfNum SURF matches or without E is skipped: no matches, count.flags = CS_MERGE_MATCH_SKIPPED.
+    template <class MatchingT>
+    int matchFeaturePointsNCCFront(int iCam, int jCam, const cs_merge_front_result* d_result, const double* d_seeds, int seedRows,
+                                   MatchingT& featMatches, double maxEpiErr, double minNcc, double maxDisp, int minSurfNum = 25) {
+        cs_merge_front_job pair;
+        pair.iCam = at(iCam), pair.jCam = at(jCam);
+        if (cs_merge_match_run_front_dev(_mm, _stream, _cams, _Ws, _Hs, 1, &pair, d_result, d_seeds, seedRows, minSurfNum, maxEpiErr, minNcc, maxDisp) !=
+            CS_OK)
+            fail();
+        return finish(iCam, jCam, featMatches);
+    }
+
+private:
+    template <class MatchingT>
+    int finish(int iCam, int jCam, MatchingT& featMatches) {
         if (cs_merge_match_counts(_mm, _stream, 1, &count) != CS_OK) fail();
-        if (count.flags) throw std::runtime_error("CoSLAMMergeMatch: the candidate list or the matches overflowed the handle (flags " + std::to_string(count.flags) + ")");
+        if (count.flags == CS_MERGE_MATCH_SKIPPED) {
+            featMatches.clear();
+            return 0;
+        }
+        if (count.flags) throw std::runtime_error("CoSLAMMergeMatch: the candidate list or the matches or the seed rows overflowed the handle (flags " + std::to_string(count.flags) + ")");
         const int n = count.count;
         std::vector<int> slots(2 * (size_t)(n > 0 ? n : 1));
         std::vector<double> score(n > 0 ? n : 1);
@@ -79,6 +105,7 @@ public:
         return n;
     }
 
+public:
     // matchMergableCameras' loop over the gate's list (cs_merge_match_select): nccNum[e] = featMatches of entry e (0 where the entry was skipped)
     static cs_merge_match_choice select(int nInfo, const cs_merge_info* info, const int* surfNum, const unsigned char* ematOk, const int* nccNum,
                                         const cs_camera_groups& groups) {

@@ -7,7 +7,8 @@
 //
 // img is the reference's ImgG (rows, cols, data: rows x cols bytes), surfPts its Mat_d (resize(rows, cols), data: [n][2] = x, y), surfDesc
 // its vector<float> of n x dimDesc.  The reference's SURF is external; the definition is this library's.  The first form keeps
-// one handle per image size (CoSLAMSurfOptions: threshold, capacity, octaves, layers, dimension, upright).  Key points whose descriptor has
+// one handle per image size (CoSLAMSurfOptions: threshold, capacity, octaves, layers, dimension, upright, keep).  keep = CS_SURF_KEEP_STRONGEST: an
+// image with more than maxPts maxima keeps those of the largest response instead of the first maxPts of the list.  Key points whose descriptor has
 // zero norm (NaN coordinates) are left out of the lists.  Header-only and synchronous: upload, cs_surf_run_dev, counts, downloads.  Needs
 // the HIP runtime header (hipMalloc).
 #ifndef COSLAM_SURF_H
@@ -27,7 +28,9 @@ struct CoSLAMSurfOptions {
     double hessianThreshold;
     int maxPts, nOctaves, nOctaveLayers, dimDesc, upright, device;
     void* stream;
-    CoSLAMSurfOptions() : hessianThreshold(100.0), maxPts(4096), nOctaves(4), nOctaveLayers(2), dimDesc(64), upright(0), device(0), stream(0) {}
+    int keep;
+    CoSLAMSurfOptions()
+        : hessianThreshold(100.0), maxPts(4096), nOctaves(4), nOctaveLayers(2), dimDesc(64), upright(0), device(0), stream(0), keep(CS_SURF_KEEP_FIRST) {}
 };
 inline CoSLAMSurfOptions& coslamSurfOptions() {   // of the cached handles: set before the first call of an image size
     static CoSLAMSurfOptions o;
@@ -37,12 +40,13 @@ inline CoSLAMSurfOptions& coslamSurfOptions() {   // of the cached handles: set 
 // a caller-held single-camera handle
 template <class ImgT, class MatT>
 int detectSURFPoints(cs_surf* surf, const ImgT& img, MatT& surfPts, std::vector<float>& surfDesc, double hessianThreshold = 100.0, int upright = 0,
-                     void* hip_stream = 0) {
+                     void* hip_stream = 0, int keepMode = CS_SURF_KEEP_FIRST) {
     struct Fail {
         static void now(const char* what) { throw std::runtime_error(std::string("detectSURFPoints: ") + what + ": " + cs_last_error()); }
     };
     cs_surf_buffers b;
     if (cs_surf_buffers_get(surf, &b) != CS_OK) Fail::now("buffers");
+    if (cs_surf_keep_set(surf, keepMode) != CS_OK) Fail::now("keep");
     if (b.nCams != 1 || img.cols != b.W || img.rows != b.H) throw std::runtime_error("detectSURFPoints: the handle is of another image size, or not of one camera");
     unsigned char* d = 0;
     const size_t bytes = (size_t)b.W * b.H;
@@ -89,7 +93,7 @@ int detectSURFPoints(const ImgT& img, MatT& surfPts, std::vector<float>& surfDes
         sf = cs_surf_create(o.device, 1, img.cols, img.rows, o.maxPts, o.nOctaves, o.nOctaveLayers, o.dimDesc);
         if (!sf) throw std::runtime_error(std::string("detectSURFPoints: ") + cs_last_error());
     }
-    return detectSURFPoints(sf, img, surfPts, surfDesc, o.hessianThreshold, o.upright, o.stream);
+    return detectSURFPoints(sf, img, surfPts, surfDesc, o.hessianThreshold, o.upright, o.stream, o.keep);
 }
 
 #endif

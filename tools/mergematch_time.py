@@ -4,7 +4,12 @@ small images of 192 x 144, one job.  Timed: the blocks (k_mm_prep + the cutter: 
 (blocks, candidate list, matcher), and k_merge_match alone on the list the stage left (cs_merge_match_from_pairs_dev); the candidate list
 is the difference.  HIP events around back-to-back calls after a warm-up, the median of 7 blocks with their spread.  Recorded with them:
 the candidates that passed the epipolar / NCC test, the matches, and the matcher's round count.  Two textures: white noise blurred once
-(decorrelates within a few pixels) and a smooth one (blurred 12 times: far more pairs pass nccMin).  Nothing is gated."""
+(decorrelates within a few pixels) and a smooth one (blurred 12 times: far more pairs pass nccMin).  Nothing is gated.
+
+--front: descriptors -> pair choice on the scene of tests/mergefront_e2e.py (3 entries: skipped, no E, the true pair), the stretch of
+MergeCamGroups.run_from_descriptors up to the counts merge_match_select reads: host-fed (MergeFront.run -> MergeMatcher.run -> counts) against
+device-fed (MergeFront.enqueue -> MergeMatcher.run_front -> counts, results).  Wall time per call (median of 30 after 5, with the spread),
+the calls that synchronise the stream, and how many of them found work in flight (the waits that stall the host)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -36,6 +41,65 @@ def smooth(img, times):
     f = (f - f.min()) / (f.max() - f.min())
     return np.ascontiguousarray((f * 255).astype(np.uint8))
 
+
+def front_mode():
+    import time
+    from tests import mergefront_dev as FD, mergefront_e2e as FE, mergematch_e2e as E2
+
+    S, cams, infos, front_cams, _want = FE.build()
+    dc, keep = D.upload_cams(cams)
+    fc, keep2 = FD.upload_cams(front_cams)
+    pairs = [(int(i[1]), int(i[4])) for i in infos]
+    mm = coslam_amd.MergeMatcher(S["nC"], S["N"], 4, S["N"], 1 << 14, S["N"])
+    mf = coslam_amd.MergeFront(S["nC"], S["N"], FE.DIM, 4, FE.N_RANSAC)
+    stream = torch.cuda.current_stream()
+    waits = dict(calls=0, stalled=0)
+
+    def counted(obj, name):
+        inner = getattr(obj, name)
+
+        def call(*a, **k):
+            waits["calls"] += 1
+            waits["stalled"] += 0 if stream.query() else 1
+            return inner(*a, **k)
+        setattr(obj, name, call)
+    counted(mf, "results"), counted(mf, "_down"), counted(mm, "counts")
+
+    def host_fed():
+        got = mf.run(fc, pairs, n_ransac=FE.N_RANSAC, seed=FE.GEN_SEED)
+        jl = [dict(iCam=p[0], jCam=p[1], E=g["E"], seeds=g["seeds"]) for p, g in zip(pairs, got) if g["surf_num"] >= 25 and g["emat_ok"]]
+        mm.run(dc, E2.WS, E2.HS, jl)
+        return mm.counts(len(jl))[-1]
+
+    def device_fed():
+        mf.enqueue(fc, pairs, n_ransac=FE.N_RANSAC, seed=FE.GEN_SEED)
+        mm.run_front(dc, E2.WS, E2.HS, pairs, mf)
+        cnt = mm.counts(len(pairs))
+        mf.results(len(pairs))
+        return cnt[-1]
+
+    rows = []
+    for name, run in (("host-fed jobs", host_fed), ("device-fed jobs", device_fed)) if hasattr(coslam_amd.lib(), "cs_merge_match_run_front_dev") \
+            else (("host-fed jobs", host_fed),):
+        for _ in range(5): last = run()
+        ts = []
+        for _ in range(30):
+            torch.cuda.synchronize()
+            waits.update(calls=0, stalled=0)
+            t0 = time.perf_counter()
+            last = run()
+            ts.append((time.perf_counter() - t0) * 1e6)
+        rows.append(last.tolist())
+        print(f"{name:16s}: {np.median(ts):8.1f} us wall per call ({min(ts):.1f} .. {max(ts):.1f}); {waits['calls']} synchronising calls, "
+              f"{waits['stalled']} with work in flight; true pair's count row {last.tolist()}")
+    assert all(r == rows[0] for r in rows)
+    print(f"seed rows the host-fed path downloads and uploads again: {len(pairs)} x {mf.max_pts} x 32 = {len(pairs) * mf.max_pts * 32} bytes down")
+    mm.close(), mf.close()
+
+
+if "--front" in sys.argv:
+    front_mode()
+    sys.exit(0)
 
 for N in (120, 2000):
     for name, blur in (("noise", 0), ("smooth", 12)):
