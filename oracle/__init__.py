@@ -1316,10 +1316,12 @@ def keyframe_ready(state, slot2map, R, t, selfR, selfT, keyFrame, keyMapped, map
     return 0, n_static, num, cen
 
 
-def intracam_new_points(K, iK, histR, histT, histXY, state, slot2map, trackSpan, isStatic, minTrackLen, maxEpiErr, sigma, cmpAcos=False):
-    """opu_intracam_new_points (SingleSLAM::newMapPoints for one camera): histR (nHist x 9), histT (nHist x 3), histXY (nHist x 2N), entry 0 =
-    this frame; state / slot2map int32[N], trackSpan int32[2N], isStatic uint8[N].  Returns (slots, firstFrames, M [n x 3], cov [n x 9])
-    in slot order."""
+def intracam_new_points(K, iK, histR, histT, histXY, state, slot2map, trackSpan, isStatic, minTrackLen, maxEpiErr, sigma, cmpAcos=False,
+                        maxWalk=None):
+    """opu_intracam_new_points / opu_intracam_new_points_walk (SingleSLAM::newMapPoints for one camera): histR (nHist x 9), histT (nHist x 3),
+    histXY (nHist x 2N), entry 0 = this frame; state / slot2map int32[N], trackSpan int32[2N], isStatic uint8[N].  maxWalk: the refinement walk looks at no more than that
+    many nodes of the track, the feature itself included (None: unbounded, the reference's).  Returns (slots, firstFrames, M [n x 3],
+    cov [n x 9]) in slot order."""
     L = lib()
     L.opu_intracam_new_points.restype = C.c_int
     histR = np.ascontiguousarray(histR, dtype=np.float64)
@@ -1333,8 +1335,13 @@ def intracam_new_points(K, iK, histR, histT, histXY, state, slot2map, trackSpan,
     assert histT.shape == (nH, 3) and histXY.shape == (nH, 2 * N) and len(st) == len(s2m) == len(fs) == N and len(sp) == 2 * N
     slot, first = np.zeros(N, np.int32), np.zeros(N, np.int32)
     M, cov = np.zeros((N, 3)), np.zeros((N, 9))
-    n = L.opu_intracam_new_points(_p(K), _p(iK), N, nH, _p(histR), _p(histT), _p(histXY), _p(st), _p(s2m), _p(sp), _p(fs), int(minTrackLen),
-                                  C.c_double(maxEpiErr), C.c_double(sigma), int(bool(cmpAcos)), _p(slot), _p(first), _p(M), _p(cov))
+    head = (_p(K), _p(iK), N, nH, _p(histR), _p(histT), _p(histXY), _p(st), _p(s2m), _p(sp), _p(fs), int(minTrackLen), C.c_double(maxEpiErr),
+            C.c_double(sigma), int(bool(cmpAcos)))
+    if maxWalk is None:
+        n = L.opu_intracam_new_points(*head, _p(slot), _p(first), _p(M), _p(cov))
+    else:
+        L.opu_intracam_new_points_walk.restype = C.c_int
+        n = L.opu_intracam_new_points_walk(*head, int(maxWalk), _p(slot), _p(first), _p(M), _p(cov))
     return slot[:n].copy(), first[:n].copy(), M[:n].copy(), cov[:n].copy()
 
 

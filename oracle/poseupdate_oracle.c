@@ -468,6 +468,9 @@ int opu_refine_map_points_ref(int nCams, int N, int nHist, const double* Ks, con
  * triangulates the current view with the widest-parallax one of the track, and the tests run once more.  A dynamic feature stops the
  * walk (:938-944): the slot's type (isStatic) stands for the whole track here.
  * hist* [nHist] with entry 0 = this frame; histXY [nHist][2N]; trackSpan [2N]; state / slot2map / isStatic [N].
+ * maxWalk: the refinement looks at no more than that many nodes of the track, the feature itself included (entries 1 .. maxWalk - 1: the
+ * device's bound on its walks, cs_newpts_intracam_dev; the reference has none); <= 0: unbounded.  The first triangulation's oldest view is
+ * not affected.
  * Out, in slot order: newSlot, newFirst (MapPoint::firstFrame = the oldest view's frame), newM [..][3], newCov [..][9].  Returns the count.
  * PARITY: the loop is pinned against the reference's own function compiled in place (tests/cxx/ref_intracam_newpts_test.cpp ->
  * tests/golden/intracam_newpts_golden.npz); binTriangulate / getBinTriangulateCovMat = triangulateMultiView / getTriangulateCovMat over
@@ -501,9 +504,10 @@ static double reproj_err(const double* K, const double* R, const double* t, cons
 }
 static int behind(const double* R, const double* t, const double* M) { return ((R[6] * M[0] + R[7] * M[1]) + R[8] * M[2]) + t[2] < 0; }
 
-int opu_intracam_new_points(const double* K, const double* iK, int N, int nHist, const double* histR, const double* histT, const double* histXY,
-                            const int* state, const int* slot2map, const int* trackSpan, const unsigned char* isStatic, int minTrackLen,
-                            double maxEpiErr, double sigma, int cmpAcos, int* newSlot, int* newFirst, double* newM, double* newCov) {
+static int intracam_new_points_core(const double* K, const double* iK, int N, int nHist, const double* histR, const double* histT,
+                                    const double* histXY, const int* state, const int* slot2map, const int* trackSpan,
+                                    const unsigned char* isStatic, int minTrackLen, double maxEpiErr, double sigma, int cmpAcos, int maxWalk,
+                                    int* newSlot, int* newFirst, double* newM, double* newCov) {
     int n = 0;
     for (int k = 0; k < N; k++) {
         if (state[k] != 0 && state[k] != 1) continue;                  /* tk.empty() */
@@ -528,7 +532,8 @@ int opu_intracam_new_points(const double* K, const double* iK, int N, int nHist,
         /* refineTriangulation(cur_fp, M, cov): the current view and the widest-parallax one behind it */
         int best = -1;
         double bestCos = 1.0, bestAngle = 0.0;
-        for (int j = 1; j <= jp; j++) {
+        const int jw = maxWalk > 0 && maxWalk - 1 < jp ? maxWalk - 1 : jp; /* the walk bound: the feature itself is node 0 */
+        for (int j = 1; j <= jw; j++) {
             double Cj[3];
             cam_center(histR + 9 * (size_t)j, histT + 3 * (size_t)j, Cj);
             const double cv = cos_between(M, org, Cj);
@@ -551,6 +556,22 @@ int opu_intracam_new_points(const double* K, const double* iK, int N, int nHist,
         n++;
     }
     return n;
+}
+
+/* the reference's function: the walk unbounded */
+int opu_intracam_new_points(const double* K, const double* iK, int N, int nHist, const double* histR, const double* histT, const double* histXY,
+                            const int* state, const int* slot2map, const int* trackSpan, const unsigned char* isStatic, int minTrackLen,
+                            double maxEpiErr, double sigma, int cmpAcos, int* newSlot, int* newFirst, double* newM, double* newCov) {
+    return intracam_new_points_core(K, iK, N, nHist, histR, histT, histXY, state, slot2map, trackSpan, isStatic, minTrackLen, maxEpiErr, sigma,
+                                    cmpAcos, 0, newSlot, newFirst, newM, newCov);
+}
+/* the same under the device's walk bound (maxWalk, above); a separate entry, so that a caller of the one above keeps its argument list */
+int opu_intracam_new_points_walk(const double* K, const double* iK, int N, int nHist, const double* histR, const double* histT,
+                                 const double* histXY, const int* state, const int* slot2map, const int* trackSpan, const unsigned char* isStatic,
+                                 int minTrackLen, double maxEpiErr, double sigma, int cmpAcos, int maxWalk, int* newSlot, int* newFirst,
+                                 double* newM, double* newCov) {
+    return intracam_new_points_core(K, iK, N, nHist, histR, histT, histXY, state, slot2map, trackSpan, isStatic, minTrackLen, maxEpiErr, sigma,
+                                    cmpAcos, maxWalk, newSlot, newFirst, newM, newCov);
 }
 
 /* ---- CoSLAM::mapPointsClassify (/root/reference/src/app/SL_CoSLAM.cpp:418-520) --------------------------------------------------
